@@ -7,8 +7,14 @@ One "step" of this bench = one pass of the hot path over one batch: the fused
 multiple-shooting transcription, B x H = 4096 x 50 = 204 800 units, through the 5-128-128-128-128-6
 tanh surrogate in fp32 (BASELINE configs[2]).  value = units / second (whole job, all ranks).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline value, ms_per_step, and the roofline
+figures derived from the same timed events).  --full adds everything reported beside the headline: the strong-scaled job
+(N > 1), the forward-only and rollout passes, the second-order and closed-loop figures (N = 1), the CPU baseline and the
+in-run parity check against the float64 oracle (N = 1, exit code 5 when it fails).  --dump-outputs DIR writes F, A, B
+of the last timed step (rank 0) as DIR/<name>.npy, see dump_outputs().
 
 Launching: under a launcher (RANK / WORLD_SIZE set) this process is one rank.  WITHOUT a launcher and with
 --gpus N > 1, main() starts N fresh rank processes itself — as its very first action, before anything touches the
@@ -17,8 +23,8 @@ ranks do not add up to --gpus exits non-zero: it never prints a single-GPU numbe
 
 Scaling: the top-level numbers are WEAK-scaled (every rank owns its own B = 4096 instances; independent MPC
 instances / random restarts shard with no data-path collective).  For N > 1 the same invocation also times the
-STRONG-scaled job the metric's wording names (B = 4096 in total, sharded with shard_bounds) and reports it in the
-"strong" object of the same JSON line.  After the K timed sweeps — once per solve, inside the timed region — the
+STRONG-scaled job the metric's wording names (B = 4096 in total, sharded with shard_bounds) with --full and reports it in
+the "strong" object of the same JSON line.  After the K timed sweeps — once per solve, inside the timed region — the
 ranks all-gather their best trajectory record over RCCL (the one exchange the path has).  Inputs are synthetic
 (seed 42) and resident in HBM before the timed region.
 """
@@ -53,9 +59,15 @@ def parse(argv=None):
     ap.add_argument("--horizon", type=int, default=50)
     ap.add_argument("--hidden", type=str, default="128,128,128,128")
     ap.add_argument("--scaling", choices=("both", "weak", "strong"), default="both",
-                    help="N > 1: which job(s) to time; the top-level value is the weak one unless 'strong' is chosen")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the second-order / closed-loop figures reported alongside")
+                    help="N > 1: which job(s) to time; the top-level value is the weak one unless 'strong' is chosen; "
+                         "'both' times the strong job beside it with --full only")
+    ap.add_argument("--full", action="store_true",
+                    help="also time and check what is reported beside the headline (strong scaling, forward / rollout "
+                         "passes, second-order and closed-loop figures, CPU baseline, in-run parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write F, A, B of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the in-run parity")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the second-order / closed-loop figures")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample (both legs together)")
     ap.add_argument("--no-mfma", action="store_true", help="VALU matmul path (BASELINE cfg2 'MFMA off')")
     return ap.parse_args(argv)
@@ -264,6 +276,39 @@ def parity_in_run(kept, F, A, Bm, tol=1e-5):
                     "float64 oracle on the same first `units` (x_k,u_k) units; every unit on its own (max norm), nothing masked"}
 
 
+DUMP_MAX_BYTES = 60_000_000  # under 64 MB in all, .npy headers included
+DUMP_SEED = 0
+
+
+def dump_outputs(path, F, A, Bm):
+    """Write what the timed path returned in its last step, F (H,13,B), A (H,13,13,B), B (H,13,7,B), as float32
+    path/F.npy, path/A.npy, path/B.npy.  When the three exceed DUMP_MAX_BYTES, the same fixed sample of instances (a
+    seeded draw without replacement from the B instances, ascending, every node of each) is written from all three:
+    shapes (H,13,m), (H,13,13,m), (H,13,7,m).  The draw depends only on (H, B), so two builds run with the same arguments
+    write the same units.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+
+    H, _, B = F.shape
+    per_instance = (F[..., 0].numel() + A[..., 0].numel() + Bm[..., 0].numel()) * 4
+    m = min(B, DUMP_MAX_BYTES // per_instance)
+    if m < 1:
+        raise ValueError(f"one instance of H={H} nodes is {per_instance} B, over the {DUMP_MAX_BYTES} B dump budget")
+    idx = None
+    if m < B:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=m, replace=False))
+        idx = torch.from_numpy(idx).to(F.device)
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in (("F", F), ("A", A), ("B", Bm)):
+        if idx is not None:
+            t = t.index_select(t.dim() - 1, idx)
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def strong_model(batch, H, world, headline_kernel, cus=256):
     """What DESIGN.md §7 predicts for the strong-scaled job before launch and gather costs, so that a SCALE run explains
     itself: the headline kernel runs in rounds of 64 units per CU; a remainder of at most half a round goes to the
@@ -392,7 +437,12 @@ def run_rank(args):
     flops_unit = 24 * F_mlp + 30000          # SURVEY.md §8d contract figure (4 stages x (1 value + 5 tangents))
     bytes_unit = 1172                         # read x,u (80 B) + write x+, A, B (1092 B)
 
-    modes = ["weak"] if world == 1 else (["weak", "strong"] if args.scaling == "both" else [args.scaling])
+    if world == 1:
+        modes = ["weak"]
+    elif args.scaling == "both":
+        modes = ["weak", "strong"] if args.full else ["weak"]
+    else:
+        modes = [args.scaling]
     results = {}
     for mode in modes:
         if mode == "weak":
@@ -409,21 +459,25 @@ def run_rank(args):
     kern_ms = primary["kern_ms"]
     name, grid, block, lds = primary["launch"]
     X, U, Fbuf = primary["X"], primary["U"], primary["F"]
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, Fbuf, primary["A"], primary["Bm"])
 
-    # reported alongside the headline: forward-only passes of the same units, untimed by the driver
-    def _time(fn, iters=10):
-        fn(); torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / iters
-    traj = torch.empty((H + 1, 13, B), device=dev)
-    x0 = X[0].contiguous()
-    Falong = torch.empty_like(Fbuf)  # the alongside passes write HERE: F, A, B of the timed sweeps stay as the timed kernel left them
-    fwd_ms = _time(lambda: ms.propagate(X, U, out=Falong))
-    roll_ms = _time(lambda: ms.rollout(x0, U, out=traj), 5)
+    if args.full:
+        # reported alongside the headline: forward-only passes of the same units, untimed by the driver
+        def _time(fn, iters=10):
+            fn(); torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record(); torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / iters
+        traj = torch.empty((H + 1, 13, B), device=dev)
+        x0 = X[0].contiguous()
+        Falong = torch.empty_like(Fbuf)  # the alongside passes write HERE: F, A, B of the timed sweeps stay as the timed kernel left them
+        fwd_ms = _time(lambda: ms.propagate(X, U, out=Falong))
+        roll_ms = _time(lambda: ms.rollout(x0, U, out=traj), 5)
 
     # HBM traffic of the dominant kernel from the PMC passes (FETCH_SIZE x2 per the gfx950 guide + WRITE_SIZE, calibrated
     # on a known-byte-count kernel of the same access pattern): collected separately with rocprofv3 --pmc and committed
@@ -487,15 +541,18 @@ def run_rank(args):
                              "batch_per_gpu": s["B"], "units_per_step": s["units_per_step"], "kernel_ms_rank0": s["kern_ms"], "gather_ms": s["gather_ms"],
                              "note": "the SAME B x H units as the 1-GPU run, sharded over the ranks (the metric's wording); "
                                      "speed-up over N=1 = this value / the N=1 run's value"}
-        res["alongside"] = {
-            "forward_shooting_steps_per_s_per_gpu": B * H / fwd_ms * 1e3, "forward_shooting_ms": fwd_ms,
-            "forward_flops_per_unit": 4 * F_mlp + 1500,
-            "forward_tflops": (4 * F_mlp + 1500) * B * H / (fwd_ms * 1e-3) / 1e12,
-            "rollout_steps_per_s_per_gpu": B * H / roll_ms * 1e3, "rollout_ms": roll_ms,
-            "note": "same units, x+ only: ac_shoot_step_f32 (all nodes independent) and ac_rollout_f32 (sequential in k)"}
-        if world == 1 and not args.no_extras:
+        if dumped is not None:
+            res["outputs"] = {"dir": args.dump_outputs, "shapes": dumped, "dtype": "float32"}
+        if args.full:
+            res["alongside"] = {
+                "forward_shooting_steps_per_s_per_gpu": B * H / fwd_ms * 1e3, "forward_shooting_ms": fwd_ms,
+                "forward_flops_per_unit": 4 * F_mlp + 1500,
+                "forward_tflops": (4 * F_mlp + 1500) * B * H / (fwd_ms * 1e-3) / 1e12,
+                "rollout_steps_per_s_per_gpu": B * H / roll_ms * 1e3, "rollout_ms": roll_ms,
+                "note": "same units, x+ only: ac_shoot_step_f32 (all nodes independent) and ac_rollout_f32 (sequential in k)"}
+        if args.full and world == 1 and not args.no_extras:
             res["alongside"].update(extras(ac, ms, X, U, dev))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the SAME numbers the GPU got: rounded to fp32 once, handed to the float64 oracle
             Xh = primary["Xh"].astype(np.float32).astype(np.float64)
             Uh = primary["Uh"].astype(np.float32).astype(np.float64)
@@ -519,6 +576,9 @@ def main(argv=None):
     args = parse(argv)
     if args.gpus < 1:
         log("[bench] --gpus must be >= 1")
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        log("[bench] --steps must be >= 1 and --warmup >= 0")
         return 2
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus, argv)  # first thing: nothing has touched the GPU in this process

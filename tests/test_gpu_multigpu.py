@@ -208,7 +208,7 @@ def _run_bench(extra, env_extra, timeout=600):
 def test_bench_two_rank_rehearsal_on_one_gpu(gpu):
     """`python bench.py --gpus 2` with no launcher starts two fresh ranks itself (here both on cuda:0, gloo collectives)
     and reports n_gpus = ranks_seen = 2 with weak- and strong-scaled figures; the N = 1 line has the same keys."""
-    r = _run_bench(["--gpus", "2"], {"AIRCRAFT_BENCH_ONE_GPU": "1", "AIRCRAFT_BENCH_BACKEND": "gloo"})
+    r = _run_bench(["--gpus", "2", "--full"], {"AIRCRAFT_BENCH_ONE_GPU": "1", "AIRCRAFT_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["n_gpus"] == 2 and res["ranks_seen"] == 2 and res["scaling"] == "weak"
@@ -217,6 +217,23 @@ def test_bench_two_rank_rehearsal_on_one_gpu(gpu):
     assert s["scaling"] == "strong" and s["batch_total"] == 512 and s["batch_per_gpu"] == 256
     assert s["units_per_step"] == 512 * 50 and s["value"] > 0 and res["value"] > 0
     assert res["roofline"]["frac"] > 0 and "cpu_baseline" not in res  # baseline leg is rank-0-at-N=1 only
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_outputs(gpu, tmp_path):
+    """A plain `bench.py --gpus 1` line carries the headline and ms_per_step of exactly --steps timed steps and nothing that
+    needs passes of its own; --dump-outputs writes F, A, B of the last timed step (all of them at this size), finite fp32."""
+    r = _run_bench(["--gpus", "1", "--dump-outputs", str(tmp_path)], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["n_gpus"] == 1 and res["steps"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0
+    assert res["unit"] == "horizon-steps/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert not {"alongside", "cpu_baseline", "parity_in_run", "strong"} & set(res)
+    H, B = 50, 512
+    want = {"F": (H, 13, B), "A": (H, 13, 13, B), "B": (H, 13, 7, B)}
+    assert res["outputs"]["shapes"] == {k: list(v) for k, v in want.items()}
+    for name, shape in want.items():
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.shape == shape and a.dtype == np.float32 and np.isfinite(a).all()
 
 
 def test_bench_refuses_a_mislabelled_run(gpu):

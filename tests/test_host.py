@@ -318,6 +318,50 @@ def test_bench_in_run_parity_gate_catches_one_bad_unit():
     assert r["state_block_rel_max"] > 0 and (r["ok"] == (r["state_block_rel_max"] <= 1e-5))
 
 
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
+    """bench.py --dump-outputs: F, A, B as float32 .npy; the full arrays when they fit, otherwise the same seeded sample of
+    instances (every node) from all three, identical from run to run and under the 64 MB bound.  A plain run is lean:
+    --full is off by default, --steps below 1 is refused before anything else runs."""
+    import subprocess
+    import sys
+
+    import torch
+
+    import bench
+
+    assert not bench.parse([]).full and bench.parse(["--full"]).full
+    assert bench.parse(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
+
+    rng = np.random.default_rng(3)
+    H, B = 2, 6
+    F, A, Bm = (torch.from_numpy(rng.normal(size=s).astype(np.float32)) for s in ((H, 13, B), (H, 13, 13, B), (H, 13, 7, B)))
+    shapes = bench.dump_outputs(str(tmp_path / "small"), F, A, Bm)
+    assert shapes == {"F": [H, 13, B], "A": [H, 13, 13, B], "B": [H, 13, 7, B]}
+    for name, t in (("F", F), ("A", A), ("B", Bm)):
+        a = np.load(tmp_path / "small" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.numpy())
+
+    H, B = 50, 4096  # the headline size: 223 MB in full, so a sample is written
+    F, A, Bm = torch.zeros((H, 13, B)), torch.zeros((H, 13, 13, B)), torch.zeros((H, 13, 7, B))
+    tag = torch.arange(B, dtype=torch.float32)
+    F[:] = tag; A[:] = tag; Bm[:] = tag  # every entry holds its instance index
+    s1 = bench.dump_outputs(str(tmp_path / "a"), F, A, Bm)
+    s2 = bench.dump_outputs(str(tmp_path / "b"), F, A, Bm)
+    assert s1 == s2 and s1["F"][:2] == [H, 13] and s1["A"][:3] == [H, 13, 13] and s1["B"][:3] == [H, 13, 7]
+    m = s1["F"][-1]
+    assert 0 < m < B and s1["A"][-1] == m and s1["B"][-1] == m
+    total = sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in ("F", "A", "B"))
+    assert total <= 64_000_000
+    picked = np.load(tmp_path / "a" / "F.npy")[0, 0]
+    assert np.all(np.diff(picked) > 0)  # distinct instances, ascending
+    for n in ("F", "A", "B"):
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert np.array_equal(a, b) and np.all(a == picked)  # same instances in all three, every node and entry
+
+
 def test_quiet_capture_pauses_the_garbage_collector_and_restores_it(monkeypatch):
     """control.moving_horizon.quiet_capture: collector run before, disabled inside, restored after — also when the body or the
     capture itself raises (a finaliser's hipFree during a capture invalidates the graph; DESIGN §5 / INTEGRATION)."""

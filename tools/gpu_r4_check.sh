@@ -14,4 +14,4 @@ for l in open(sys.argv[1]):
     d = json.loads(l)
     print(f"{d['case']:40s} sens {d['sens_ms']*1e3:8.1f} us {d['sens_steps_per_s']:.3e}/s  fwd {d['fwd_ms']*1e3:7.1f} us  rollout {d['rollout_ms']*1e3:7.1f} us  [{d['sens_kernel']}]")
 PY
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json
