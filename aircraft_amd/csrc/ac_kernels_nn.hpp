@@ -40,7 +40,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_nn_step_sens(const DevParams P, c
                                                             float* __restrict__ Xn, float* __restrict__ A,
                                                             float* __restrict__ Bm, float* __restrict__ c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    MlpEngine<6, WT, USE_MFMA> eng(plan, blob, smem);
+    typedef MlpEngine<6, WT, USE_MFMA, true, false, 0, 0, kBf16Hidden && USE_MFMA && WT == 8> Engine;  // (plan_bf when bf16)
+    Engine eng(plan, blob, smem);
     eng.st.start();
     WaveClock wc;
     wc.start();
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_nn_step_sens(const DevParams P, c
     unsigned long long* stamp_buf = reinterpret_cast<unsigned long long*>(c);
     c = nullptr;
 #endif
-    MlpCoeffs<MlpEngine<6, WT, USE_MFMA>> coeffs(eng);
+    MlpCoeffs<Engine> coeffs(eng);
     // PERSISTENT workgroups: the grid is at most one workgroup per CU and workgroup b runs the tasks (64 units each)
     // b, b + gridDim.x, ...  With one 138 KB workgroup resident per CU, a workgroup per task had every CU idle between the
     // last wave of one task and the first of the next (dispatch + the weight prologue: -DAC_CLOCKS measured a wave lifetime
@@ -216,10 +217,10 @@ __global__ __launch_bounds__(kBlock, 1) void k_nn_step_sens_pair(const DevParams
     // behind the plan's image: [2 pairs][WT KiB] value activations, then [2 pairs][16 units][36] outputs
     float* xch = reinterpret_cast<float*>(smem + plan.lds_total + 2 * WT * 1024) + pair * (16 * 36);
     if (role == 0)
-        sens_pair_body<MlpEngine<3, WT, true, true, false, 0, 1>, 0>(P, plan, blob, smem, xch, true, X, U, dt, dt_per_unit, n,
+        sens_pair_body<MlpEngine<3, WT, true, true, false, 0, 1, kBf16Hidden && WT == 8>, 0>(P, plan, blob, smem, xch, true, X, U, dt, dt_per_unit, n,
                                                                       blk, unit0, pair, Xn, A, Bm, c);
     else
-        sens_pair_body<MlpEngine<3, WT, true, true, false, 2, 2>, 2>(P, plan, blob, smem, xch, false, X, U, dt, dt_per_unit, n,
+        sens_pair_body<MlpEngine<3, WT, true, true, false, 2, 2, kBf16Hidden && WT == 8>, 2>(P, plan, blob, smem, xch, false, X, U, dt, dt_per_unit, n,
                                                                       blk, unit0, pair, Xn, A, Bm, c);
 }
 

@@ -37,7 +37,17 @@ struct MlpPlan {
     int first_streamed;          // index of the first streamed layer (-1 if none)
     int streamed[AC_MAX_LAYERS]; // layer index of the i-th streamed layer, i < n_streamed
     int lds_total;               // dynamic LDS bytes to request
+    int bf_region[3];            // plan_bf / plan_bf_pair: byte offsets of the half-layer regions of the bf16 hidden layers
 };
+
+// The sensitivity engines of the two headline kernels (k_nn_step_sens<8, true>, k_nn_step_sens_pair<8>) run their hidden
+// layers on bf16 MFMA with three-plane operands (MlpEngine::layer_bf).  -DAC_HIDDEN_FP32 (in those two units
+// AND in aircraft_hip.hip, which then hands them plan_sens) builds the fp32 form of round 4 for A/B measurements.
+#ifdef AC_HIDDEN_FP32
+constexpr bool kBf16Hidden = false;
+#else
+constexpr bool kBf16Hidden = true;
+#endif
 
 // ---- 16x16x4 fp32 matrix-multiply-accumulate on one wave -------------------------------------
 // "MFMA off" validation path: the same contraction with cross-lane reads on the VALU.
@@ -105,17 +115,28 @@ template <> struct TripleHolder<false> {
     AC_DI int tri(int) const { return 0; }
 };
 
+// Ring state of the bf16 hidden layers (layer_bf); empty in every other engine, for the reason above.
+template <bool ON> struct BfRingState {
+    int bf_front = 0;              // region index of the front half of the layer about to be acquired (three-region ring)
+    const char* bf_back = nullptr; // LDS address of the back half of the current layer
+    const float* bf_next_src = nullptr;  // front half of the next streamed layer, requested behind the mid-layer barrier
+    int bf_next_dst = 0;
+};
+template <> struct BfRingState<false> {};
+
 // PAIR (k_nn_step_sens_pair: two waves share the six slabs of one unit group, three each): 1 = the wave with the value slab and
 // tangents TOFF, TOFF + 1 — it publishes every hidden layer's value activations h through LDS (`hx`); 2 = the wave with three
 // tangent slabs and NO value slab — its hidden-layer outputs stay unscaled until it has read h behind the next barrier
 // (scale_from_hx).  Both roles meet at the same workgroup barriers: one at the head of every hidden layer, one after the second
 // slab of it (between the reader's load of h and the writer's next store), one before the last layer.
-template <int NSLAB, int WT, bool USE_MFMA, bool TANGENT = (NSLAB == 6), bool SECOND = false, int TOFF = 0, int PAIR = 0>
-struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10> {
+template <int NSLAB, int WT, bool USE_MFMA, bool TANGENT = (NSLAB == 6), bool SECOND = false, int TOFF = 0, int PAIR = 0,
+          bool BF = false>
+struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     using TripleHolder<SECOND && NSLAB <= 10>::tri;
     static constexpr bool kNoValue = PAIR == 2;  // every slab is a tangent slab
     static constexpr int kFirstTangent = kNoValue ? 0 : 1;  // slab index of tangent TOFF
     static_assert(PAIR == 0 || (TANGENT && USE_MFMA && NSLAB == 3), "wave-pair roles: three slabs each, matrix-core flavour");
+    static_assert(!BF || (TANGENT && USE_MFMA && WT == 8), "bf16 hidden layers: the width-128 sensitivity engines");
     static_assert(!TANGENT || (NSLAB >= 2 && NSLAB <= 6 && TOFF + NSLAB - kFirstTangent <= 5), "tangent mode = value + a range of the 5 input tangents");
     static constexpr int kTangents = TANGENT ? NSLAB - kFirstTangent : 0;
     // second-order mode over K inputs (a triple (p, q, r) set with set_triple(), NSLAB = 10; or all five, NSLAB = 21):
@@ -192,7 +213,11 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10> {
     AC_DI void load_weights() {
         for (int l = 0; l < plan.n_layers; ++l)
             if (plan.lds_off[l] >= 0) lds_dma_copy(gblob + plan.g_off[l], lds + plan.lds_off[l], plan.bytes[l], wave, nwaves, lane);
-        if (plan.n_streamed > 0) {
+        if constexpr (BF) {
+            // three-region ring: the front half of the first hidden layer into region 0 (the wave-pair ring loads on acquire)
+            if (!kPairRing && plan.n_streamed > 0)
+                lds_dma_copy(gblob + plan.g_off[plan.first_streamed], lds + plan.bf_region[0], kBfFront, wave, nwaves, lane);
+        } else if (plan.n_streamed > 0) {
             const int l = plan.first_streamed;
             lds_dma_copy(gblob + plan.g_off[l], lds + plan.ring_off[0], plan.bytes[l], wave, nwaves, lane);
         }
@@ -394,6 +419,140 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10> {
         }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) epilogue_tile<NT, ACT>(NSLAB - 1, nt, o[(NSLAB - 1) & 1], act);
+    }
+
+    // ---- hidden layers on bf16 MFMA (BF engines) ----------------------------------------------------------
+    // W = w1 + w2 + w3 exactly (three bf16 planes split on the host, ac_bf16_pack.hpp); the fp32 activations are split the same
+    // way in registers.  Of the nine plane products the six down to 2^-16 relative enter — (1,1), (1,2), (2,1), (2,2), (1,3),
+    // (3,1); the three dropped ones are <= 2^-24 of a term.  w1 x1 accumulates alone in `hi` (exact products, one rounding per
+    // 32-deep MFMA, as the fp32 chain); the five small products go to a second accumulator `lo`, smallest first, added once at
+    // the end of the tile — so the rounding of the big running sum never swallows them.
+    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    static constexpr int KC = WT / 2;  // 32-deep k-chunks
+    static constexpr bool kPairRing = PAIR != 0;
+    static constexpr int kBfFront = (WT / 2) * KC * 3 * 1024 + 1024, kBfBack = (WT / 2) * KC * 3 * 1024;
+
+    AC_DI static unsigned cvt_pk_bf16(float x, float y) {
+        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x, y}, bf16x2));  // v_cvt_pk_bf16_f32 (RNE)
+    }
+    // k-chunk c of slab s as the B operand: lane (col, g), element q = rows 4 g + q of tile 2c (q < 4) and 4 g + q - 4 of
+    // tile 2c + 1 — the host permuted the weight columns to match (bf16_chunk_row) — in three planes
+    AC_DI void split_chunk(int s, int c, bf16x8 (&p)[3]) const {
+        u32x4 q[3];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float x = a[s][2 * c + (i >> 1)][(2 * i) & 3], y = a[s][2 * c + (i >> 1)][(2 * i + 1) & 3];
+            unsigned u = cvt_pk_bf16(x, y);
+            q[0][i] = u;
+            x -= __uint_as_float(u << 16); y -= __uint_as_float(u & 0xffff0000u);
+            u = cvt_pk_bf16(x, y);
+            q[1][i] = u;
+            x -= __uint_as_float(u << 16); y -= __uint_as_float(u & 0xffff0000u);
+            q[2][i] = cvt_pk_bf16(x, y);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = __builtin_bit_cast(bf16x8, q[k]);
+    }
+    AC_DI static f32x4 mfma_bf(const bf16x8& w, const bf16x8& x, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0);
+    }
+    // Slab 0 reaches the back half: wait for it (every wave's pieces, then the barrier), then request the next layer's front.
+    AC_DI void mid_layer() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if constexpr (!kPairRing) lds_dma_copy(this->bf_next_src, lds + this->bf_next_dst, kBfFront, wave, nwaves, lane);
+    }
+
+    // One hidden layer (WT x WT tiles, tanh) on all slabs.  Per slab: CH output tiles at a time, each over the KC k-chunks with
+    // six MFMAs per chunk and tile (a "block").  Straight-line code, one fenced region per block: the A fragments of the NEXT
+    // block are requested at its head, and the VALU work runs beside the block's matrix stream (a bf16 MFMA holds vector issue
+    // for 8 of its 16 cycles): in block 1 + i of a chunk of output tiles the epilogue of its tile i in the previous slab, and in
+    // the last chunk of output tiles, behind block c, the split of the next slab's k-chunk c into the planes block c has just
+    // consumed — one set of planes live at any time (48 registers; a second set cost 260 B of scratch per lane).
+    AC_DI void layer_bf(const char* wfront) {
+        const bf16x8* wf0 = reinterpret_cast<const bf16x8*>(wfront) + lane;
+        const bf16x8* wf1 = reinterpret_cast<const bf16x8*>(this->bf_back) + lane;
+        const f32x4* bias4 = reinterpret_cast<const f32x4*>(wfront + kBfBack);
+        constexpr int C = CH;
+        static_assert(WT % C == 0 && (WT / 2) % C == 0 && C < KC, "a chunk of output tiles lies in one half");
+        auto frag = [&](int nt, int c, int p) -> bf16x8 {
+            return (nt < WT / 2 ? wf0 : wf1)[(((nt % (WT / 2)) * KC + c) * 3 + p) * 64];
+        };
+        f32x4 o[2][WT];
+        bf16x8 xc[KC][3];
+        bf16x8 w[2][C][3];  // A fragments: the block running, the next one
+#pragma unroll
+        for (int i = 0; i < C; ++i)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) w[0][i][p] = frag(i, 0, p);
+#pragma unroll
+        for (int c = 0; c < KC; ++c) split_chunk(0, c, xc[c]);
+#pragma unroll
+        for (int s = 0; s < NSLAB; ++s) {
+#pragma unroll
+            for (int nc = 0; nc < WT; nc += C) {
+                f32x4 hi[C], lo[C];
+#pragma unroll
+                for (int i = 0; i < C; ++i) {
+                    hi[i] = (s == 0 && !kNoValue) ? bias4[(nc + i) * 4 + g] : f32x4{0.f, 0.f, 0.f, 0.f};
+                    lo[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int c = 0; c < KC; ++c) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    const int cur = ((nc / C) * KC + c) & 1;
+                    const bool last_c = c + 1 == KC;
+                    const int nnc = last_c ? nc + C : nc, nkc = last_c ? 0 : c + 1;
+                    const bool more = !(s + 1 == NSLAB && nnc == WT);
+                    // slab 0 about to enter the back half: wait for it before the first read of it
+                    if (s == 0 && last_c && nnc == WT / 2) { mid_layer(); __builtin_amdgcn_sched_barrier(0); }
+                    if (more) {
+#pragma unroll
+                        for (int i = 0; i < C; ++i)
+#pragma unroll
+                            for (int p = 0; p < 3; ++p) w[cur ^ 1][i][p] = frag((nnc % WT) + i, nkc, p);
+                    }
+                    const bf16x8 (&wc)[C][3] = w[cur];
+#pragma unroll
+                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][2], xc[c][0], lo[i]);
+#pragma unroll
+                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][0], xc[c][2], lo[i]);
+#pragma unroll
+                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][1], xc[c][1], lo[i]);
+#pragma unroll
+                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][1], xc[c][0], lo[i]);
+#pragma unroll
+                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][0], xc[c][1], lo[i]);
+#pragma unroll
+                    for (int i = 0; i < C; ++i) hi[i] = mfma_bf(wc[i][0], xc[c][0], hi[i]);
+                    // the previous slab's epilogue of these tiles (its accumulators are long complete; the tangent epilogues read
+                    // the new value activations, finished during slab 1)
+                    if (c >= 1 && c <= C && s > 0) epilogue_tile<WT, 1>(s - 1, nc + c - 1, o[(s - 1) & 1], 1);
+                    // the next slab's split of this k-chunk (its inputs are read nowhere else)
+                    if (nc + C == WT && s + 1 < NSLAB) split_chunk(s + 1, c, xc[c]);
+                }
+#pragma unroll
+                for (int i = 0; i < C; ++i) o[s & 1][nc + i] = hi[i] + lo[i];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (PAIR != 0) {
+                if (s == 1) {
+                    // as in layer(): the partner has read the previous layer's h; a[0] is h of THIS layer (slab 0's epilogue
+                    // ran during slab 1)
+                    __syncthreads();
+                    if constexpr (PAIR == 1) {
+#pragma unroll
+                        for (int nt = 0; nt < WT; ++nt) hx[nt * 64 + lane] = f32x4{a[0][nt][0], a[0][nt][1], a[0][nt][2], a[0][nt][3]};
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int nt = 0; nt < WT; ++nt) epilogue_tile<WT, 1>(NSLAB - 1, nt, o[(NSLAB - 1) & 1], 1);
     }
 
     // First layer (5 -> width), tangent-aware: the value slab runs on the MFMA (one padded k-tile); the tangent
@@ -802,6 +961,32 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10> {
         if (plan.lds_off[l] >= 0) return lds + plan.lds_off[l];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        if constexpr (BF) {
+            // A bf16 hidden layer is two half-blocks (front: output tiles 0..WT/2-1 + bias, back: the rest).  The barrier just
+            // passed proves every wave done with the previous layer.  Three regions rotate: this layer's front landed during the
+            // previous layer; its back goes into the previous layer's front region now (slab 0 walks the front tiles first, so
+            // it has 1/12 of a layer to land: mid_layer() waits for it), and the next layer's front into the previous layer's
+            // back region behind the mid-layer barrier.  The wave-pair kernel (less LDS: two regions) loads both halves here.
+            const float* src = gblob + plan.g_off[l];
+            if constexpr (kPairRing) {
+                lds_dma_copy(src, lds + plan.bf_region[0], kBfFront, wave, nwaves, lane);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                lds_dma_copy(src + kBfFront / 4, lds + plan.bf_region[1], kBfBack, wave, nwaves, lane);
+                this->bf_back = lds + plan.bf_region[1];
+                return lds + plan.bf_region[0];
+            } else {
+                const int f = this->bf_front, b = f == 2 ? 0 : f + 1, nx = b == 2 ? 0 : b + 1;
+                lds_dma_copy(src + kBfFront / 4, lds + plan.bf_region[b], kBfBack, wave, nwaves, lane);
+                this->bf_back = lds + plan.bf_region[b];
+                const int nl = plan.streamed[snext];
+                snext = (snext + 1 == plan.n_streamed) ? 0 : snext + 1;
+                this->bf_next_src = gblob + plan.g_off[nl];
+                this->bf_next_dst = plan.bf_region[nx];
+                this->bf_front = nx;
+                return lds + plan.bf_region[f];
+            }
+        }
         const char* wl = lds + plan.ring_off[ring_pos & 1];
         const int nl = plan.streamed[snext];  // one scalar load (was: a scan of lds_off[] and a modulo per call)
         snext = (snext + 1 == plan.n_streamed) ? 0 : snext + 1;
@@ -832,7 +1017,7 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10> {
                 const char* wl = acquire(l);
                 if (plan.lds_off[l] >= 0) __syncthreads();  // a streamed layer's acquire() has just passed one
                 if constexpr (kNoValue) { if (l > 1) scale_from_hx(); }  // (layer 0's act' this wave formed itself)
-                layer<WT, WT, 1>(wl, 1);
+                if constexpr (BF) layer_bf(wl); else layer<WT, WT, 1>(wl, 1);
             }
             if (Lp > 2) {
                 __syncthreads();
@@ -901,7 +1086,8 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10> {
             for (int l = 1; l < L - 1; ++l) {
                 const char* wl = acquire(l);
                 AC_MARK(st, 3);  // [3] acquire: DMA wait + barrier + DMA issue
-                layer<WT, WT, 1>(wl, 1);  // tanh on every layer but the last: ac_set_mlp folds activation-free layers away
+                // tanh on every layer but the last: ac_set_mlp folds activation-free layers away
+                if constexpr (BF) layer_bf(wl); else layer<WT, WT, 1>(wl, 1);
                 AC_MARK(st, 4);  // [4] hidden layer GEMM + epilogues
             }
             if constexpr (kVLast && !kDeriv) {

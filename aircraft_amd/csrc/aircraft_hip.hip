@@ -10,6 +10,7 @@
 #include <new>
 #include <vector>
 
+#include "ac_bf16_pack.hpp"
 #include "ac_kernels_analytic.hpp"
 #include "ac_nn_decl.hpp"
 #include "ac_ilqr.hpp"
@@ -76,6 +77,9 @@ struct ac_handle {
     MlpPlan plan;
     MlpPlan plan_sens;  // the MFMA sensitivity engines' plan: last layer = [bias][wlt] for MlpEngine::last_valu (ac_set_mlp)
     MlpPlan plan_rev;   // width 128 on the matrix cores, <= 3 hidden products: plan_sens + the TRANSPOSED hidden blocks for the
+    MlpPlan plan_bf;       // width 128 (wt 8), matrix cores: plan_sens with the hidden layers as three-plane bf16 images streamed
+    MlpPlan plan_bf_pair;  // in half-layer regions — three rotating (k_nn_step_sens), two (k_nn_step_sens_pair); ac_set_mlp
+    bool has_bf;
     bool has_rev;       // reverse sweep of k_nn_stage_tensors_rev (ac_hess_rev.hpp); rev_layers = layers of the net itself
     int rev_layers;
     float* d_rev_scratch;  // per-wave layer states of that kernel (ac_reserve_hess_workspace)
@@ -418,8 +422,16 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
     const size_t rev_block_floats = (size_t)wt * wt * 256 + 256;  // fragments + a (zero) bias piece: the hidden blocks' size class
     if (want_rev)
         for (int i = 0; i < n_hid; ++i) { rev_off[i] = total_floats; total_floats += rev_block_floats; }
+    // Width 128 with hidden layers: their three-plane bf16 images (ac_bf16_pack.hpp) for the sensitivity kernels' layer_bf.
+    const bool want_bf = wt == 8 && n_hid >= 1;
+    size_t bf_off[AC_MAX_LAYERS] = {0};
+    if (want_bf)
+        for (int l = 1; l < n_layers - 1; ++l) { bf_off[l] = total_floats; total_floats += (size_t)bf16_layer_bytes(wt) / 4; }
     // Pack: [nt][kt][lane][4] with lane = col + 16 g -> W[16 nt + col][16 kt + 4 g + j]; then the padded bias.
     std::vector<float> blob(total_floats, 0.f);
+    if (want_bf)
+        for (int l = 1; l < n_layers - 1; ++l)
+            bf16_pack_layer(fW[(size_t)l].data(), fb[(size_t)l].data(), widths[l], widths[l + 1], wt, blob.data() + bf_off[l]);
     if (want_rev)
         for (int i = 0; i < n_hid; ++i) {
             const int l = n_hid - i;  // forward layer l: h_l (nin) -> h_{l+1} (nout); the block multiplies by its transpose
@@ -514,6 +526,28 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
         const int rc = plan_lds(ps);
         if (rc != AC_OK) return rc;
     }
+    // plan_bf: the edge blocks of plan_sens resident where they are, every hidden layer streamed through half-layer regions
+    // behind them (MlpEngine::acquire, BF engines)
+    MlpPlan pb = ps, pbp = ps;
+    if (want_bf) {
+        int off = 0;
+        for (int l = 0; l < n_layers; ++l) {
+            if (l == 0 || l == n_layers - 1) { pb.lds_off[l] = off; off += ps.bytes[l]; continue; }
+            pb.lds_off[l] = -1;
+            pb.g_off[l] = (int)bf_off[l];
+            pb.bytes[l] = bf16_layer_bytes(wt);
+        }
+        pb.n_streamed = 0; pb.first_streamed = 1;
+        for (int l = 1; l < n_layers - 1; ++l) pb.streamed[pb.n_streamed++] = l;
+        const int region = bf16_front_bytes(wt);
+        for (int i = 0; i < 3; ++i) pb.bf_region[i] = off + i * region;
+        pb.ring_off[0] = pb.ring_off[1] = -1;
+        pbp = pb;
+        pb.lds_total = off + 3 * region;
+        pbp.lds_total = off + 2 * region;
+        pbp.bf_region[2] = -1;
+        if (pb.lds_total > kLdsBudget) return fail(AC_ERR_UNSUPPORTED, "bf16 hidden-layer ring does not fit the LDS");
+    }
     MlpPlan pr = ps;
     bool rev_ok = false;
     if (want_rev) {
@@ -586,6 +620,9 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
     h->plan = pl;
     h->plan_sens = ps;
     h->plan_rev = pr;
+    h->plan_bf = pb;
+    h->plan_bf_pair = pbp;
+    h->has_bf = want_bf;
     h->has_rev = rev_ok;
     h->rev_layers = n_layers;
     h->wt = wt;
@@ -940,6 +977,9 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
             if (rem > 0 && rem <= 32 * cus) { n_main = n - rem; n_pair = rem; }
             if (h->all_pair) { n_main = 0; n_pair = n; }
         }
+        // width 128 on the matrix cores: the hidden layers on bf16 MFMA (plan_bf; -DAC_HIDDEN_FP32: plan_sens, as round 4)
+        const bool bf = kBf16Hidden && h->use_mfma && h->wt == 8 && h->has_bf;
+        const MlpPlan& plan_main = bf ? h->plan_bf : h->plan_sens;
         if (h->use_mfma && h->wt == 2 && h->dp.p.substeps <= 1) {
             // small nets: two persistent workgroups per CU = two waves per SIMD (k_nn_step_sens_w2)
             const int lds = ((h->plan_sens.lds_total + 15) & ~15) + kSensW2AccBytes;
@@ -964,24 +1004,25 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
             bool launched = false;
             AC_NN_CASE_SENS(2, true, (k_nn_step_sens<2, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
             AC_NN_CASE_SENS(4, true, (k_nn_step_sens<4, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
-            AC_NN_CASE_SENS(8, true, (k_nn_step_sens<8, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
+            AC_NN_CASE_PLAN(plan_main, 8, true, (k_nn_step_sens<8, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
             AC_NN_CASE_SENS(2, false, (k_nn_step_sens<2, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
             AC_NN_CASE_SENS(4, false, (k_nn_step_sens<4, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
             AC_NN_CASE_SENS(8, false, (k_nn_step_sens<8, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
             if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-            note_launch(h, "k_nn_step_sens", grid, kBlock, (h->use_mfma ? h->plan_sens : h->plan).lds_total);
+            note_launch(h, "k_nn_step_sens", grid, kBlock, (h->use_mfma ? plan_main : h->plan).lds_total);
             AC_HIP(hipGetLastError());
         }
         if (n_pair > 0) {
             const int grid_p = (int)((n_pair + 31) / 32);
-            const int lds_p = h->plan_sens.lds_total + 2 * h->wt * 1024 + 2 * 16 * 36 * (int)sizeof(float);  // + the pairs' activation and output exchanges
+            const MlpPlan& plan_p = bf ? h->plan_bf_pair : h->plan_sens;
+            const int lds_p = plan_p.lds_total + 2 * h->wt * 1024 + 2 * 16 * 36 * (int)sizeof(float);  // + the pairs' activation and output exchanges
             bool launched = false;
 #define AC_PAIR_CASE(WT_)                                                                                              \
             if (h->wt == WT_) {                                                                                        \
                 auto kern = k_nn_step_sens_pair<WT_>;                                                                  \
                 int rc_ = set_lds_limit(h, kern, lds_p);                                                                  \
                 if (rc_ != AC_OK) return rc_;                                                                          \
-                hipLaunchKernelGGL(kern, grid_p, kBlock, lds_p, st, h->dp, h->plan_sens, h->d_blob, X, U, dt, dt_per_unit, n, \
+                hipLaunchKernelGGL(kern, grid_p, kBlock, lds_p, st, h->dp, plan_p, h->d_blob, X, U, dt, dt_per_unit, n,      \
                                    blk, Xn, A, Bm, c, n_main);                                                          \
                 launched = true;                                                                                       \
             }
