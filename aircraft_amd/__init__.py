@@ -13,11 +13,12 @@ from .dynamics.coefficient_models import (COEFF_MODEL_REGISTRY, CoefficientModel
                                           NeuralModel, PolynomialModel)
 from ._lib import AircraftHipError
 from .trajectory_io import TrajectoryData, load_trajectory, save_trajectory
+from . import autodiff
 
 __all__ = [
     "AircraftConfiguration", "TrajectoryConfiguration", "MlpData", "load_model", "load_poly", "load_linear",
     "SixDOF", "SixDOFOpts", "BatchedFunction", "Aircraft", "AircraftOpts", "Quadrotor", "COEFF_MODEL_REGISTRY",
     "CoefficientModel", "DefaultModel", "LinearModel", "NeuralModel", "PolynomialModel", "AircraftHipError",
-    "TrajectoryData", "load_trajectory", "save_trajectory",
+    "TrajectoryData", "load_trajectory", "save_trajectory", "autodiff",
 ]
 __version__ = "0.1.0"

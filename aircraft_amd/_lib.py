@@ -16,6 +16,8 @@ AC_OK = 0
 STATUS_NAMES = {0: "AC_OK", -1: "AC_ERR_BAD_ARG", -2: "AC_ERR_HIP", -3: "AC_ERR_UNSUPPORTED",
                 -4: "AC_ERR_NO_MODEL", -5: "AC_ERR_NO_DEVICE", -6: "AC_ERR_WORKSPACE"}
 MODEL_KINDS = {"default": 0, "linear": 1, "nn": 2, "poly": 3, "quad": 4}
+VJP_ROUTES = {"auto": 0, "fused": 1, "composed": 2}   # ac_vjp_route
+VJP_STEP, VJP_ROLLOUT, VJP_DERIVATIVE = 0, 1, 2       # ac_vjp_which
 NUM_STATES = 13
 NUM_CONTROLS = 7
 AERO_ROWS = 22
@@ -122,6 +124,11 @@ PROTOTYPES = {
     "ac_mhtt_loss_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP]),
     "ac_rollout_policy_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _FP, C.c_int, C.c_float, C.c_long, C.c_long,
                                         _VP, _VP, _VP]),
+    "ac_set_vjp_route": (C.c_int, [_VP, C.c_int]),
+    "ac_vjp_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_step_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_rollout_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_state_derivative_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     "ac_device_arch": (C.c_int, [C.c_char_p, C.c_size_t]),

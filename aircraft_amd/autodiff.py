@@ -1,0 +1,159 @@
+"""Differentiable forms of the hot path: `step`, `rollout` and `state_derivative` as torch.autograd.Functions.
+
+The forward passes are the library's own kernels (ac_step_f32, ac_rollout_f32, ac_state_derivative_f32); the backward passes
+are its reverse-mode kernels (ac_step_vjp_f32, ac_rollout_vjp_f32, ac_state_derivative_vjp_f32), which take one
+cotangent per unit.  A loss written in plain torch over the outputs then back-propagates to the states, the controls and dt:
+
+    X = autodiff.rollout(ac, x0, U, dt)          # (H+1, 13, B), X[0] = x0
+    loss = ((X[-1, :3] - goal) ** 2).sum()
+    loss.backward()                              # U.grad, x0.grad (where they require grad)
+
+Conventions: tensors only (NumPy arrays are refused: autograd cannot track them); outputs and gradients come back in the
+dtype and on the device of the state input (the kernels compute in float32 on the handle's GPU); dt may be a Python number,
+a 0-d tensor or, for `step`, a per-unit tensor (n,) — a tensor dt that requires grad receives one.  First order only:
+differentiating a backward pass again raises.
+"""
+from __future__ import annotations
+
+import torch
+from torch.autograd.function import once_differentiable
+
+__all__ = ["step", "rollout", "state_derivative"]
+
+
+def _tensor(a, name):
+    if not isinstance(a, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(a).__name__} (aircraft_amd.autodiff is tensor-only; "
+                        "use SixDOF.step_vjp / rollout_vjp for NumPy)")
+    return a
+
+
+def _dt(dt, n, per_unit_ok):
+    """-> (value handed to the kernels, tensor or None)"""
+    if isinstance(dt, torch.Tensor):
+        if dt.numel() == 1:
+            return float(dt.detach().reshape(())), dt
+        if not per_unit_ok:
+            raise ValueError("rollout: dt must be a scalar")
+        if dt.dim() != 1 or dt.numel() != n:
+            raise ValueError(f"dt: expected a scalar or ({n},), got {tuple(dt.shape)}")
+        return dt.detach(), dt
+    if hasattr(dt, "__array__") or isinstance(dt, (list, tuple)):
+        raise TypeError("dt: expected a Python number or a torch.Tensor")
+    return float(dt), None
+
+
+def _check_states(ac, x, rows, name):
+    if x.dim() not in (1, 2) or x.shape[0] != rows:
+        raise ValueError(f"{name}: expected ({rows}, n) or ({rows},), got {tuple(x.shape)}")
+
+
+def _grad_like(g, ref):
+    if g is not None and g.shape[-ref.dim():] != ref.shape:  # a 7-row control buffer of a plugin with fewer controls
+        pad = list(ref.shape)
+        pad[-ref.dim()] = ref.shape[-ref.dim()] - g.shape[-ref.dim()]
+        g = torch.cat([g, g.new_zeros(pad)], dim=-ref.dim())
+    return None if g is None else g.to(device=ref.device, dtype=ref.dtype)
+
+
+def _dt_grad(gdt, dt_t):
+    """dt_bar per unit (n,) -> the gradient of the dt the caller passed (a scalar sums the units)."""
+    if dt_t is None:
+        return None
+    g = gdt.sum() if dt_t.numel() == 1 else gdt
+    return g.reshape(dt_t.shape).to(device=dt_t.device, dtype=dt_t.dtype)
+
+
+class _Step(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, u, dt_t, ac, dt_val):
+        ctx.ac, ctx.dt_val = ac, dt_val
+        ctx.save_for_backward(x, u, dt_t)
+        y = ac.state_update(x.detach(), u.detach(), dt_val)
+        return y.to(device=x.device, dtype=x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, u, dt_t = ctx.saved_tensors
+        need_x, need_u, need_dt = ctx.needs_input_grad[:3]
+        if not (need_x or need_u or need_dt):
+            return None, None, None, None, None
+        xb, ub, db = ctx.ac.step_vjp(x.detach(), u.detach(), ctx.dt_val, gy.contiguous())
+        return (_grad_like(xb, x) if need_x else None, _grad_like(ub, u) if need_u else None,
+                _dt_grad(db, dt_t) if need_dt else None, None, None)
+
+
+class _Rollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x0, U, dt_t, ac, dt_val):
+        ctx.ac, ctx.dt_val = ac, dt_val
+        X = ac.rollout(x0.detach(), U.detach(), dt_val)  # float32 on the handle's device: saved as the kernels read it
+        ctx.save_for_backward(x0, U, X, dt_t)
+        return X.to(device=x0.device, dtype=x0.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gX):
+        x0, U, X, dt_t = ctx.saved_tensors
+        need_x, need_u, need_dt = ctx.needs_input_grad[:3]
+        if not (need_x or need_u or need_dt):
+            return None, None, None, None, None
+        vec = x0.dim() == 1
+        Xs, Us, G = (X, U, gX) if not vec else (X.unsqueeze(-1), U.unsqueeze(-1), gX.unsqueeze(-1))
+        x0b, ub, db = ctx.ac.rollout_vjp(Xs, Us.detach(), ctx.dt_val, G.contiguous())
+        if vec:
+            x0b, ub, db = x0b[..., 0], ub[..., 0], db[0:1]
+        return (_grad_like(x0b, x0) if need_x else None, _grad_like(ub, U) if need_u else None,
+                _dt_grad(db, dt_t) if need_dt else None, None, None)
+
+
+class _Derivative(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, u, ac):
+        ctx.ac = ac
+        ctx.save_for_backward(x, u)
+        y = ac.state_derivative(x.detach(), u.detach())
+        return y.to(device=x.device, dtype=x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, u = ctx.saved_tensors
+        need_x, need_u = ctx.needs_input_grad[:2]
+        if not (need_x or need_u):
+            return None, None, None
+        xb, ub = ctx.ac.state_derivative_vjp(x.detach(), u.detach(), gy.contiguous())
+        return _grad_like(xb, x) if need_x else None, _grad_like(ub, u) if need_u else None, None
+
+
+def step(ac, x, u, dt):
+    """x+ = F(x, u, dt) (SixDOF.state_update) with a grad_fn.  x (13, n) or (13,), u (num_controls, n), dt a number, a 0-d
+    tensor or a per-unit tensor (n,)."""
+    _tensor(x, "x"); _tensor(u, "u")
+    _check_states(ac, x, ac.num_states, "x")
+    if u.dim() != x.dim() or u.shape[0] not in (ac.num_controls, 7) or u.shape[1:] != x.shape[1:]:
+        raise ValueError(f"u: expected ({ac.num_controls},{' n' if x.dim() == 2 else ''}) matching x, got {tuple(u.shape)}")
+    n = x.shape[1] if x.dim() == 2 else 1
+    dt_val, dt_t = _dt(dt, n, per_unit_ok=True)
+    return _Step.apply(x, u, dt_t, ac, dt_val)
+
+
+def rollout(ac, x0, U, dt):
+    """X[k+1] = F(X[k], U[k], dt) (SixDOF.rollout) with a grad_fn.  x0 (13, B) or (13,), U (H, num_controls, B) or
+    (H, num_controls), dt a number or a 0-d tensor -> X (H+1, 13, B)."""
+    _tensor(x0, "x0"); _tensor(U, "U")
+    _check_states(ac, x0, ac.num_states, "x0")
+    if U.dim() != x0.dim() + 1 or U.shape[1] not in (ac.num_controls, 7) or U.shape[2:] != x0.shape[1:]:
+        raise ValueError(f"U: expected (H, {ac.num_controls}, B) matching x0, got {tuple(U.shape)}")
+    dt_val, dt_t = _dt(dt, 1, per_unit_ok=False)
+    return _Rollout.apply(x0, U, dt_t, ac, dt_val)
+
+
+def state_derivative(ac, x, u):
+    """x_dot = f(x, u) (SixDOF.state_derivative) with a grad_fn."""
+    _tensor(x, "x"); _tensor(u, "u")
+    _check_states(ac, x, ac.num_states, "x")
+    if u.dim() != x.dim() or u.shape[0] not in (ac.num_controls, 7) or u.shape[1:] != x.shape[1:]:
+        raise ValueError(f"u: expected ({ac.num_controls},{' n' if x.dim() == 2 else ''}) matching x, got {tuple(u.shape)}")
+    return _Derivative.apply(x, u, ac)

@@ -376,9 +376,11 @@ template <int N> struct StageLds {
 };
 #endif
 
+// norm_adj: apply the adjoint of the quaternion normalisation (when P.p.normalise is set).  The reference normalises once,
+// after the LAST sub-step (dynamics/base.py:473-474): a sub-step composition passes true for that sub-step only.
 template <class T, class Coeffs, class Store>
 AC_DI void rk4_vjp(const DevParams& P, Coeffs& coeffs, const T x[13], const T u[7], const T& h, const float lam[13], T xo[13],
-                   T gx[13], T gu[7], T& gh, Store& store) {
+                   T gx[13], T gu[7], T& gh, Store& store, bool norm_adj = true) {
     // forward: stage states
     T acc[13], k[13];
     T xcur[13];
@@ -404,7 +406,7 @@ AC_DI void rk4_vjp(const DevParams& P, Coeffs& coeffs, const T x[13], const T u[
     T xb_out[13];
 #pragma unroll
     for (int i = 0; i < 13; ++i) xb_out[i] = T(lam[i]);
-    if (P.p.normalise) {
+    if (P.p.normalise && norm_adj) {
         const T n = m_sqrt(xo[6] * xo[6] + xo[7] * xo[7] + xo[8] * xo[8] + xo[9] * xo[9]);
         const T inv = 1.0f / n;
         T qn[4], dot = T(0.f);
@@ -457,9 +459,9 @@ AC_DI void rk4_vjp(const DevParams& P, Coeffs& coeffs, const T x[13], const T u[
 
 template <class T, class Coeffs>
 AC_DI void rk4_vjp(const DevParams& P, Coeffs& coeffs, const T x[13], const T u[7], const T& h, const float lam[13], T xo[13],
-                   T gx[13], T gu[7], T& gh) {
+                   T gx[13], T gu[7], T& gh, bool norm_adj = true) {
     StageRegs<T> store;
-    rk4_vjp<T>(P, coeffs, x, u, h, lam, xo, gx, gu, gh, store);
+    rk4_vjp<T>(P, coeffs, x, u, h, lam, xo, gx, gu, gh, store, norm_adj);
 }
 
 }  // namespace ac

@@ -21,6 +21,7 @@
 #include "ac_hess_nn.hpp"
 #include "ac_hess_rev.hpp"
 #include "ac_select.hpp"
+#include "ac_vjp.hpp"
 
 using namespace ac;
 
@@ -105,6 +106,7 @@ struct ac_handle {
     const void* lds_fn[48];
     int lds_bytes_set[48];
     int n_lds_fn;
+    int vjp_route;   // ac_vjp_route (ac_set_vjp_route); 0 = AC_VJP_AUTO
     // last launch (profiling aid)
     char last_name[64];
     int last_grid, last_block, last_lds;
@@ -1804,6 +1806,167 @@ int ac_hess_workspace(const ac_handle* h, float** ptr, size_t* floats) {
     if (!h) return AC_ERR_BAD_ARG;
     if (ptr) *ptr = h->d_hess_ws;
     if (floats) *floats = h->hess_ws_floats;
+    return AC_OK;
+}
+
+// ---- reverse mode: vector-Jacobian products (ac_vjp.hpp) ----------------------------------------------------------------------
+namespace {
+// The route a VJP call of this handle takes: AC_VJP_FUSED, AC_VJP_COMPOSED, or AC_ERR_UNSUPPORTED (fused forced on a model
+// that has no fused kernel, or more sub-steps than its LDS column holds).
+int vjp_route_of(const ac_handle* h) {
+    const int mk = h->dp.p.model_kind;
+    const bool fusable = (mk == AC_MODEL_DEFAULT || mk == AC_MODEL_LINEAR || mk == AC_MODEL_POLY) &&
+                         h->dp.p.substeps <= kVjpMaxSubsteps;
+    if (h->vjp_route == AC_VJP_COMPOSED) return AC_VJP_COMPOSED;
+    if (h->vjp_route == AC_VJP_FUSED) return fusable ? AC_VJP_FUSED : AC_ERR_UNSUPPORTED;
+    return fusable ? AC_VJP_FUSED : AC_VJP_COMPOSED;
+}
+// floats per unit of the composed route's workspace: x+ (or x_dot), A (Fx), B (Fu) and, for the step, c
+constexpr size_t kVjpStepWs = 13 + 169 + 91 + 13;
+constexpr size_t kVjpDerivWs = 13 + 169 + 91;
+size_t vjp_ws_floats(const ac_handle* h, int which, long n, long H) {
+    if (vjp_route_of(h) != AC_VJP_COMPOSED) return 0;
+    if (which == AC_VJP_ROLLOUT) return (size_t)n * (size_t)H * kVjpStepWs;
+    return (size_t)n * (which == AC_VJP_DERIVATIVE ? kVjpDerivWs : kVjpStepWs);
+}
+int vjp_lds_bytes(const ac_handle* h) { return vjp_lane_words(h->dp.p.substeps) * kVjpBlock * (int)sizeof(float); }
+}  // namespace
+
+int ac_set_vjp_route(ac_handle* h, int route) {
+    AC_ENTER(h);
+    if (!h || route < AC_VJP_AUTO || route > AC_VJP_COMPOSED) return AC_ERR_BAD_ARG;
+    h->vjp_route = route;
+    return AC_OK;
+}
+
+int ac_vjp_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats) {
+    if (!h || !floats || n_or_B < 0 || H < 0 || which < AC_VJP_STEP || which > AC_VJP_DERIVATIVE) return AC_ERR_BAD_ARG;
+    const int route = vjp_route_of(h);
+    if (route < 0) return fail(route, "fused VJP route requested for a model without fused kernels (or too many sub-steps)");
+    *floats = vjp_ws_floats(h, which, n_or_B, H);
+    return AC_OK;
+}
+
+int ac_step_vjp_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+                    float* Xbar, float* Ubar, float* dtbar, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (h && n == 0) return AC_OK;
+    if (!h || !X || !U || !Lam || !Xbar || !Ubar || n < 0) return AC_ERR_BAD_ARG;
+    int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    const int route = vjp_route_of(h);
+    if (route < 0) return fail(route, "fused VJP route requested for a model without fused kernels (or too many sub-steps)");
+    hipStream_t st = (hipStream_t)stream;
+    if (route == AC_VJP_FUSED) {
+        const int grid = (int)((n + kVjpBlock - 1) / kVjpBlock);
+        const int lds = vjp_lds_bytes(h);
+#define AC_VJP_STEP_CASE(M_)                                                                                            \
+        case M_: {                                                                                                      \
+            rc = set_lds_limit(h, k_step_vjp<M_>, lds);                                                                 \
+            if (rc != AC_OK) return rc;                                                                                 \
+            hipLaunchKernelGGL(k_step_vjp<M_>, grid, kVjpBlock, lds, st, h->dp, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar); \
+            break;                                                                                                      \
+        }
+        switch (h->dp.p.model_kind) { AC_VJP_STEP_CASE(AC_MODEL_LINEAR) AC_VJP_STEP_CASE(AC_MODEL_POLY) default: AC_VJP_STEP_CASE(AC_MODEL_DEFAULT) }
+#undef AC_VJP_STEP_CASE
+        note_launch(h, "k_step_vjp", grid, kVjpBlock, lds);
+        AC_HIP(hipGetLastError());
+        return AC_OK;
+    }
+    const size_t N = (size_t)n;
+    if (!ws || ws_floats < N * kVjpStepWs) return fail(AC_ERR_WORKSPACE, "VJP workspace too small: see ac_vjp_workspace_floats");
+    float* Xn = ws;
+    float* A = Xn + 13 * N;
+    float* Bm = A + 169 * N;
+    float* c = Bm + 91 * N;
+    rc = sens_impl(h, X, U, dt, dt_per_unit, n, n, Xn, A, Bm, dtbar ? c : nullptr, stream);
+    if (rc != AC_OK) return rc;
+    const int grid = (int)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_vjp_contract, grid, kBlock, 0, st, A, Bm, dtbar ? c : nullptr, Lam, n, Xbar, Ubar, dtbar);
+    note_launch(h, "k_vjp_contract", grid, kBlock, 0);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+
+int ac_rollout_vjp_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
+                       float* Ubar, float* dtbar, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !Xtraj || !G || !X0bar || B < 0 || H < 0 || (H > 0 && (!U || !Ubar))) return AC_ERR_BAD_ARG;
+    int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    const int route = vjp_route_of(h);
+    if (route < 0) return fail(route, "fused VJP route requested for a model without fused kernels (or too many sub-steps)");
+    hipStream_t st = (hipStream_t)stream;
+    if (H == 0) {  // X[0] = x0: the cotangent passes through; dt does not enter
+        AC_HIP(hipMemcpyAsync(X0bar, G, (size_t)B * 13 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (dtbar) AC_HIP(hipMemsetAsync(dtbar, 0, (size_t)B * sizeof(float), st));
+        return AC_OK;
+    }
+    if (route == AC_VJP_FUSED) {
+        const int grid = (int)((B + kVjpBlock - 1) / kVjpBlock);
+        const int lds = vjp_lds_bytes(h);
+#define AC_VJP_ROLL_CASE(M_)                                                                                            \
+        case M_: {                                                                                                      \
+            rc = set_lds_limit(h, k_rollout_vjp<M_>, lds);                                                              \
+            if (rc != AC_OK) return rc;                                                                                 \
+            hipLaunchKernelGGL(k_rollout_vjp<M_>, grid, kVjpBlock, lds, st, h->dp, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar); \
+            break;                                                                                                      \
+        }
+        switch (h->dp.p.model_kind) { AC_VJP_ROLL_CASE(AC_MODEL_LINEAR) AC_VJP_ROLL_CASE(AC_MODEL_POLY) default: AC_VJP_ROLL_CASE(AC_MODEL_DEFAULT) }
+#undef AC_VJP_ROLL_CASE
+        note_launch(h, "k_rollout_vjp", grid, kVjpBlock, lds);
+        AC_HIP(hipGetLastError());
+        return AC_OK;
+    }
+    const size_t N = (size_t)B * (size_t)H;
+    if (!ws || ws_floats < N * kVjpStepWs) return fail(AC_ERR_WORKSPACE, "VJP workspace too small: see ac_vjp_workspace_floats");
+    float* Xn = ws;
+    float* A = Xn + 13 * N;
+    float* Bm = A + 169 * N;
+    float* c = Bm + 91 * N;
+    // every (node, instance) pair of the saved trajectory is one unit of the multiple-shooting sensitivity kernels
+    rc = sens_impl(h, Xtraj, U, dt, nullptr, B * H, B, Xn, A, Bm, c, stream);
+    if (rc != AC_OK) return rc;
+    const int grid = (int)((B + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_vjp_recur, grid, kBlock, 0, st, A, Bm, c, G, B, H, X0bar, Ubar, dtbar);
+    note_launch(h, "k_vjp_recur", grid, kBlock, 0);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+
+int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, long n, const float* W, float* Xbar, float* Ubar,
+                                float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (h && n == 0) return AC_OK;
+    if (!h || !X || !U || !W || !Xbar || !Ubar || n < 0) return AC_ERR_BAD_ARG;
+    int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    const int route = vjp_route_of(h);
+    if (route < 0) return fail(route, "fused VJP route requested for a model without fused kernels (or too many sub-steps)");
+    hipStream_t st = (hipStream_t)stream;
+    if (route == AC_VJP_FUSED) {
+        const int grid = (int)((n + kBlock - 1) / kBlock);
+        switch (h->dp.p.model_kind) {
+            case AC_MODEL_LINEAR: hipLaunchKernelGGL(k_deriv_vjp<AC_MODEL_LINEAR>, grid, kBlock, 0, st, h->dp, X, U, W, n, Xbar, Ubar); break;
+            case AC_MODEL_POLY: hipLaunchKernelGGL(k_deriv_vjp<AC_MODEL_POLY>, grid, kBlock, 0, st, h->dp, X, U, W, n, Xbar, Ubar); break;
+            default: hipLaunchKernelGGL(k_deriv_vjp<AC_MODEL_DEFAULT>, grid, kBlock, 0, st, h->dp, X, U, W, n, Xbar, Ubar); break;
+        }
+        note_launch(h, "k_deriv_vjp", grid, kBlock, 0);
+        AC_HIP(hipGetLastError());
+        return AC_OK;
+    }
+    const size_t N = (size_t)n;
+    if (!ws || ws_floats < N * kVjpDerivWs) return fail(AC_ERR_WORKSPACE, "VJP workspace too small: see ac_vjp_workspace_floats");
+    float* Xd = ws;
+    float* Fx = Xd + 13 * N;
+    float* Fu = Fx + 169 * N;
+    rc = deriv_sens_impl(h, X, U, n, n, Xd, Fx, Fu, stream);
+    if (rc != AC_OK) return rc;
+    const int grid = (int)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_vjp_contract, grid, kBlock, 0, st, Fx, Fu, nullptr, W, n, Xbar, Ubar, nullptr);
+    note_launch(h, "k_vjp_contract", grid, kBlock, 0);
+    AC_HIP(hipGetLastError());
     return AC_OK;
 }
 

@@ -103,6 +103,7 @@ class SixDOF(ABC):
         self.epsilon = opts.epsilon
         self.mass = opts.mass
         self.normalise = False  # controllers flip this (control/base.py:182-185)
+        self.vjp_route = "auto"  # reverse mode: "auto" (fused where a fused kernel exists), "fused" or "composed"
         self.physical_integration_substeps: int = opts.physical_integration_substeps
         self.stall_scaling = False
         self._handle = C.c_void_p()
@@ -382,6 +383,125 @@ class SixDOF(ABC):
             self._sync()  # push the current sub-step count first: the reservation is sized for it
             _lib.check(_lib.load().ac_reserve_hess_workspace(self._handle, n), "ac_reserve_hess_workspace")
             self._hess_reserved = n
+
+    # ---- reverse mode: vector-Jacobian products (include/aircraft_hip.h, ac_*_vjp_f32) ----------------------------------
+    _VJP_KINDS = {"step": _lib.VJP_STEP, "rollout": _lib.VJP_ROLLOUT, "derivative": _lib.VJP_DERIVATIVE}
+
+    def _set_vjp_route(self):
+        lib = self._sync()
+        if self.vjp_route not in _lib.VJP_ROUTES:
+            raise ValueError(f"vjp_route: expected one of {sorted(_lib.VJP_ROUTES)}, got {self.vjp_route!r}")
+        _lib.check(lib.ac_set_vjp_route(self._handle, _lib.VJP_ROUTES[self.vjp_route]), "ac_set_vjp_route")
+        return lib
+
+    def vjp_workspace(self, kind, n, H=0):
+        """Device workspace the VJP of `kind` ("step", "rollout" with n = B, "derivative") needs on the current route, or
+        None (the fused kernels need none).  Allocate it before capturing a graph and pass it as `ws=`."""
+        lib = self._set_vjp_route()
+        need = C.c_size_t()
+        _lib.check(lib.ac_vjp_workspace_floats(self._handle, self._VJP_KINDS[kind], int(n), int(H), C.byref(need)),
+                   "ac_vjp_workspace_floats")
+        if need.value == 0:
+            return None
+        return _torch().empty(need.value, device=self._device_obj(), dtype=_torch().float32)
+
+    def _vjp_ws(self, kind, n, H, ws):
+        """-> (lib, workspace tensor or None, its size in floats); a caller's workspace is passed on as it is (the library
+        checks its size)."""
+        if ws is None:
+            ws = self.vjp_workspace(kind, n, H)
+        else:
+            self._set_vjp_route()
+        return _lib.load(), ws, (0 if ws is None else ws.numel())
+
+    def step_vjp(self, x, u, dt, lam, ws=None):
+        """Reverse mode of state_update: (x_bar, u_bar, dt_bar) = (A' lam, B' lam, c . lam) per unit — the gradient of
+        sum(lam * F(x, u, dt)) without forming A, B, c.  lam (13, n); dt a scalar or (n,); dt_bar is per unit (n,).
+        The route follows `self.vjp_route` ("auto", "fused", "composed"); `ws` is an optional pre-allocated workspace
+        (vjp_workspace("step", n))."""
+        torch = _torch()
+        X, npx, vec = self._in(x, self.num_states, "x")
+        U, _, _ = self._in_u(u)
+        L, _, _ = self._in(lam, self.num_states, "lam")
+        n = X.shape[1]
+        if U.shape[1] != n or L.shape[1] != n:
+            raise ValueError("x, u and lam must have the same number of columns")
+        lib, ws, wsn = self._vjp_ws("step", n, 0, ws)
+        dts, dtp, keep = self._dt_args(dt, n)
+        Xb = torch.empty_like(X)
+        Ub = torch.empty((_lib.NUM_CONTROLS, n), device=X.device, dtype=torch.float32)
+        db = torch.empty((n,), device=X.device, dtype=torch.float32)
+        _lib.check(lib.ac_step_vjp_f32(self._handle, X.data_ptr(), U.data_ptr(), dts, dtp, n, L.data_ptr(), Xb.data_ptr(),
+                                       Ub.data_ptr(), db.data_ptr(), ws.data_ptr() if ws is not None else None, wsn,
+                                       self._stream()), "ac_step_vjp_f32")
+        del keep
+        Ub = Ub[: self.num_controls]
+        if npx:
+            Xb, Ub, db = (t.cpu().numpy().astype(np.float64) for t in (Xb, Ub, db))
+        if vec:
+            Xb, Ub, db = Xb[..., 0], Ub[..., 0], db[0]
+        return Xb, Ub, db
+
+    def rollout_vjp(self, X, U, dt, G, ws=None):
+        """Reverse mode of rollout: X (H+1, 13, B) the trajectory rollout() returned for (x0, U, dt), G (H+1, 13, B) the
+        cotangent of every node -> (x0_bar (13, B), U_bar (H, num_controls, B), dt_bar (B,)).  dt is a scalar, as in
+        rollout(); dt_bar is the per-instance sum over the nodes."""
+        torch = _torch()
+        dev = self._device_obj()
+        from_np = not isinstance(X, torch.Tensor)
+
+        def t3(a, name, rows):
+            t = torch.as_tensor(np.asarray(a, dtype=np.float32) if not isinstance(a, torch.Tensor) else a)
+            if t.dim() != 3 or t.shape[1] not in rows:
+                raise ValueError(f"{name}: expected (., {rows[0]}, B), got {tuple(t.shape)}")
+            return t.to(device=dev, dtype=torch.float32)
+
+        Xt = t3(X, "X", (self.num_states,)).contiguous()
+        Gt = t3(G, "G", (self.num_states,)).contiguous()
+        Hp1, _, B = Xt.shape
+        H = Hp1 - 1
+        Ut = t3(U, "U", (self.num_controls, _lib.NUM_CONTROLS)) if H > 0 else torch.zeros((0, _lib.NUM_CONTROLS, B), device=dev)
+        if Gt.shape != Xt.shape or Ut.shape[0] != H or Ut.shape[2] != B:
+            raise ValueError(f"X {tuple(Xt.shape)}, U {tuple(Ut.shape)} and G {tuple(Gt.shape)} do not describe one rollout")
+        if Ut.shape[1] < _lib.NUM_CONTROLS:
+            Ut = torch.cat([Ut, torch.zeros((H, _lib.NUM_CONTROLS - Ut.shape[1], B), device=dev)], dim=1)
+        Ut = Ut.contiguous()
+        if np.ndim(dt) > 0 or (isinstance(dt, torch.Tensor) and dt.numel() != 1):
+            raise ValueError("rollout_vjp: dt must be a scalar (as in rollout)")
+        lib, ws, wsn = self._vjp_ws("rollout", B, H, ws)
+        X0b = torch.empty((self.num_states, B), device=dev, dtype=torch.float32)
+        Ub = torch.empty((H, _lib.NUM_CONTROLS, B), device=dev, dtype=torch.float32)
+        db = torch.empty((B,), device=dev, dtype=torch.float32)
+        _lib.check(lib.ac_rollout_vjp_f32(self._handle, Xt.data_ptr(), Ut.data_ptr() if H else None, C.c_float(float(dt)), B,
+                                          H, Gt.data_ptr(), X0b.data_ptr(), Ub.data_ptr() if H else None, db.data_ptr(),
+                                          ws.data_ptr() if ws is not None else None, wsn, self._stream()),
+                   "ac_rollout_vjp_f32")
+        Ub = Ub[:, : self.num_controls]
+        if from_np:
+            X0b, Ub, db = (t.cpu().numpy().astype(np.float64) for t in (X0b, Ub, db))
+        return X0b, Ub, db
+
+    def state_derivative_vjp(self, x, u, w, ws=None):
+        """Reverse mode of state_derivative: (x_bar, u_bar) = ((df/dx)' w, (df/du)' w) per unit; w (13, n)."""
+        torch = _torch()
+        X, npx, vec = self._in(x, self.num_states, "x")
+        U, _, _ = self._in_u(u)
+        W, _, _ = self._in(w, self.num_states, "w")
+        n = X.shape[1]
+        if U.shape[1] != n or W.shape[1] != n:
+            raise ValueError("x, u and w must have the same number of columns")
+        lib, ws, wsn = self._vjp_ws("derivative", n, 0, ws)
+        Xb = torch.empty_like(X)
+        Ub = torch.empty((_lib.NUM_CONTROLS, n), device=X.device, dtype=torch.float32)
+        _lib.check(lib.ac_state_derivative_vjp_f32(self._handle, X.data_ptr(), U.data_ptr(), n, W.data_ptr(), Xb.data_ptr(),
+                                                   Ub.data_ptr(), ws.data_ptr() if ws is not None else None, wsn,
+                                                   self._stream()), "ac_state_derivative_vjp_f32")
+        Ub = Ub[: self.num_controls]
+        if npx:
+            Xb, Ub = (t.cpu().numpy().astype(np.float64) for t in (Xb, Ub))
+        if vec:
+            Xb, Ub = Xb[..., 0], Ub[..., 0]
+        return Xb, Ub
 
     # ---- getters (reference dynamics/base.py:147-278, aircraft.py:255-330) ------------------------
     def _aero(self, x, u):

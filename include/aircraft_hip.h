@@ -54,7 +54,8 @@ typedef enum ac_status {
     AC_ERR_UNSUPPORTED = -3,   /* e.g. MLP wider than AC_MAX_WIDTH */
     AC_ERR_NO_MODEL = -4,      /* model_kind needs data that was never set */
     AC_ERR_NO_DEVICE = -5,     /* no gfx950 device visible */
-    AC_ERR_WORKSPACE = -6      /* a handle-owned workspace is too small: call the matching ac_reserve_* first */
+    AC_ERR_WORKSPACE = -6      /* a handle-owned workspace is too small: call the matching ac_reserve_* first; or a
+                                  caller-provided one is (ac_vjp_workspace_floats) */
 } ac_status;
 
 /* Registry keys of COEFF_MODEL_REGISTRY, dynamics/coefficient_models.py:32-37 */
@@ -386,6 +387,40 @@ int ac_track_progress_f32(ac_handle* h, const ac_mhtt_weights* weights, const fl
 /* J [B] = MHTT.loss (moving_horizon.py:44-105) of X [H+1][13][B], U [H][7][B] with progress S [H+1][B] */
 int ac_mhtt_loss_f32(ac_handle* h, const ac_mhtt_weights* weights, const float* X, const float* U, const float* S,
                      long B, long H, float* J, void* stream);
+
+/* ---- Reverse mode: vector-Jacobian products (autograd) ----------------------------------------------------------------------
+ * One cotangent per unit instead of 21 tangents: the gradient of a scalar loss through the step, a rollout or f.
+ *   ac_step_vjp_f32              Lam [13][n] (dLoss/dx+)  ->  Xbar = A' Lam [13][n], Ubar = B' Lam [7][n], dtbar = c . Lam [n]
+ *                                (dtbar may be NULL).  A, B, c are the blocks of ac_step_sens_f32: every sub-step, the final
+ *                                normalisation and dt_per_unit (NULL or [n]) exactly as ac_step_f32 applies them.  p never
+ *                                enters f, so Xbar[0..2] of a step equals Lam[0..2].
+ *   ac_rollout_vjp_f32           Xtraj [H+1][13][B] the saved forward trajectory (ac_rollout_f32's output), U [H][7][B],
+ *                                G [H+1][13][B] = dLoss/dX[k] (the cotangent of every node, node 0 included)
+ *                                ->  X0bar [13][B], Ubar [H][7][B], dtbar [B] (nullable: sum over nodes of c_k . lambda_{k+1})
+ *                                by  lambda_H = G_H,  lambda_k = G_k + A_k' lambda_{k+1},  Ubar_k = B_k' lambda_{k+1},
+ *                                X0bar = lambda_0.  The Jacobians are taken at the saved nodes.
+ *   ac_state_derivative_vjp_f32  W [13][n] (dLoss/dx_dot)  ->  Xbar = (df/dx)' W [13][n], Ubar = (df/du)' W [7][n];
+ *                                Xbar[0..2] = 0.
+ * Routes (ac_set_vjp_route; AC_VJP_AUTO picks the first that applies):
+ *   fused     default / linear / cubic-fit models with substeps <= 40: k_step_vjp, k_rollout_vjp, k_deriv_vjp — one lane per
+ *             unit (instance), the RK4 stages recomputed and pulled back in registers and LDS; no workspace
+ *   composed  the MLP surrogate and the quadrotor (any model on request): ac_step_sens_f32 / ac_shoot_sens_f32 /
+ *             ac_state_derivative_sens_f32 write A, B (, c) into the WORKSPACE, then k_vjp_contract applies the cotangent
+ *             (k_vjp_recur runs the rollout's reverse recurrence)
+ * ws / ws_floats: caller-owned device scratch of at least ac_vjp_workspace_floats(h, which, n or B, H) floats (0 for the
+ * fused route: ws may then be NULL); smaller returns AC_ERR_WORKSPACE.  The composed route's buffers are therefore the
+ * caller's: the handle reserves nothing, and a caller that captures a hipGraph allocates the workspace before capture.
+ * Like every compute call: asynchronous on `stream`, no allocation, no synchronisation, hipGraph-capturable. */
+typedef enum ac_vjp_which { AC_VJP_STEP = 0, AC_VJP_ROLLOUT = 1, AC_VJP_DERIVATIVE = 2 } ac_vjp_which;
+typedef enum ac_vjp_route { AC_VJP_AUTO = 0, AC_VJP_FUSED = 1, AC_VJP_COMPOSED = 2 } ac_vjp_route;
+int ac_set_vjp_route(ac_handle* h, int route);  /* AC_VJP_FUSED on a model without fused kernels: the calls return AC_ERR_UNSUPPORTED */
+int ac_vjp_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats);
+int ac_step_vjp_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+                    float* Xbar, float* Ubar, float* dtbar, float* ws, size_t ws_floats, void* stream);
+int ac_rollout_vjp_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
+                       float* Ubar, float* dtbar, float* ws, size_t ws_floats, void* stream);
+int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, long n, const float* W, float* Xbar, float* Ubar,
+                                float* ws, size_t ws_floats, void* stream);
 
 /* Diagnostics */
 const char* ac_last_error(void);     /* thread-local text of the last failing HIP call */
