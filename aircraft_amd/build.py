@@ -24,8 +24,10 @@ UNIT_FLAGS = {
     # they are bound by vector-ALU throughput, not by dependent issue — DESIGN.md §6.2)
     "an_inst_sens_poly": ["-fno-slp-vectorize"],
     "nn_inst_wt2_mfma_sens_w2": ["-fno-slp-vectorize"],  # (the small-net kernel at two waves per SIMD)
-    "nn_inst_wt8_mfma_sens": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6"],
-    "nn_inst_wt8_mfma_pair": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6"],
+    # -amdgpu-mfma-vgpr-form: the MFMA accumulators in the vector file, where the VALU sums and epilogues read them, and
+    # the weight fragments in AGPRs (MlpEngine::ds_frag): ~530 -> ~170 AGPR<->VGPR moves per bf16 hidden layer.
+    "nn_inst_wt8_mfma_sens": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],
+    "nn_inst_wt8_mfma_pair": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],
 }
 
 

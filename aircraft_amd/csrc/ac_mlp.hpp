@@ -459,6 +459,20 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     AC_DI static f32x4 mfma_bf(const bf16x8& w, const bf16x8& x, f32x4 c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0);
     }
+    // One A fragment (16 B per lane) straight from LDS into accumulation registers: only the MFMA reads the weights, and in
+    // the vector file they pushed the accumulators into AGPRs, which then cost a v_accvgpr_read per element for every
+    // hi + lo sum and epilogue (~530 moves per layer call).  The waitcnt pass does not see this read: the caller waits
+    // lgkmcnt(0) (wait_frags) before the first MFMA that uses it.  `lds_addr`: the LDS byte address of lane 0's piece + 16 lane.
+    // `off` must fold to a constant (the fully unrolled loops of layer_bf): it is the instruction's 16-bit immediate offset.
+    AC_DI static bf16x8 ds_frag(unsigned lds_addr, int off) {
+        bf16x8 v;
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(v) : "v"(lds_addr), "i"(off));
+        return v;
+    }
+    AC_DI static void wait_frags() {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // Slab 0 reaches the back half: wait for it (every wave's pieces, then the barrier), then request the next layer's front.
     AC_DI void mid_layer() {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -478,8 +492,12 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
         const f32x4* bias4 = reinterpret_cast<const f32x4*>(wfront + kBfBack);
         constexpr int C = CH;
         static_assert(WT % C == 0 && (WT / 2) % C == 0 && C < KC, "a chunk of output tiles lies in one half");
+        // LDS addresses of this lane's piece in the two halves (generic -> LDS pointer: the low 32 bits)
+        const unsigned la0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf0;
+        const unsigned la1 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf1;
+        static_assert((WT / 2) * KC * 3 * 1024 <= 65536, "a half-layer fits the ds_read immediate offset");
         auto frag = [&](int nt, int c, int p) -> bf16x8 {
-            return (nt < WT / 2 ? wf0 : wf1)[(((nt % (WT / 2)) * KC + c) * 3 + p) * 64];
+            return ds_frag(nt < WT / 2 ? la0 : la1, (((nt % (WT / 2)) * KC + c) * 3 + p) * 1024);
         };
         f32x4 o[2][WT];
         bf16x8 xc[KC][3];
@@ -509,6 +527,8 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
                     const bool more = !(s + 1 == NSLAB && nnc == WT);
                     // slab 0 about to enter the back half: wait for it before the first read of it
                     if (s == 0 && last_c && nnc == WT / 2) { mid_layer(); __builtin_amdgcn_sched_barrier(0); }
+                    // this block's fragments (requested at the head of the previous block) have landed
+                    wait_frags();
                     if (more) {
 #pragma unroll
                         for (int i = 0; i < C; ++i)
@@ -538,6 +558,7 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
                 for (int i = 0; i < C; ++i) o[s & 1][nc + i] = hi[i] + lo[i];
             }
             __builtin_amdgcn_sched_barrier(0);
+            if (s == 0) AC_MARK(st, 9); else if (s == 1) AC_MARK(st, 10); else AC_MARK(st, 11);  // as in layer()
             if constexpr (PAIR != 0) {
                 if (s == 1) {
                     // as in layer(): the partner has read the previous layer's h; a[0] is h of THIS layer (slab 0's epilogue
