@@ -18,6 +18,7 @@ STATUS_NAMES = {0: "AC_OK", -1: "AC_ERR_BAD_ARG", -2: "AC_ERR_HIP", -3: "AC_ERR_
 MODEL_KINDS = {"default": 0, "linear": 1, "nn": 2, "poly": 3, "quad": 4}
 VJP_ROUTES = {"auto": 0, "fused": 1, "composed": 2}   # ac_vjp_route
 VJP_STEP, VJP_ROLLOUT, VJP_DERIVATIVE = 0, 1, 2       # ac_vjp_which
+TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac_trim_f32 status per instance
 NUM_STATES = 13
 NUM_CONTROLS = 7
 AERO_ROWS = 22
@@ -51,6 +52,11 @@ class GoalLoss(C.Structure):
     _fields_ = [("w_goal", C.c_float), ("w_rate", C.c_float), ("eps_rate", C.c_float), ("w_height", C.c_float),
                 ("w_speed", C.c_float), ("w_vx", C.c_float), ("w_vyz", C.c_float), ("vx_max", C.c_float), ("w_al", C.c_float),
                 ("time_row", C.c_int)]
+
+
+class TrimOpts(C.Structure):
+    """struct ac_trim_opts (include/aircraft_hip.h)."""
+    _fields_ = [("lateral", C.c_int), ("tol_v", C.c_float), ("tol_w", C.c_float), ("lo", C.c_float * 6), ("hi", C.c_float * 6)]
 
 
 class EnvelopePenalty(C.Structure):
@@ -129,6 +135,9 @@ PROTOTYPES = {
     "ac_step_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_rollout_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_state_derivative_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_trim_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_trim_f32": (C.c_int, [_VP, C.POINTER(TrimOpts), _VP, _VP, _VP, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
+                              _VP]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     "ac_device_arch": (C.c_int, [C.c_char_p, C.c_size_t]),

@@ -22,6 +22,7 @@
 #include "ac_hess_rev.hpp"
 #include "ac_select.hpp"
 #include "ac_vjp.hpp"
+#include "ac_trim.hpp"
 
 using namespace ac;
 
@@ -1967,6 +1968,57 @@ int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, lo
     hipLaunchKernelGGL(k_vjp_contract, grid, kBlock, 0, st, Fx, Fu, nullptr, W, n, Xbar, Ubar, nullptr);
     note_launch(h, "k_vjp_contract", grid, kBlock, 0);
     AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+
+// ---- steady-flight trim (ac_trim.hpp) -----------------------------------------------------------------------------------------
+namespace {
+// the six workspace buffers each start on a 256-byte boundary, as a torch allocation would
+constexpr size_t kTrimWsPad = 6 * 64;
+size_t trim_ws_floats(long n) { return (size_t)n * (size_t)kTrimWsFloats + kTrimWsPad; }
+float* align256(float* p) { return (float*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+}  // namespace
+
+int ac_trim_workspace_floats(const ac_handle* h, long n, size_t* floats) {
+    if (!h || !floats || n < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, "trim is defined for the fixed-wing models only");
+    *floats = trim_ws_floats(n);
+    return AC_OK;
+}
+
+int ac_trim_f32(ac_handle* h, const ac_trim_opts* o, const float* target, const float* Uhold, const float* Z0, int iters, long n,
+                float* X, float* U, float* Z, float* R, int* status, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !o || iters < 1 || n < 0 || (o->lateral != 0 && o->lateral != 1)) return AC_ERR_BAD_ARG;
+    if (!(o->tol_v > 0.f) || !(o->tol_w > 0.f)) return fail(AC_ERR_BAD_ARG, "trim tolerances must be > 0");
+    for (int j = 0; j < 6; ++j)
+        if (!(o->lo[j] <= o->hi[j])) return fail(AC_ERR_BAD_ARG, "trim bounds: lo > hi (or NaN)");
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, "trim is defined for the fixed-wing models only");
+    if (n == 0) return AC_OK;
+    if (!target || !Uhold || !Z0 || !X || !U || !Z || !R || !status) return AC_ERR_BAD_ARG;
+    int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    const size_t N = (size_t)n;
+    if (!ws || ws_floats < trim_ws_floats(n))
+        return fail(AC_ERR_WORKSPACE, "trim workspace too small: see ac_trim_workspace_floats");
+    float* Xw = align256(ws);
+    float* Uw = align256(Xw + 13 * N);
+    float* Xd = align256(Uw + 7 * N);
+    float* Fx = align256(Xd + 13 * N);
+    float* Fu = align256(Fx + 169 * N);
+    float* St = align256(Fu + 91 * N);  // ends at most ws + 350 N + 6 * 63 floats
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = (int)((n + kTrimBlock - 1) / kTrimBlock);
+    for (int k = 0; k < iters; ++k) {
+        hipLaunchKernelGGL(k_trim_assemble, grid, kTrimBlock, 0, st, *o, target, Uhold, Z0, n, (int)(k == 0), Xw, Uw, St);
+        AC_HIP(hipGetLastError());
+        rc = deriv_sens_impl(h, Xw, Uw, n, n, Xd, Fx, Fu, stream);
+        if (rc != AC_OK) return rc;
+        hipLaunchKernelGGL(k_trim_update, grid, kTrimBlock, 0, st, *o, target, Uhold, Xd, Fx, Fu, n, (int)(k == iters - 1), St, X, U,
+                           Z, R, status);
+        AC_HIP(hipGetLastError());
+    }
+    note_launch(h, "k_trim_update", grid, kTrimBlock, 0);
     return AC_OK;
 }
 

@@ -8,7 +8,9 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Tuple, Union
+from typing import Any, Tuple, Union
+
+import ctypes as C
 
 import numpy as np
 
@@ -17,7 +19,7 @@ from ..utils import AircraftConfiguration
 from .base import SixDOF, SixDOFOpts
 from .coefficient_models import COEFF_MODEL_REGISTRY, CoefficientModel, DefaultModel
 
-__all__ = ["Aircraft", "AircraftOpts"]
+__all__ = ["Aircraft", "AircraftOpts", "TrimResult"]
 
 
 def _torch_mod():
@@ -44,6 +46,21 @@ class AircraftOpts(SixDOFOpts):
         factory = COEFF_MODEL_REGISTRY.get(self.coeff_model_type, COEFF_MODEL_REGISTRY["default"])
         self.coefficient_model = lambda aircraft: factory(self.coeff_model_path, aircraft, realtime=self.realtime,
                                                           use_mfma=self.use_mfma)
+
+
+@dataclass
+class TrimResult:
+    """Aircraft.trim's result for n instances (numpy in -> numpy out; tensors stay on the device).
+    x (13, n) and u (7, n): the trimmed state and control; z (6, n) = (alpha, theta, phi [rad], aileron, elevator [deg],
+    rudder [deg] (lateral mode 0) | beta [rad] (mode 1)); residual (6, n) = (r_v [m/s^2], r_w [rad/s^2]) at z; status (n,):
+    0 converged, 1 not converged within iters, 2 stopped on a bound, 3 non-finite (include/aircraft_hip.h, ac_trim_f32);
+    converged (n,) = status == 0."""
+    x: Any
+    u: Any
+    z: Any
+    residual: Any
+    status: Any
+    converged: Any
 
 
 def inertia_about_com(cfg_Ixx, cfg_Iyy, cfg_Izz, cfg_Ixz, mass, com):
@@ -132,6 +149,120 @@ class Aircraft(SixDOF):
             rows = rows[..., 0]
             Jx = None if Jx is None else Jx[..., 0]
         return rows, Jx
+
+    # ---- steady-flight trim (include/aircraft_hip.h, ac_trim_f32) -------------------------------------
+    def trim_bounds(self, lateral: int = 0):
+        """Default bounds (lo (6,), hi (6,)) of z: alpha +-20 deg and beta +-10 deg (the envelope, control/aircraft.py:53-58),
+        theta +-60 deg, phi +-80 deg (rad), the surfaces +-10 deg (problem_definition.json:32-34)."""
+        d = np.deg2rad
+        hi = np.array([d(20.0), d(60.0), d(80.0), 10.0, 10.0, d(10.0) if lateral else 10.0])
+        return -hi, hi
+
+    def trim_workspace(self, n: int):
+        """Device workspace of a trim of n instances (ac_trim_workspace_floats); allocate it before capturing a graph."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_trim_workspace_floats(self._handle, int(n), C.byref(need)), "ac_trim_workspace_floats")
+        return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
+
+    def trim(self, airspeed, *, psi=0.0, turn_rate=0.0, beta=0.0, rudder=None, position=(0.0, 0.0, -200.0), thrust=0.0,
+             flaps=0.0, guess=None, bounds=None, iters=30, tol=(1e-4, 1e-4), ws=None) -> TrimResult:
+        """Steady flight for n instances: z = (alpha, theta, phi, aileron, elevator, rudder | beta) such that body velocity
+        and body rates stay constant at airspeed V, heading psi, turn rate psid (rad/s about NED down; 0 = straight).
+        beta (rad) is held and the rudder solved for; passing `rudder` (deg) holds it and solves for beta instead.
+        Per-instance arguments are scalars or (n,); position (3,) or (3, n); thrust a scalar, (3,) or (3, n); flaps a scalar
+        or (n,); guess (6,) or (6, n); bounds (lo (6,), hi (6,)) (default trim_bounds()); tol (tol_v, tol_w).
+        Default guess: alpha 4 deg, theta = alpha + the glide angle -atan(1 / glide_ratio), phi = atan(V psid / g), surfaces 0.
+        `iters` Levenberg-Marquardt iterations, each three kernel launches; no host synchronisation (graph-capturable with a
+        workspace `ws` from trim_workspace(n))."""
+        torch = _torch_mod()
+        lateral = 0 if rudder is None else 1
+        if lateral and (isinstance(beta, torch.Tensor) or np.ndim(beta) != 0 or float(beta) != 0.0):
+            raise ValueError("trim: pass beta (held sideslip, rudder solved) or rudder (held rudder, beta solved), not both")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 1:
+            raise ValueError(f"trim: iters must be an integer >= 1, got {iters!r}")
+        tol = tuple(float(t) for t in np.ravel(tol))
+        if len(tol) != 2 or not all(np.isfinite(t) and t > 0 for t in tol):
+            raise ValueError(f"trim: tol must be two finite values > 0 (tol_v, tol_w), got {tol}")
+        lo, hi = self.trim_bounds(lateral) if bounds is None else (np.asarray(b, dtype=np.float64) for b in bounds)
+        if np.shape(lo) != (6,) or np.shape(hi) != (6,) or np.isnan(lo).any() or np.isnan(hi).any() or (lo > hi).any():
+            raise ValueError("trim: bounds must be (lo (6,), hi (6,)) with lo <= hi")
+        if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.float32 or not ws.is_cuda
+                               or not ws.is_contiguous()):
+            raise ValueError("trim: ws must be a contiguous float32 device tensor (trim_workspace(n))")
+        lat = beta if rudder is None else rudder
+        args = {"airspeed": (airspeed, None), "psi": (psi, None), "turn_rate": (turn_rate, None),
+                ("rudder" if lateral else "beta"): (lat, None), "position": (position, 3), "thrust": (thrust, 3),
+                "flaps": (flaps, None), "guess": (guess, 6)}
+
+        def cols(name, a, rows):
+            shp = tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+            if rows is None and len(shp) <= 1:
+                return shp[0] if shp else 1
+            if rows is not None and (len(shp) == 0 and name == "thrust" or shp == (rows,)):
+                return 1
+            if rows is not None and len(shp) == 2 and shp[0] == rows:
+                return shp[1]
+            want = "a scalar or (n,)" if rows is None else f"({rows},) or ({rows}, n)"
+            raise ValueError(f"trim: {name} must be {want}, got shape {shp}")
+
+        m = {k: cols(k, a, r) for k, (a, r) in args.items() if a is not None}
+        sizes = {v for v in m.values() if v != 1}
+        if len(sizes) > 1:
+            raise ValueError(f"trim: arguments do not broadcast to one n: {m}")
+        n = sizes.pop() if sizes else 1
+        tensors = any(isinstance(a, torch.Tensor) for a, _ in args.values())
+
+        # ---- device side ----
+        lib = self._sync()
+        dev = self._device_obj()
+
+        def rows_of(a, rows):
+            if not isinstance(a, torch.Tensor) and np.size(a) <= rows:
+                # a constant: filled on the device (no host-to-device copy, so a default argument can be graph-captured)
+                v = np.asarray(a, dtype=np.float32).ravel()
+                t = torch.empty((v.size, 1), device=dev, dtype=torch.float32)
+                for k, e in enumerate(v):
+                    t[k].fill_(float(e))
+                return t.expand(rows, n)
+            t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float32))
+            t = t.to(device=dev, dtype=torch.float32)
+            return t.reshape(rows if t.numel() != 1 else 1, -1).expand(rows, n)
+
+        V = rows_of(airspeed, 1)
+        psid = rows_of(turn_rate, 1)
+        target = torch.cat([rows_of(position, 3), V, rows_of(psi, 1), psid, rows_of(lat, 1)]).contiguous()
+        Uhold = torch.zeros((_lib.NUM_CONTROLS, n), device=dev, dtype=torch.float32)
+        Uhold[3:6] = rows_of(thrust, 3)
+        Uhold[6:7] = rows_of(flaps, 1)
+        if guess is None:
+            a0 = float(np.deg2rad(4.0))
+            gamma0 = -float(np.arctan(1.0 / float(self.opts.aircraft_config.glide_ratio)))
+            Z0 = torch.zeros((6, n), device=dev, dtype=torch.float32)
+            Z0[0] = a0
+            Z0[1] = a0 + gamma0
+            Z0[2] = torch.atan(V[0] * psid[0] / float(self.gravity[2]))
+        else:
+            Z0 = rows_of(guess, 6).contiguous()
+        opts = _lib.TrimOpts()
+        opts.lateral = lateral
+        opts.tol_v, opts.tol_w = tol
+        opts.lo[:] = [float(v) for v in lo]
+        opts.hi[:] = [float(v) for v in hi]
+        if ws is None:
+            ws = self.trim_workspace(n)
+        X = torch.empty((13, n), device=dev, dtype=torch.float32)
+        U = torch.empty((_lib.NUM_CONTROLS, n), device=dev, dtype=torch.float32)
+        Z = torch.empty((6, n), device=dev, dtype=torch.float32)
+        R = torch.empty((6, n), device=dev, dtype=torch.float32)
+        S = torch.empty((n,), device=dev, dtype=torch.int32)
+        _lib.check(lib.ac_trim_f32(self._handle, C.byref(opts), target.data_ptr(), Uhold.data_ptr(), Z0.data_ptr(), int(iters),
+                                   n, X.data_ptr(), U.data_ptr(), Z.data_ptr(), R.data_ptr(), S.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), self._stream()), "ac_trim_f32")
+        if not tensors:
+            X, U, Z, R = (t.cpu().numpy().astype(np.float64) for t in (X, U, Z, R))
+            S = S.cpu().numpy()
+        return TrimResult(X, U, Z, R, S, S == 0)
 
     # what the test oracle needs to rebuild the same airframe (tests only)
     def airframe_dict(self) -> dict:

@@ -422,6 +422,39 @@ int ac_rollout_vjp_f32(ac_handle* h, const float* Xtraj, const float* U, float d
 int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, long n, const float* W, float* Xbar, float* Ubar,
                                 float* ws, size_t ws_floats, void* stream);
 
+/* ---- steady-flight trim (fixed-wing models) ------------------------------------------------------------------
+ * Per instance, find z = (alpha, theta, phi [rad], aileron, elevator [deg], rudder [deg] | beta [rad]) such that the flight
+ * given by target (p, V, psi, turn rate psid about NED down, and beta or rudder) is steady:
+ *     q = Euler-to-quaternion(phi, theta, psi) (xyzw, body -> NED; the convention ac_aero_f32's phi/theta/psi rows invert)
+ *     v_b = V (cos a cos b, sin b, sin a cos b),  v_ned = q v_b q^-1,  omega_b = q^-1 (0, 0, psid) q
+ *     u = (aileron, elevator, rudder, Uhold rows 3-6)
+ *     r_v = q^-1 f[3:6] q - omega_b x v_b   (m/s^2),   r_w = f[10:13]   (rad/s^2),   f = ac_state_derivative_f32(x, u)
+ * r = 0 exactly when body velocity and body rates are constant; with psid = 0 it is the reference's trim objective
+ * |v_dot_ned|^2 + |omega_dot|^2 = 0 at omega = 0 (a steady glide sinks with v_dot_ned = 0).
+ * lateral 0: beta = target row 6 is held and the rudder is z[5]; lateral 1: the rudder = target row 6 is held and beta is z[5]
+ * (the linear model has no rudder column: trim its turns in mode 1).
+ * Solver: `iters` Levenberg-Marquardt iterations with projection onto [lo, hi], each three launches on `stream`:
+ * k_trim_assemble (z -> x, u), the handle's ac_state_derivative_sens_f32 launch (f, df/dx, df/du), k_trim_update (r and
+ * dr/dz, accept / reject, the next candidate by a 6x6 Cholesky solve).  An instance whose max|r_v| <= tol_v and
+ * max|r_w| <= tol_w is frozen: later iterations leave its results bit-identical.  Z0 [6][n] is the initial guess (projected
+ * onto the bounds).  Outputs: X [13][n], U [7][n], Z [6][n] at the best z found, R [6][n] = (r_v, r_w) there, and status [n]:
+ *   0 converged, 1 not converged within iters, 2 stopped on a bound with the residual above tolerance,
+ *   3 non-finite (V <= 0, a NaN or Inf input, or a model that returns no finite residual at the guess).
+ * ws / ws_floats: caller-owned device scratch of at least ac_trim_workspace_floats(h, n) floats, else AC_ERR_WORKSPACE.
+ * AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG for iters < 1, n < 0, !(lo <= hi), tol <= 0, NULL pointers or an
+ * unknown lateral mode.  Like every compute call: asynchronous, no allocation, no synchronisation, hipGraph-capturable. */
+typedef struct ac_trim_opts {
+    int lateral;         /* 0: beta held, rudder solved; 1: rudder held, beta solved */
+    float tol_v, tol_w;  /* convergence: max |r_v| (m/s^2), max |r_w| (rad/s^2) */
+    float lo[6], hi[6];  /* bounds of z = (alpha, theta, phi [rad], aileron, elevator [deg], rudder [deg] | beta [rad]) */
+} ac_trim_opts;
+int ac_trim_workspace_floats(const ac_handle* h, long n, size_t* floats);
+int ac_trim_f32(ac_handle* h, const ac_trim_opts* o,
+                const float* target /* [7][n]: p(3), V, psi, turn_rate, beta (mode 0) | rudder (mode 1) */,
+                const float* Uhold /* [7][n]: rows 3-6 held, rows 0-2 ignored */, const float* Z0 /* [6][n] */, int iters, long n,
+                float* X /* [13][n] */, float* U /* [7][n] */, float* Z /* [6][n] */, float* R /* [6][n] */, int* status /* [n] */,
+                float* ws, size_t ws_floats, void* stream);
+
 /* Diagnostics */
 const char* ac_last_error(void);     /* thread-local text of the last failing HIP call */
 const char* ac_version(void);
