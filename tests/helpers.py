@@ -244,3 +244,115 @@ def oracle_step_hessian(orc, X, U, dt, lam, h=1e-5):
             dd[:] = h
         Hm[a] = (grad(X + dX, U + dU, dtv + dd) - grad(X - dX, U - dU, dtv - dd)) / (2 * h)
     return Hm
+
+
+# ---- second-order blocks, block by block ---------------------------------------------------------------------------------
+# Groups of z = (x[13], u[7], dt) the (21, 21, n) Hessian of lam . F is checked by.  Position (0:3) and the thrust controls
+# (16:19) are structural zeros (asserted exactly by the tests); the remaining six groups give 21 block pairs.
+HESS_GROUPS = {"v": slice(3, 6), "q": slice(6, 10), "w": slice(10, 13), "surf": slice(13, 16), "flap": slice(19, 20),
+               "dt": slice(20, 21)}
+# the quadrotor plugin: four thrust controls in rows 13:17, rows 17:20 are zero
+QUAD_HESS_GROUPS = {"v": slice(3, 6), "q": slice(6, 10), "w": slice(10, 13), "thrust": slice(13, 17), "dt": slice(20, 21)}
+# Floor of the per-block metric in the tests: the smallest blocks are ~1e-8 .. 1e-7 of their unit (controls of the default
+# model: their second derivatives carry dt^2 and the model is linear in them); at 1e-8 every block pair is above the floor on
+# at least 90 % of the units of every model the tests use, and the checker's own noise per block stays below bar / 30
+# (tests/test_hess_blocks.py).
+HESS_FLOOR = 1e-8
+# Per-block bar: every block pair of every unit within it, or within 8 x that unit's per-block conditioning where that is
+# larger.  Measured worst on an MI355X over every route: ~5e-4 (tiny control-control blocks), most routes below 1e-4
+# (DESIGN.md section 5).
+HESS_BLOCK_BAR = 1e-3
+
+
+def hess_block_pairs(groups=HESS_GROUPS):
+    """the unordered group pairs (a, b), a before b in `groups` order: 21 for HESS_GROUPS"""
+    names = list(groups)
+    return [(a, b) for i, a in enumerate(names) for b in names[i:]]
+
+
+def _pair_sq(H, groups, a, b):
+    """per unit: squared Frobenius norm of the (a, b) block pair — both H[a, b] and H[b, a] when a != b"""
+    sa, sb = groups[a], groups[b]
+    s = (H[sa, sb] ** 2).sum(axis=(0, 1))
+    return s if a == b else s + (H[sb, sa] ** 2).sum(axis=(0, 1))
+
+
+def hess_block_norms(H, groups=HESS_GROUPS):
+    """{'a-b': (n,) Frobenius norm of the block pair}, and (n,) the Frobenius norm of the whole unit"""
+    H = np.asarray(H, dtype=np.float64)
+    whole = np.sqrt((H ** 2).sum(axis=(0, 1)))
+    return {f"{a}-{b}": np.sqrt(_pair_sq(H, groups, a, b)) for a, b in hess_block_pairs(groups)}, whole
+
+
+def hess_block_rel(got, want, floor=1e-6, groups=HESS_GROUPS):
+    """{'a-b': (n,)} per unit and block pair:  ||got_ab - want_ab||_F / max(||want_ab||_F, floor * ||want||_F).
+    One norm over the whole (21, 21) unit is dominated by the dt row and column (no factor of dt there; the state and control
+    blocks carry dt or dt^2): a wrong control-control block moves it by ~1e-6.  A block the reference makes (near) zero is
+    held to floor * the unit's norm instead of its own."""
+    got = np.asarray(got, dtype=np.float64); want = np.asarray(want, dtype=np.float64)
+    d = got - want
+    whole = np.sqrt((want ** 2).sum(axis=(0, 1)))
+    out = {}
+    for a, b in hess_block_pairs(groups):
+        den = np.maximum(np.sqrt(_pair_sq(want, groups, a, b)), floor * whole)
+        with np.errstate(all="ignore"):
+            out[f"{a}-{b}"] = np.sqrt(_pair_sq(d, groups, a, b)) / np.maximum(den, 1e-300)
+    return out
+
+
+def hess_block_conditioning(orc, X, U, dt, lam, want=None, eps=1e-7, draws=2, seed=0, floor=1e-6, groups=HESS_GROUPS):
+    """Per block pair and unit, how far the float64 reference Hessian itself moves when x and u are perturbed by a relative
+    `eps` (about one fp32 ulp; random signs, worst of `draws` draws), in the metric of hess_block_rel: {'a-b': (n,)}.
+    Follows `conditioning`: no fp32 evaluation can be expected to agree with the reference much better than this."""
+    rng = np.random.default_rng(seed)
+    if want is None:
+        want = oracle_step_hessian(orc, X, U, dt, lam)
+    dev = {k: np.zeros(X.shape[1]) for k in (f"{a}-{b}" for a, b in hess_block_pairs(groups))}
+    for _ in range(draws):
+        Xp = X * (1.0 + eps * rng.choice([-1.0, 1.0], X.shape))
+        Up = U * (1.0 + eps * rng.choice([-1.0, 1.0], U.shape))
+        e = hess_block_rel(oracle_step_hessian(orc, Xp, Up, dt, lam), want, floor, groups)
+        for k in dev:
+            dev[k] = np.maximum(dev[k], np.nan_to_num(e[k], nan=np.inf))
+    return dev
+
+
+def check_hess_blocks(name, got, want, bar, *, route=None, cond=None, factor=8.0, floor=HESS_FLOOR, groups=HESS_GROUPS,
+                      populated=0.5, zero=(), alt=None):
+    """Assert on every block pair of every unit:  hess_block_rel(got, want) <= max(bar, factor * cond[block])  (cond: the
+    per-block conditioning of hess_block_conditioning, or None for the plain bar), and that each block is above the floor
+    on at least a `populated` fraction of the units, so that no block is checked vacuously.  Blocks named in `zero` are
+    zero in the model itself: they are exempt from that, and the metric holds them to bar * floor * the unit's norm.
+    `alt`: a second reference (a finer difference step) a unit may be held to instead, block by block.
+    One parity_report line per call: p50 / p99 / worst per block, the route, the bar.  Returns the errors."""
+    got = np.asarray(got, dtype=np.float64); want = np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape and got.shape[:2] == (21, 21), (name, got.shape, want.shape)
+    err = hess_block_rel(got, want, floor, groups)
+    if alt is not None:
+        err2 = hess_block_rel(got, alt, floor, groups)
+        err = {k: np.fmin(v, err2[k]) for k, v in err.items()}
+    err = {k: np.where(np.isnan(v), np.inf, v) for k, v in err.items()}
+    norms, whole = hess_block_norms(want, groups)
+    frac = {k: float((v > floor * whole).mean()) for k, v in norms.items()}
+    bound = {k: np.maximum(bar, factor * cond[k]) if cond is not None else np.full(v.shape, float(bar)) for k, v in err.items()}
+    bad = {k: int((v > bound[k]).sum()) for k, v in err.items()}
+    blocks = {k: [float(np.median(v)), float(np.quantile(v, 0.99)), float(v.max())] for k, v in err.items()}
+    worst = max(blocks, key=lambda k: blocks[k][2])
+    rep = dict(route=route, bar=bar, floor=floor, units=int(got.shape[-1]), worst_block=worst, worst=blocks[worst][2],
+               violations=int(sum(bad.values())), blocks_p50_p99_max=blocks, frac_above_floor=frac)
+    if cond is not None:
+        rep["over_bar_by_conditioning"] = int(sum(((v > bar) & (v <= bound[k])).sum() for k, v in err.items()))
+    parity_report(name, **rep)
+    assert not any(bad.values()), (name, route, {k: (n, blocks[k][2]) for k, n in bad.items() if n})
+    thin = {k: f for k, f in frac.items() if f < populated and k not in zero}
+    assert not thin, (name, "blocks at or below the floor on most units (a vacuous check):", thin)
+    return err
+
+
+def check_hess_against_oracle(name, got, orc, X, U, dt, lam, bar=HESS_BLOCK_BAR, *, route=None, want=None, **kw):
+    """check_hess_blocks against oracle_step_hessian, with the per-block conditioning of the same units"""
+    if want is None:
+        want = oracle_step_hessian(orc, X, U, dt, lam)
+    groups = kw.get("groups", HESS_GROUPS)
+    cond = hess_block_conditioning(orc, X, U, dt, lam, want=want, floor=kw.get("floor", HESS_FLOOR), groups=groups)
+    return check_hess_blocks(name, got, want, bar, route=route, cond=cond, **kw)

@@ -76,6 +76,11 @@ def test_cfg3_second_order_blocks_at_full_size(cfg3):
     rel = float((num / np.maximum(den, 1e-30)).max())
     parity_report("cfg3_hess_full_size", units=len(flat), rel_block_max=rel)
     assert rel < 5e-4
+    # every block pair of every sampled unit on its own (the whole-unit norm is dominated by the dt row and column)
+    from tests.helpers import check_hess_against_oracle
+    check_hess_against_oracle("hess_blocks[cfg3_full_size_in_place]", got, make_oracle(ac), Xs, Us, 0.01, ls,
+                              route="ac_shoot_hess_f32 in place, 3 200 tasks: k_nn_stage_tensors_rev3<8,true> + k_step_hess<NN>",
+                              want=want)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(X.device)  # noqa: E731
     alone = ac.step_hess(dev(Xs), dev(Us), 0.01, dev(ls))
     assert torch.equal(alone, torch.from_numpy(np.ascontiguousarray(Hz.cpu().numpy()[k, :, :, b].transpose(1, 2, 0))).to(X.device))

@@ -4,8 +4,8 @@ up (e.g. stall scaling x sub-stepped sensitivities x per-unit dt on a ragged bat
 import numpy as np
 import pytest
 
-from tests.helpers import (block_rel_err, f32_exact, make_aircraft, make_oracle, oracle_step_hessian, rel_fro, unit_max_rel,
-                           synthetic_units)
+from tests.helpers import (HESS_BLOCK_BAR, HESS_FLOOR, block_rel_err, check_hess_blocks, f32_exact, hess_block_conditioning,
+                           hess_block_rel, make_aircraft, make_oracle, oracle_step_hessian, rel_fro, unit_max_rel, synthetic_units)
 
 pytestmark = pytest.mark.gpu
 
@@ -57,16 +57,21 @@ def test_random_configuration(gpu, seed):
         Hr = oracle_step_hessian(orc, X, U, dts, lam)
         num = np.sqrt(((Hm - Hr) ** 2).sum(axis=(0, 1))); den = np.sqrt((Hr ** 2).sum(axis=(0, 1)))
         rel = num / np.maximum(den, 1e-30)
-        if rel.max() >= 1e-3:
+        # every block pair of every unit on its own, within the bar or 8 x the unit's per-block conditioning
+        cond = hess_block_conditioning(orc, X, U, dts, lam, want=Hr, floor=HESS_FLOOR)
+        eb = hess_block_rel(Hm, Hr, HESS_FLOOR)
+        Hr7 = None
+        if rel.max() >= 1e-3 or any((v > np.maximum(HESS_BLOCK_BAR, 8.0 * cond[k])).any() for k, v in eb.items()):
             # The CHECKER differentiates exact Jacobians by central differences with h = 1e-5: a unit whose alpha or beta passes
             # through 0 inside that step (the |.| kinks of the stall scaling) gets a wrong reference, not a wrong kernel —
             # tools/fuzz_diag.py, round 3: seeds 157, 214, 302, 463 disagree by 3e-2 .. 1 at h = 1e-5 and by < 1e-6 at h = 1e-7.
-            # Such units are re-checked against the finer step.
+            # Such units are re-checked against the finer step (per unit, and per block below).
             Hr7 = oracle_step_hessian(orc, X, U, dts, lam, h=1e-7)
             num7 = np.sqrt(((Hm - Hr7) ** 2).sum(axis=(0, 1))); den7 = np.sqrt((Hr7 ** 2).sum(axis=(0, 1)))
             rel = np.minimum(rel, num7 / np.maximum(den7, 1e-30))
             assert (rel >= 1e-3).sum() == 0 and (num / np.maximum(den, 1e-30) >= 1e-3).sum() <= max(2, n // 50), tag
         assert rel.max() < 1e-3, tag
+        check_hess_blocks(f"fuzz_hess_blocks[seed={seed}]", Hm, Hr, HESS_BLOCK_BAR, route=tag, cond=cond, alt=Hr7, populated=0.0)
     # a short rollout from the same states
     H = 6
     Uh = f32_exact(np.tile(U[None], (H, 1, 1)))

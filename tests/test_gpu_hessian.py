@@ -3,7 +3,8 @@ central differences of the oracle's exact float64 Jacobians."""
 import numpy as np
 import pytest
 
-from tests.helpers import f32_exact, make_aircraft, make_oracle, oracle_step_hessian, synthetic_units
+from tests.helpers import (QUAD_HESS_GROUPS, check_hess_against_oracle, f32_exact,
+                           make_aircraft, make_oracle, oracle_step_hessian, synthetic_units)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,6 +22,28 @@ def rel_block(got, want):
     return float((num / np.maximum(den, 1e-30)).max())
 
 
+def nn_route(hidden, use_mfma=True, n_products=None):
+    """The stage-tensor kernel hess_single (aircraft_hip.hip) dispatches for a net (widths after the fold of activation-free
+    layers), then k_step_hess: last_launch() names only the latter.  Register tiles per slab: width <= 32 -> 2, <= 64 -> 4,
+    else 8; width 128 takes the reverse sweep for one to three hidden products, the slab kernel and its cross-pair launch for
+    more (matrix cores only)."""
+    widths = (32,) if hidden is None else tuple(hidden)
+    wt = 2 if max(widths) <= 32 else 4 if max(widths) <= 64 else 8
+    mf = "true" if use_mfma else "false"
+    nprod = len(widths) - 1 if n_products is None else n_products
+    if wt == 8 and 1 <= nprod <= 3:
+        return f"k_nn_stage_tensors_rev3<8,{mf}> ({nprod} hidden product(s)) + k_step_hess<NN>"
+    if wt == 8:
+        assert use_mfma
+        return "k_nn_stage_tensors<8,true,0> + k_nn_stage_tensors<8,true,1> (cross pairs) + k_step_hess<NN>"
+    return f"k_nn_stage_tensors<{wt},{mf},0> + k_step_hess<NN>"
+
+
+def assert_launched(ac, substeps=1):
+    name = ac.last_launch()[0]
+    assert name == ("k_step_hess" if substeps == 1 else "k_step_hess (composed over sub-steps)"), name
+
+
 def units(n, seed):
     X, U = synthetic_units(n, seed=seed, flaps=True)
     rng = np.random.default_rng(seed + 100)
@@ -35,9 +58,13 @@ def test_hessian_matches_finite_differences_of_exact_jacobians(gpu, model, norma
     orc = make_oracle(ac)
     X, U, lam = units(96, seed=31)
     Hm = ac.step_hess(dev(X, gpu), dev(U, gpu), 0.01, dev(lam, gpu)).cpu().numpy().astype(np.float64)
+    assert_launched(ac)
     want = oracle_step_hessian(orc, X, U, 0.01, lam)
     assert Hm.shape == (21, 21, 96)
     assert rel_block(Hm, want) < 2e-4
+    # every block pair of every unit on its own (the whole-unit norm is dominated by the dt row and column)
+    check_hess_against_oracle(f"hess_blocks[{model}-normalise={normalise}-stall={model == 'default'}]", Hm, orc, X, U, 0.01, lam,
+                              route=f"k_step_hess<{model.upper()}>", want=want)
     # structure: symmetric (every (a, b) pair is computed on its own lane), zero rows for position and the thrust controls
     assert np.abs(Hm - Hm.transpose(1, 0, 2)).max() <= 1e-5 * np.abs(Hm).max()
     for z in (0, 1, 2, 16, 17, 18):
@@ -45,9 +72,36 @@ def test_hessian_matches_finite_differences_of_exact_jacobians(gpu, model, norma
     assert np.abs(want[[0, 1, 2, 16, 17, 18]]).max() < 1e-6 * np.abs(want).max()
 
 
+@pytest.mark.parametrize("model,stall,normalise,per_unit_dt", [("default", False, False, False), ("default", False, True, True),
+                                                               ("default", True, False, True), ("linear", False, False, False)])
+def test_hessian_blocks_analytic_variants(gpu, model, stall, normalise, per_unit_dt):
+    """k_step_hess on the analytic models where the test above does not reach: the default model without stall scaling, the
+    linear table without normalisation, per-unit dt (its own tangent direction of the step): every block pair of every unit."""
+    ac = make_aircraft(model, normalise=normalise, stall_scaling=stall)
+    orc = make_oracle(ac)
+    X, U, lam = units(96, seed=35)
+    dt = f32_exact(np.random.default_rng(4).uniform(0.005, 0.02, 96)) if per_unit_dt else 0.01
+    Hm = ac.step_hess(dev(X, gpu), dev(U, gpu), dev(dt, gpu) if per_unit_dt else dt, dev(lam, gpu)).cpu().numpy().astype(np.float64)
+    assert_launched(ac)
+    want = oracle_step_hessian(orc, X, U, dt, lam)
+    # with stall scaling, a unit whose alpha or beta sits at a |.| kink gets a wrong reference at h = 1e-5 (here unit 17,
+    # beta = 1.3e-6 rad: 7e-3 against h = 1e-7); such units may meet the finer step instead (tests/test_gpu_fuzz.py)
+    alt = oracle_step_hessian(orc, X, U, dt, lam, h=1e-7) if stall else None
+    num = lambda ref: np.sqrt(((Hm - ref) ** 2).sum(axis=(0, 1))) / np.sqrt((ref ** 2).sum(axis=(0, 1)))  # noqa: E731
+    rel = num(want) if alt is None else np.minimum(num(want), num(alt))
+    assert rel.max() < 2e-4 and (num(want) >= 2e-4).sum() <= 1, (float(rel.max()), int((num(want) >= 2e-4).sum()))
+    assert np.abs(Hm - Hm.transpose(1, 0, 2)).max() <= 1e-5 * np.abs(Hm).max()
+    for z in (0, 1, 2, 16, 17, 18):
+        assert not Hm[z].any() and not Hm[:, z].any()
+    check_hess_against_oracle(f"hess_blocks[{model}-stall={stall}-normalise={normalise}-dt_per_unit={per_unit_dt}]", Hm, orc, X, U,
+                              dt, lam, route=f"k_step_hess<{model.upper()}>", want=want, alt=alt)
+
+
 @pytest.mark.parametrize("hidden,normalise,use_mfma", [((64, 64, 64), True, True), (None, False, True), ((128, 128, 128, 128), True, True),
                                                        ((32, 32), True, False), ((128, 100, 128), True, False),
-                                                       ((128, 128), True, False), ((128, 128), False, True)])
+                                                       ((128, 128), True, False), ((128, 128), False, True),
+                                                       ((32, 32), True, True), ((64, 64, 64), True, False), (None, True, False),
+                                                       ((128, 128, 128), True, True), ((128, 128, 128, 128), True, False)])
 def test_hessian_mlp_surrogate(gpu, hidden, normalise, use_mfma):
     """MLP surrogate: stage tensors (y, J, d2y/dz dz) from the MFMA engine's second-order mode, then the same
     second-order forward-mode kernel.  hidden=None is the reference's own network (Linear-tanh-Linear)."""
@@ -55,12 +109,15 @@ def test_hessian_mlp_surrogate(gpu, hidden, normalise, use_mfma):
     orc = make_oracle(ac)
     X, U, lam = units(80, seed=41)
     Hm = ac.step_hess(dev(X, gpu), dev(U, gpu), 0.01, dev(lam, gpu)).cpu().numpy().astype(np.float64)
+    assert_launched(ac)
     want = oracle_step_hessian(orc, X, U, 0.01, lam)
     assert np.isfinite(Hm).all()
     assert rel_block(Hm, want) < 5e-4
     assert np.abs(Hm - Hm.transpose(1, 0, 2)).max() <= 2e-5 * np.abs(Hm).max()
     for z in (0, 1, 2, 16, 17, 18):
         assert not Hm[z].any() and not Hm[:, z].any()
+    check_hess_against_oracle(f"hess_blocks[nn-{hidden}-normalise={normalise}-mfma={use_mfma}]", Hm, orc, X, U, 0.01, lam,
+                              route=nn_route(hidden, use_mfma), want=want)
     # the workspace can be sized ahead of time (hipGraph capture); a later, larger call re-uses / grows it
     from aircraft_amd import _lib
     assert _lib.load().ac_reserve_hess_workspace(ac._handle, 300) == 0
@@ -76,7 +133,9 @@ def test_hessian_per_unit_dt_and_numpy_vector(gpu):
     X, U, lam = units(40, seed=33)
     dts = f32_exact(np.random.default_rng(2).uniform(0.005, 0.02, 40))
     Hm = ac.step_hess(dev(X, gpu), dev(U, gpu), dev(dts, gpu), dev(lam, gpu)).cpu().numpy().astype(np.float64)
-    assert rel_block(Hm, oracle_step_hessian(orc, X, U, dts, lam)) < 2e-4
+    want = oracle_step_hessian(orc, X, U, dts, lam)
+    assert rel_block(Hm, want) < 2e-4
+    check_hess_against_oracle("hess_blocks[poly-dt_per_unit]", Hm, orc, X, U, dts, lam, route="k_step_hess<POLY>", want=want)
     one = ac.step_hess(X[:, 3], U[:, 3], float(dts[3]), lam[:, 3])  # numpy vectors in -> (21, 21) float64 out
     assert one.shape == (21, 21) and np.allclose(one, Hm[:, :, 3], rtol=0, atol=1e-6 * np.abs(Hm[:, :, 3]).max())
 
@@ -93,8 +152,14 @@ def test_hessian_quadrotor(gpu):
     X, U = quad_units(64, seed=9)
     lam = f32_exact(np.random.default_rng(3).normal(size=(13, 64)))
     Hm = q.step_hess(dev(X, gpu), dev(U, gpu), 0.02, dev(lam, gpu)).cpu().numpy().astype(np.float64)
+    assert_launched(q)
     want = oracle_step_hessian(orc, X, pad7(U), 0.02, lam)
     assert rel_block(Hm, want) < 2e-4
+    # per block: the quadrotor's layout (four thrusts in rows 13:17); its velocity rows are exactly zero in the model, and the
+    # metric holds them to bar x floor x the unit's norm
+    check_hess_against_oracle("hess_blocks[quadrotor]", Hm, orc, X, pad7(U), 0.02, lam,
+                              route="k_step_hess<QUAD>", want=want, groups=QUAD_HESS_GROUPS,
+                              zero=("v-v", "v-q", "v-w", "v-thrust"))
     for z in (0, 1, 2, 17, 18, 19):  # position, and the three control rows this plugin does not have
         assert not Hm[z].any() and not Hm[:, z].any()
     assert np.abs(Hm[13:17, 13:17]).max() > 0  # thrust-thrust curvature comes from the normalisation and RK4 coupling
@@ -201,6 +266,9 @@ def test_single_layer_net_first_and_second_order(gpu, act_last):
     assert np.isfinite(Hm).all()
     parity_report(f"single_layer_hess[act={act_last}]", rel_block=rel_block(Hm, want))
     assert rel_block(Hm, want) < 5e-4
+    assert_launched(ac)
+    check_hess_against_oracle(f"hess_blocks[single_layer-act={act_last}]", Hm, orc, X, U, 0.01, lam,
+                              route="L == 1: k_nn_stage_tensors<2,true,0> + k_step_hess<NN>", want=want)
     # same handle, repeated: identical bits (no dependence on what earlier calls left in registers / LDS / workspace)
     H2 = ac.step_hess(dev(X, gpu), dev(U, gpu), 0.01, dev(lam, gpu)).cpu().numpy().astype(np.float64)
     assert np.array_equal(Hm, H2)
@@ -253,7 +321,8 @@ def test_hessian_reads_nothing_it_did_not_write(gpu, hidden):
 
 @pytest.mark.parametrize("model,hidden,substeps,normalise", [("default", None, 3, True), ("poly", None, 10, False),
                                                              ("poly", None, 10, True), ("nn", (64, 64, 64), 4, True),
-                                                             ("nn", None, 10, True), ("nn", (128, 128, 128), 3, True)])
+                                                             ("nn", None, 10, True), ("nn", (128, 128, 128), 3, True),
+                                                             ("poly", None, 2, True), ("nn", (64, 64, 64), 2, False)])
 def test_hessian_composed_over_substeps(gpu, model, hidden, substeps, normalise):
     """physical_integration_substeps > 1 (the reference's default is 10): the blocks of the sub-steps composed on the
     device — sum_s T_s' H_s T_s with the first-order chain and the pulled-back multipliers — against central differences
@@ -269,6 +338,10 @@ def test_hessian_composed_over_substeps(gpu, model, hidden, substeps, normalise)
     from tests.helpers import parity_report
     parity_report(f"hess_substeps[{model}-{hidden}-{substeps}]", rel_block=rel_block(Hm, want))
     assert rel_block(Hm, want) < 1e-3
+    assert_launched(ac, substeps)
+    route = f"sum_s T_s' H_s T_s over {substeps} sub-steps of " + (nn_route(hidden) if model == "nn" else f"k_step_hess<{model.upper()}>")
+    check_hess_against_oracle(f"hess_blocks[substeps-{model}-{hidden}-{substeps}-normalise={normalise}]", Hm, orc, X, U, dt, lam,
+                              route=route, want=want)
     assert np.abs(Hm - Hm.transpose(1, 0, 2)).max() <= 2e-5 * np.abs(Hm).max()
     for z in (0, 1, 2, 16, 17, 18):
         assert not Hm[z].any() and not Hm[:, z].any()
@@ -277,7 +350,10 @@ def test_hessian_composed_over_substeps(gpu, model, hidden, substeps, normalise)
     import torch
     dts = f32_exact(np.random.default_rng(5).uniform(0.01, 0.03, n))
     H2 = ac.step_hess(dev(X, gpu), dev(U, gpu), dev(dts, gpu), dev(lam, gpu)).cpu().numpy().astype(np.float64)
-    assert rel_block(H2[:, :, :24], oracle_step_hessian(orc, X[:, :24], U[:, :24], dts[:24], lam[:, :24])) < 1e-3
+    want2 = oracle_step_hessian(orc, X[:, :24], U[:, :24], dts[:24], lam[:, :24])
+    assert rel_block(H2[:, :, :24], want2) < 1e-3
+    check_hess_against_oracle(f"hess_blocks[substeps-{model}-{hidden}-{substeps}-dt_per_unit]", H2[:, :, :24], orc, X[:, :24],
+                              U[:, :24], dts[:24], lam[:, :24], route=route, want=want2)
     ms = MultipleShooting(system=ac, dt=dt, num_nodes=7, opts={"quaternion": "integration" if normalise else None})
     B = n // 7
     Xs = dev(X[:, : 7 * B].reshape(13, 7, B).transpose(1, 0, 2), gpu)
@@ -322,6 +398,11 @@ def test_width_128_stage_tensors_by_reverse_sweep(gpu, hidden, act_last, n, kern
     assert np.isfinite(Hh).all()
     assert rel_block(Hh[:, :, :m], want) < 5e-4
     assert np.abs(Hh - Hh.transpose(1, 0, 2)).max() <= 2e-5 * np.abs(Hh).max()
+    assert_launched(ac)
+    route = nn_route(hidden)
+    assert ("rev3" in route) == (kernel == "rev"), route
+    check_hess_against_oracle(f"hess_blocks[w128-{hidden}-act_last={act_last}-n={n}]", Hh[:, :, :m], orc, X[:, :m], U[:, :m], 0.01,
+                              lam[:, :m], route=route, want=want)
     # same inputs twice on the same handle: identical bits (scratch slots, ring position and workspace carry nothing over)
     H2 = ac.step_hess(Xd, Ud, 0.01, Ld)
     assert torch.equal(Hm, H2)
@@ -329,4 +410,3 @@ def test_width_128_stage_tensors_by_reverse_sweep(gpu, hidden, act_last, n, kern
     perm = torch.randperm(n, device=gpu)
     Hp = ac.step_hess(Xd[:, perm].contiguous(), Ud[:, perm].contiguous(), 0.01, Ld[:, perm].contiguous())
     assert torch.equal(Hp, Hm[:, :, perm])
-    del kernel  # (documents which stage-tensor kernel the dispatcher picks: profiles/r03_hess_rev_stats.txt shows it by name)

@@ -147,6 +147,14 @@ def test_costate_and_newton_backward_match_numpy(gpu):
     f64 = lambda t: t.cpu().numpy().astype(np.float64)  # noqa: E731
     assert rel_fro(f64(Lam), io.costate(cost, f64(X), f64(A))) < 1e-5
     Hz = il.hessian(X, Ud, Lam)
+    # the blocks fed to both sides below come from the GPU: check them on their own against the oracle, block by block, on a
+    # sample of nodes x instances (node k: (x_k, u_k, dt) with the costate Lam[k])
+    from tests.helpers import check_hess_against_oracle
+    ks = np.repeat([0, 5, 10, 15], 12); bs = np.tile(np.arange(12), 4)
+    Xh, Lh, Hh = f64(X), f64(Lam), f64(Hz)
+    Xs = np.ascontiguousarray(Xh[ks, :, bs].T); Us = np.ascontiguousarray(U[ks, :, bs].T); Ls = np.ascontiguousarray(Lh[ks, :, bs].T)
+    check_hess_against_oracle("hess_blocks[ilqr_newton_Hz]", Hh[ks, :, :, bs].transpose(1, 2, 0), make_oracle(ac), Xs, Us, 0.01, Ls,
+                              route="ac_shoot_hess_f32 (ILQR.hessian): k_step_hess<POLY>")
     K, kff, dV = il.backward(X, Ud, A, Bm, Hz=Hz)
     Kr, kr, dVr = io.backward(cost, f64(X), U, f64(A), f64(Bm), Hz=f64(Hz))
     assert rel_fro(f64(K), Kr) < 2e-3 and rel_fro(f64(kff), kr) < 2e-3 and rel_fro(f64(dV), dVr) < 2e-3

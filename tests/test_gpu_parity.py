@@ -311,6 +311,14 @@ def test_activation_free_layers_are_folded(gpu, act):
     eh = unit_max_rel(Hd, Hr)  # every unit on its own
     parity_report(f"step_hess_folded{act}", unit_rel_max=float(eh.max()), unit_rel_p50=float(np.median(eh)))
     assert eh.max() < 2e-3, (int(eh.argmax()), float(eh.max()))
+    # every block pair of every unit on its own; after the fold the net has as many layers as act has tanh entries before the
+    # last, plus the last layer (an all-linear net is ONE layer: the L == 1 path)
+    from tests.helpers import check_hess_against_oracle
+    kept = [w for w, a in zip((48, 24, 40), act[:-1]) if a]  # hidden widths after the fold
+    wt = 2 if max(kept, default=0) <= 32 else 4
+    check_hess_against_oracle(f"hess_blocks[folded-{act}]", Hd, orc, X, U, 0.01, lam,
+                              route=f"{len(kept) + 1} layer(s) after the fold: k_nn_stage_tensors<{wt},true,0> + k_step_hess<NN>",
+                              want=Hr)
 
 
 @pytest.mark.parametrize("hidden", [(128,), (128, 128), (100, 128), (128, 128, 128)])
