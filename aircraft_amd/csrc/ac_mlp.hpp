@@ -433,29 +433,15 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     static constexpr bool kPairRing = PAIR != 0;
     static constexpr int kBfFront = (WT / 2) * KC * 3 * 1024 + 1024, kBfBack = (WT / 2) * KC * 3 * 1024;
 
-    AC_DI static unsigned cvt_pk_bf16(float x, float y) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    AC_DI static unsigned cvt_pk_bf16(f32x2 xy) {
         typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x, y}, bf16x2));  // v_cvt_pk_bf16_f32 (RNE)
+        return __builtin_bit_cast(unsigned, __builtin_convertvector(xy, bf16x2));  // v_cvt_pk_bf16_f32 (RNE)
     }
+    AC_DI static unsigned cvt_pk_bf16(float x, float y) { return cvt_pk_bf16(f32x2{x, y}); }
     // k-chunk c of slab s as the B operand: lane (col, g), element q = rows 4 g + q of tile 2c (q < 4) and 4 g + q - 4 of
-    // tile 2c + 1 — the host permuted the weight columns to match (bf16_chunk_row) — in three planes
-    AC_DI void split_chunk(int s, int c, bf16x8 (&p)[3]) const {
-        u32x4 q[3];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float x = a[s][2 * c + (i >> 1)][(2 * i) & 3], y = a[s][2 * c + (i >> 1)][(2 * i + 1) & 3];
-            unsigned u = cvt_pk_bf16(x, y);
-            q[0][i] = u;
-            x -= __uint_as_float(u << 16); y -= __uint_as_float(u & 0xffff0000u);
-            u = cvt_pk_bf16(x, y);
-            q[1][i] = u;
-            x -= __uint_as_float(u << 16); y -= __uint_as_float(u & 0xffff0000u);
-            q[2][i] = cvt_pk_bf16(x, y);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p[k] = __builtin_bit_cast(bf16x8, q[k]);
-    }
+    // tile 2c + 1 — the host permuted the weight columns to match (bf16_chunk_row) — in three planes q[0..2]; pair i =
+    // elements 2 i, 2 i + 1 of the chunk (split_pair below; layer_bf runs it in stages, bf_stage)
     AC_DI static f32x4 mfma_bf(const bf16x8& w, const bf16x8& x, f32x4 c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0);
     }
@@ -474,106 +460,304 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
         __builtin_amdgcn_sched_barrier(0);
     }
     // Slab 0 reaches the back half: wait for it (every wave's pieces, then the barrier), then request the next layer's front.
+    // (-DAC_STAMPS_MID, on top of the diagnostic build: the two waits apart — the back half's DMA into stamp [6], the drift
+    // between the waves at the barrier into [0]; both slots are next to empty otherwise)
     AC_DI void mid_layer() {
+#ifdef AC_STAMPS_MID
+        AC_MARK(st, 9);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        AC_MARK(st, 6);
+        __syncthreads();
+        AC_MARK(st, 0);
+#else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+#endif
         if constexpr (!kPairRing) lds_dma_copy(this->bf_next_src, lds + this->bf_next_dst, kBfFront, wave, nwaves, lane);
     }
 
-    // One hidden layer (WT x WT tiles, tanh) on all slabs.  Per slab: CH output tiles at a time, each over the KC k-chunks with
-    // six MFMAs per chunk and tile (a "block").  Straight-line code, one fenced region per block: the A fragments of the NEXT
-    // block are requested at its head, and the VALU work runs beside the block's matrix stream (a bf16 MFMA holds vector issue
-    // for 8 of its 16 cycles): in block 1 + i of a chunk of output tiles the epilogue of its tile i in the previous slab, and in
-    // the last chunk of output tiles, behind block c, the split of the next slab's k-chunk c into the planes block c has just
-    // consumed — one set of planes live at any time (48 registers; a second set cost 260 B of scratch per lane).
-    AC_DI void layer_bf(const char* wfront) {
-        const bf16x8* wf0 = reinterpret_cast<const bf16x8*>(wfront) + lane;
-        const bf16x8* wf1 = reinterpret_cast<const bf16x8*>(this->bf_back) + lane;
-        const f32x4* bias4 = reinterpret_cast<const f32x4*>(wfront + kBfBack);
-        constexpr int C = CH;
-        static_assert(WT % C == 0 && (WT / 2) % C == 0 && C < KC, "a chunk of output tiles lies in one half");
-        // LDS addresses of this lane's piece in the two halves (generic -> LDS pointer: the low 32 bits)
-        const unsigned la0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf0;
-        const unsigned la1 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf1;
-        static_assert((WT / 2) * KC * 3 * 1024 <= 65536, "a half-layer fits the ds_read immediate offset");
-        auto frag = [&](int nt, int c, int p) -> bf16x8 {
-            return ds_frag(nt < WT / 2 ? la0 : la1, (((nt % (WT / 2)) * KC + c) * 3 + p) * 1024);
-        };
-        f32x4 o[2][WT];
-        bf16x8 xc[KC][3];
-        bf16x8 w[2][C][3];  // A fragments: the block running, the next one
-#pragma unroll
-        for (int i = 0; i < C; ++i)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) w[0][i][p] = frag(i, 0, p);
-#pragma unroll
-        for (int c = 0; c < KC; ++c) split_chunk(0, c, xc[c]);
-#pragma unroll
-        for (int s = 0; s < NSLAB; ++s) {
-#pragma unroll
-            for (int nc = 0; nc < WT; nc += C) {
-                f32x4 hi[C], lo[C];
-#pragma unroll
-                for (int i = 0; i < C; ++i) {
-                    hi[i] = (s == 0 && !kNoValue) ? bias4[(nc + i) * 4 + g] : f32x4{0.f, 0.f, 0.f, 0.f};
-                    lo[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int c = 0; c < KC; ++c) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    const int cur = ((nc / C) * KC + c) & 1;
-                    const bool last_c = c + 1 == KC;
-                    const int nnc = last_c ? nc + C : nc, nkc = last_c ? 0 : c + 1;
-                    const bool more = !(s + 1 == NSLAB && nnc == WT);
-                    // slab 0 about to enter the back half: wait for it before the first read of it
-                    if (s == 0 && last_c && nnc == WT / 2) { mid_layer(); __builtin_amdgcn_sched_barrier(0); }
-                    // this block's fragments (requested at the head of the previous block) have landed
-                    wait_frags();
-                    if (more) {
-#pragma unroll
-                        for (int i = 0; i < C; ++i)
-#pragma unroll
-                            for (int p = 0; p < 3; ++p) w[cur ^ 1][i][p] = frag((nnc % WT) + i, nkc, p);
-                    }
-                    const bf16x8 (&wc)[C][3] = w[cur];
-#pragma unroll
-                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][2], xc[c][0], lo[i]);
-#pragma unroll
-                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][0], xc[c][2], lo[i]);
-#pragma unroll
-                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][1], xc[c][1], lo[i]);
-#pragma unroll
-                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][1], xc[c][0], lo[i]);
-#pragma unroll
-                    for (int i = 0; i < C; ++i) lo[i] = mfma_bf(wc[i][0], xc[c][1], lo[i]);
-#pragma unroll
-                    for (int i = 0; i < C; ++i) hi[i] = mfma_bf(wc[i][0], xc[c][0], hi[i]);
-                    // the previous slab's epilogue of these tiles (its accumulators are long complete; the tangent epilogues read
-                    // the new value activations, finished during slab 1)
-                    if (c >= 1 && c <= C && s > 0) epilogue_tile<WT, 1>(s - 1, nc + c - 1, o[(s - 1) & 1], 1);
-                    // the next slab's split of this k-chunk (its inputs are read nowhere else)
-                    if (nc + C == WT && s + 1 < NSLAB) split_chunk(s + 1, c, xc[c]);
-                }
-#pragma unroll
-                for (int i = 0; i < C; ++i) o[s & 1][nc + i] = hi[i] + lo[i];
+    // One hidden layer (WT x WT tiles, tanh) on all slabs.  A block = CH output tiles over one k-chunk: six MFMAs per tile.
+    // A bf16 MFMA holds vector issue for 8 of its 16 cycles, so the gap behind it hides two plain vector instructions (or
+    // one v_exp / v_rcp) and every further one is paid in full.  The vector work of a layer (activation splits, epilogues,
+    // hi + lo sums, the fragment reads of the next block) about fills those gaps — when it is spread level.  So the work is
+    // cut into STAGES of at most two plain instructions, every gap gets its stages by the placement functions below, and a
+    // scheduling fence on both sides of every MFMA keeps them there (tools/mfma_gaps.py reads the result
+    // off the emitted ISA).
+    //
+    // Walk of a slab: the first NG - kTail groups of output tiles one after the other (k-chunks inner), the last kTail groups
+    // k-chunk-outer — so k-chunk c is read for the last time kTail blocks before chunk c + 1 is, and the split of the next
+    // slab's chunk c into the same plane registers has those blocks to itself (one set of planes live: a second set cost
+    // 260 B of scratch per lane).  Every accumulator still receives the same MFMAs on the same operands in the same order
+    // (chunks ascending; per chunk lo: (3,1), (1,3), (2,2), (2,1), (1,2), then hi alone), so the outputs do not change.
+    static constexpr int NG = WT / CH;        // groups of output tiles
+    static constexpr int kTail = 2;           // groups walked k-chunk-outer (both in the back half: slab 0 waits where it did)
+    static constexpr int kHead = (NG - kTail) * KC;  // blocks of the head groups
+    static constexpr int NB = NG * KC;        // blocks per slab
+    static constexpr int NGAP = 6 * CH;       // MFMAs (gaps) per block
+    static_assert(!BF || (kTail >= 2 && kTail < NG && NB % 2 == 0), "layer_bf walk");
+    AC_DI static constexpr int blk_group(int b) { return b < kHead ? b / KC : NG - kTail + (b - kHead) % kTail; }
+    AC_DI static constexpr int blk_chunk(int b) { return b < kHead ? b % KC : (b - kHead) / kTail; }
+    // block after which k-chunk c of the running slab is dead / group gi of output tiles is complete
+    AC_DI static constexpr int chunk_dead(int c) { return kHead + kTail * c + kTail - 1; }
+    AC_DI static constexpr int group_done(int gi) { return gi < NG - kTail ? gi * KC + KC - 1 : kHead + kTail * (KC - 1) + gi - (NG - kTail); }
+    // Where the vector work runs (block index; NB + b = block b of the NEXT slab):
+    // hi + lo of a group: the block after its last MFMA, behind the block's other stages and never before its fifth gap (the
+    // sum does not wait for the matrix pipe); the last group's in the next slab's first block (the last slab's: behind the layer)
+    AC_DI static constexpr int sum_blk(int gi) { return group_done(gi) + 1; }
+    // pair i (of four) of the next slab's split of k-chunk c: the kTail blocks behind the chunk's last read (the last pair of
+    // chunk KC - 2 one block later, which makes room for the sum of the last group but one); the last chunk's in blocks 1 and
+    // 2 of the next slab, which reads it in block KC - 1
+    AC_DI static constexpr int split_blk(int c, int i) {
+        if (c + 1 == KC) return NB + 1 + i / 2;
+        if (c + 2 == KC && i == 3) return NB;
+        return chunk_dead(c) + 1 + (i * kTail) / 4;
+    }
+    // scaling epilogue of tile t of tangent slab us (it reads the finished value activations: slab 0's tanh ends in slab 1).
+    // Head-group tiles of the slabs from 2 on: in the slab itself, right behind their sum, so their sums do not wait a slab
+    // in registers (epi_own); every other tile in the slab after, over the blocks between the last deferred split of that
+    // slab's planes and the first split for the next (epi_blk)
+    AC_DI static constexpr bool epi_own(int us, int t) { return (kNoValue || us >= 2) && t < (NG - kTail) * CH; }
+    AC_DI static constexpr int epi_own_blk(int t) { return sum_blk(t / CH) + 1 + (t / CH + 1 < NG - kTail ? t % CH : 0); }
+    AC_DI static constexpr int epi_blk(int us, int t) {
+        return (kNoValue || us >= 2) ? KC - 1 + t - (NG - kTail) * CH : KC - 1 + (t * (chunk_dead(0) - KC + 2)) / WT;
+    }
+    // tanh of tile t of the value slab, one tile per block (it fills one): the head groups' tiles already in slab 0, behind
+    // their sums, as far as the blocks before its splits reach; the others in slab 1 (NB + b) beside no sum
+    AC_DI static constexpr int tanh_blk(int t) {
+        const int gi = t / CH, early = sum_blk(gi) + 1 + t % CH;
+        if (gi < NG - kTail && early <= chunk_dead(0)) return early;
+        int b = KC - 1;  // first block behind the deferred split
+        for (int u = 0; u < t; ++u) {
+            const int gu = u / CH;
+            if (gu < NG - kTail && sum_blk(gu) + 1 + u % CH <= chunk_dead(0)) continue;
+            ++b;
+            while (b == sum_blk(0) || b == sum_blk(1)) ++b;
+        }
+        return NB + b;
+    }
+
+    // pair i of k-chunk c of slab s in one piece (slab 0, in front of the first MFMA)
+    AC_DI void split_pair(int s, int c, int i, u32x4 (&q)[3]) const {
+        float x = a[s][2 * c + (i >> 1)][(2 * i) & 3], y = a[s][2 * c + (i >> 1)][(2 * i + 1) & 3];
+        unsigned u = cvt_pk_bf16(x, y);
+        q[0][i] = u;
+        x -= __uint_as_float(u << 16); y -= __uint_as_float(u & 0xffff0000u);
+        u = cvt_pk_bf16(x, y);
+        q[1][i] = u;
+        x -= __uint_as_float(u << 16); y -= __uint_as_float(u & 0xffff0000u);
+        q[2][i] = cvt_pk_bf16(x, y);
+    }
+
+    // Work units of a block and their stages.  Unit u: [0, WT) hi + lo of tile u (2 stages); [WT, 2 WT) epilogue of tile u - WT
+    // of the slab before (tangent: 4 stages, one element each; value: 12, three per element); [2 WT, 2 WT + 4 KC) pair
+    // (u - 2 WT) % 4 of the split of k-chunk (u - 2 WT) / 4 (6 stages).
+    static constexpr int NU = 2 * WT + 4 * KC;
+    // slab the unit works on when it runs in block B of slab S, or -1: not here
+    AC_DI static constexpr int unit_slab(int S, int B, int u) {
+        if (u < WT) {
+            const int sb = sum_blk(u / CH);
+            return sb % NB == B ? (sb < NB ? S : S - 1) : -1;
+        }
+        if (u < 2 * WT) {
+            const int t = u - WT;
+            if (!kNoValue) {
+                const int tb = tanh_blk(t);
+                if ((S == 0 && tb == B) || (S == 1 && tb == NB + B)) return 0;
             }
-            __builtin_amdgcn_sched_barrier(0);
-            if (s == 0) AC_MARK(st, 9); else if (s == 1) AC_MARK(st, 10); else AC_MARK(st, 11);  // as in layer()
-            if constexpr (PAIR != 0) {
-                if (s == 1) {
-                    // as in layer(): the partner has read the previous layer's h; a[0] is h of THIS layer (slab 0's epilogue
-                    // ran during slab 1)
-                    __syncthreads();
-                    if constexpr (PAIR == 1) {
+            if (S >= kFirstTangent && epi_own(S, t) && epi_own_blk(t) == B) return S;
+            if (S > kFirstTangent && !epi_own(S - 1, t) && epi_blk(S - 1, t) == B) return S - 1;
+            return -1;
+        }
+        const int pb = split_blk((u - 2 * WT) / 4, (u - 2 * WT) % 4);
+        if (pb < NB) return (pb == B && S + 1 < NSLAB) ? S + 1 : -1;
+        return (pb == NB + B && S > 0) ? S : -1;
+    }
+    AC_DI static constexpr int unit_stages(int us, int u) {
+        return u < WT ? 2 : u < 2 * WT ? (!kNoValue && us == 0 ? 12 : 4) : 6;
+    }
+    // n-th stage that runs in gap J of block B of slab S, as unit * 16 + stage; -1: none.  One stage after the other from gap 0,
+    // the sums last
+    AC_DI static constexpr int gap_stage(int S, int B, int J, int n) {
+        int j = 0;
+        for (int v = WT; v < NU + WT; ++v) {
+            const int u = v % NU;  // epilogues, splits, then the sums
+            const int us = unit_slab(S, B, u);
+            if (us < 0) continue;
+            if (u < WT && j < 4) j = 4;
+            for (int k = 0; k < unit_stages(us, u); ++k, ++j)
+                if ((j < NGAP ? j : NGAP - 1) == J && n-- == 0) return u * 16 + k;
+        }
+        return -1;
+    }
+
+    // Registers of one layer_bf call (every index into them is a compile-time constant: they stay registers).
+    struct BfRegs {
+        f32x4 o[2][WT], hi[2][WT], lo[2][WT];  // ping-pong by slab parity: sums and epilogues of slab s - 1 run inside slab s
+        u32x4 xq[WT / 2][3];                   // the three planes of the KC k-chunks of the running slab
+        bf16x8 w[2][CH][3];                    // A fragments: the block running, the next one
+        unsigned la0, la1;                     // LDS byte addresses of this lane's piece in the two halves
+        const f32x4* bias4;
+        f32x2 sxy[2 * WT]; float tt[WT][4];    // between the stages of a split pair / of a tanh
+        unsigned su[2 * WT], sa[2 * WT], sb[2 * WT];
+    };
+    // Keeps a value computed in front of the mid-layer barrier in front of it: the DMA loop behind the barrier ends the basic
+    // block, and work whose results are first read behind it is otherwise sunk there, in front of the first MFMA
+    AC_DI static void bf_pin(float& v) { asm volatile("" : "+v"(v)); }
+    AC_DI static void bf_pin(unsigned& v) { asm volatile("" : "+v"(v)); }
+
+    // Stage K of unit U, run in block B of slab S.  The arithmetic is split_pair()'s, act_tanh()'s and epilogue_tile()'s,
+    // operation for operation.
+    template <int S, int B, int U, int K> AC_DI void bf_stage(BfRegs& r) {
+        constexpr int us = unit_slab(S, B, U);
+        constexpr bool early = S == 0 && B < kHead;  // in front of the mid-layer barrier
+        if constexpr (U < WT) {
 #pragma unroll
-                        for (int nt = 0; nt < WT; ++nt) hx[nt * 64 + lane] = f32x4{a[0][nt][0], a[0][nt][1], a[0][nt][2], a[0][nt][3]};
-                    }
+            for (int e = 2 * K; e < 2 * K + 2; ++e) {
+                float v = r.hi[us & 1][U][e] + r.lo[us & 1][U][e];
+                bf_pin(v);
+                r.o[us & 1][U][e] = v;
+            }
+        } else if constexpr (U < 2 * WT) {
+            constexpr int t = U - WT;
+            if constexpr (kNoValue) {
+                a[us][t][K] = r.o[us & 1][t][K];
+            } else if constexpr (us == 0) {
+                constexpr int e = K / 3;
+                float v;
+                if constexpr (K % 3 == 0) v = __builtin_amdgcn_exp2f(r.o[0][t][e] * 2.8853900817779268f);
+                else if constexpr (K % 3 == 1) v = __builtin_amdgcn_rcpf(1.0f + r.tt[t][e]);
+                else v = 1.0f - 2.0f * r.tt[t][e];
+                if constexpr (K % 3 != 2 || early) bf_pin(v);
+                if constexpr (K % 3 == 2) a[0][t][e] = v; else r.tt[t][e] = v;
+            } else {
+                const float h = a[0][t][K];
+                a[us][t][K] = r.o[us & 1][t][K] * fmaf(-h, h, 1.0f);
+            }
+        } else {
+            constexpr int p = U - 2 * WT, c = p / 4, i = p % 4;
+            if constexpr (K == 0) {
+                r.sxy[p] = f32x2{a[us][2 * c + (i >> 1)][(2 * i) & 3], a[us][2 * c + (i >> 1)][(2 * i + 1) & 3]};
+                r.su[p] = cvt_pk_bf16(r.sxy[p]);
+                r.xq[c][0][i] = r.su[p];
+                r.sa[p] = r.su[p] << 16;
+                bf_pin(r.sa[p]);
+            } else if constexpr (K == 1) {
+                r.sb[p] = r.su[p] & 0xffff0000u;
+                float x = r.sxy[p][0] - __uint_as_float(r.sa[p]);
+                bf_pin(r.sb[p]); bf_pin(x);
+                r.sxy[p][0] = x;
+            } else if constexpr (K == 2) {
+                r.sxy[p][1] -= __uint_as_float(r.sb[p]);
+                r.su[p] = cvt_pk_bf16(r.sxy[p]);
+                bf_pin(r.su[p]);
+                r.xq[c][1][i] = r.su[p];
+            } else if constexpr (K == 3) {
+                r.sa[p] = r.su[p] << 16;
+                r.sb[p] = r.su[p] & 0xffff0000u;
+                bf_pin(r.sa[p]); bf_pin(r.sb[p]);
+            } else if constexpr (K == 4) {
+                float x = r.sxy[p][0] - __uint_as_float(r.sa[p]), y = r.sxy[p][1] - __uint_as_float(r.sb[p]);
+                bf_pin(x); bf_pin(y);
+                r.sxy[p] = f32x2{x, y};
+            } else {
+                r.xq[c][2][i] = cvt_pk_bf16(r.sxy[p]);
+            }
+        }
+    }
+
+    AC_DI bf16x8 bf_frag(const BfRegs& r, int nt, int c, int p) const {
+        return ds_frag(nt < WT / 2 ? r.la0 : r.la1, (((nt % (WT / 2)) * KC + c) * 3 + p) * 1024);
+    }
+
+    // MFMA J of block B of slab S and what its gap carries: one fragment read of the next block behind each of the first
+    // 3 CH MFMAs, and the gap's stages.  Products in the order (3,1), (1,3), (2,2), (2,1), (1,2) into lo, then (1,1) into hi.
+    template <int S, int B, int J> AC_DI void bf_gap(BfRegs& r) {
+        constexpr int nc = blk_group(B) * CH, c = blk_chunk(B), cur = B & 1, i = J % CH, m = J / CH;
+        constexpr bool more = !(S + 1 == NSLAB && B + 1 == NB);
+        constexpr int nb = (B + 1) % NB, nnc = blk_group(nb) * CH, nkc = blk_chunk(nb);
+        constexpr int wp = m == 0 ? 2 : (m == 1 || m == 4 || m == 5) ? 0 : 1, xp = m == 1 ? 2 : (m == 2 || m == 4) ? 1 : 0;
+        const bf16x8 x = __builtin_bit_cast(bf16x8, r.xq[c][xp]);
+        if constexpr (m < 5) r.lo[S & 1][nc + i] = mfma_bf(r.w[cur][i][wp], x, r.lo[S & 1][nc + i]);
+        else r.hi[S & 1][nc + i] = mfma_bf(r.w[cur][i][wp], x, r.hi[S & 1][nc + i]);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (more && J < 3 * CH) r.w[cur ^ 1][J / 3][J % 3] = bf_frag(r, nnc + J / 3, nkc, J % 3);
+        constexpr int e0 = gap_stage(S, B, J, 0), e1 = gap_stage(S, B, J, 1);
+        static_assert(gap_stage(S, B, J, 2) < 0, "at most two stages to a gap");
+        if constexpr (e0 >= 0) bf_stage<S, B, e0 / 16, e0 % 16>(r);
+        if constexpr (e1 >= 0) bf_stage<S, B, e1 / 16, e1 % 16>(r);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (J + 1 < NGAP) bf_gap<S, B, J + 1>(r);
+    }
+
+    template <int S, int B> AC_DI void bf_block(BfRegs& r) {
+        constexpr int nc = blk_group(B) * CH, c = blk_chunk(B);
+        constexpr int nnc = blk_group((B + 1) % NB) * CH;
+        __builtin_amdgcn_sched_barrier(0);
+        // slab 0 about to enter the back half: wait for it before the first read of it
+        if constexpr (S == 0 && nc < WT / 2 && nnc >= WT / 2) { mid_layer(); __builtin_amdgcn_sched_barrier(0); }
+        // this block's fragments (requested during the previous block) have landed
+        wait_frags();
+        if constexpr (c == 0) {
+#pragma unroll
+            for (int i = 0; i < CH; ++i) {
+                r.hi[S & 1][nc + i] = (S == 0 && !kNoValue) ? r.bias4[(nc + i) * 4 + g] : f32x4{0.f, 0.f, 0.f, 0.f};
+                r.lo[S & 1][nc + i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        bf_gap<S, B, 0>(r);
+        if constexpr (B + 1 == NB) {
+            if (S == 0) AC_MARK(st, 9); else if (S == 1) AC_MARK(st, 10); else AC_MARK(st, 11);  // as in layer()
+            if constexpr (PAIR != 0 && S == 1) {
+                // as in layer(): the partner has read the previous layer's h; a[0] is h of THIS layer (slab 0's epilogue ran
+                // during slabs 0 and 1)
+                __syncthreads();
+                if constexpr (PAIR == 1) {
+#pragma unroll
+                    for (int nt = 0; nt < WT; ++nt) hx[nt * 64 + lane] = f32x4{a[0][nt][0], a[0][nt][1], a[0][nt][2], a[0][nt][3]};
                 }
             }
         }
-        __builtin_amdgcn_sched_barrier(0);
+    }
+    template <int I> AC_DI void bf_blocks(BfRegs& r) {
+        if constexpr (I < NSLAB * NB) {
+            bf_block<I / NB, I % NB>(r);
+            bf_blocks<I + 1>(r);
+        }
+    }
+
+    AC_DI void layer_bf(const char* wfront) {
+        const bf16x8* wf0 = reinterpret_cast<const bf16x8*>(wfront) + lane;
+        const bf16x8* wf1 = reinterpret_cast<const bf16x8*>(this->bf_back) + lane;
+        static_assert(WT % CH == 0 && (WT / 2) % CH == 0 && CH < KC, "a chunk of output tiles lies in one half");
+        static_assert((WT / 2) * KC * 3 * 1024 <= 65536, "a half-layer fits the ds_read immediate offset");
+        BfRegs r;
+        // LDS addresses of this lane's piece in the two halves (generic -> LDS pointer: the low 32 bits)
+        r.la0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf0;
+        r.la1 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf1;
+        r.bias4 = reinterpret_cast<const f32x4*>(wfront + kBfBack);
 #pragma unroll
-        for (int nt = 0; nt < WT; ++nt) epilogue_tile<WT, 1>(NSLAB - 1, nt, o[(NSLAB - 1) & 1], 1);
+        for (int i = 0; i < CH; ++i)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) r.w[0][i][p] = bf_frag(r, i, 0, p);
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+            u32x4 q[3];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) split_pair(0, c, i, q);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) r.xq[c][k] = q[k];
+        }
+        bf_blocks<0>(r);
+        __builtin_amdgcn_sched_barrier(0);
+        constexpr int L = (NSLAB - 1) & 1;
+#pragma unroll
+        for (int gi = 0; gi < NG; ++gi)
+#pragma unroll
+            for (int i = 0; i < CH; ++i)
+                if (sum_blk(gi) >= NB) r.o[L][gi * CH + i] = r.hi[L][gi * CH + i] + r.lo[L][gi * CH + i];
+#pragma unroll
+        for (int nt = 0; nt < WT; ++nt)
+            if (!epi_own(NSLAB - 1, nt)) epilogue_tile<WT, 1>(NSLAB - 1, nt, r.o[L], 1);
     }
 
     // First layer (5 -> width), tangent-aware: the value slab runs on the MFMA (one padded k-tile); the tangent
