@@ -17,6 +17,7 @@ STATUS_NAMES = {0: "AC_OK", -1: "AC_ERR_BAD_ARG", -2: "AC_ERR_HIP", -3: "AC_ERR_
                 -4: "AC_ERR_NO_MODEL", -5: "AC_ERR_NO_DEVICE", -6: "AC_ERR_WORKSPACE"}
 MODEL_KINDS = {"default": 0, "linear": 1, "nn": 2, "poly": 3, "quad": 4}
 VJP_ROUTES = {"auto": 0, "fused": 1, "composed": 2}   # ac_vjp_route
+HIDDEN_ROUTES = {"auto": 0, "bf16": 1, "f16": 2}      # ac_hidden_route
 VJP_STEP, VJP_ROLLOUT, VJP_DERIVATIVE = 0, 1, 2       # ac_vjp_which
 TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac_trim_f32 status per instance
 NUM_STATES = 13
@@ -131,6 +132,8 @@ PROTOTYPES = {
     "ac_rollout_policy_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _FP, C.c_int, C.c_float, C.c_long, C.c_long,
                                         _VP, _VP, _VP]),
     "ac_set_vjp_route": (C.c_int, [_VP, C.c_int]),
+    "ac_set_hidden_route": (C.c_int, [_VP, C.c_int]),
+    "ac_hidden_route_of": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ac_vjp_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_step_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_rollout_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),

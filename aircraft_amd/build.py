@@ -28,6 +28,9 @@ UNIT_FLAGS = {
     # the weight fragments in AGPRs (MlpEngine::ds_frag): ~530 -> ~170 AGPR<->VGPR moves per bf16 hidden layer.
     "nn_inst_wt8_mfma_sens": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],
     "nn_inst_wt8_mfma_pair": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],
+    # the same two kernels with the hidden layers on two-plane f16 MFMA (the route ac_set_mlp's gate picks; bf16 is the fall-back)
+    "nn_inst_wt8_f16_sens": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],
+    "nn_inst_wt8_f16_pair": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],
 }
 
 

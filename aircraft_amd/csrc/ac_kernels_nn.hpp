@@ -32,7 +32,9 @@ struct WaveUnit {
           unit(task_unit(tid, task) < n ? task_unit(tid, task) : n - 1), live(task_unit(tid, task) < n), ua(unit, blk) {}
 };
 
-template <int WT, bool USE_MFMA>
+// HID: how the hidden layers run (kHiddenFp32 / kHiddenBf16 / kHiddenF16, ac_mlp.hpp).  The default is the product form of the
+// (WT, USE_MFMA) pair; the two-plane f16 form is instantiated beside it for width 128 (nn_inst_wt8_f16_*.hip) and chosen per net.
+template <int WT, bool USE_MFMA, int HID = (USE_MFMA && WT == 8 ? kDefaultHidden : kHiddenFp32)>
 __global__ __launch_bounds__(kBlock, 1) void k_nn_step_sens(const DevParams P, const MlpPlan plan,
                                                             const float* __restrict__ blob,
                                                             const float* __restrict__ X, const float* __restrict__ U,
@@ -40,7 +42,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_nn_step_sens(const DevParams P, c
                                                             float* __restrict__ Xn, float* __restrict__ A,
                                                             float* __restrict__ Bm, float* __restrict__ c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef MlpEngine<6, WT, USE_MFMA, true, false, 0, 0, kBf16Hidden && USE_MFMA && WT == 8> Engine;  // (plan_bf when bf16)
+    typedef MlpEngine<6, WT, USE_MFMA, true, false, 0, 0, HID> Engine;  // (plan_bf when bf16, plan_f16 when f16)
     Engine eng(plan, blob, smem);
     eng.st.start();
     WaveClock wc;
@@ -204,7 +206,7 @@ AC_DI void sens_pair_body(const DevParams& P, const MlpPlan& plan, const float* 
     }
 }
 
-template <int WT>
+template <int WT, int HID = (WT == 8 ? kDefaultHidden : kHiddenFp32)>
 __global__ __launch_bounds__(kBlock, 1) void k_nn_step_sens_pair(const DevParams P, const MlpPlan plan,
                                                                  const float* __restrict__ blob,
                                                                  const float* __restrict__ X, const float* __restrict__ U,
@@ -217,10 +219,10 @@ __global__ __launch_bounds__(kBlock, 1) void k_nn_step_sens_pair(const DevParams
     // behind the plan's image: [2 pairs][WT KiB] value activations, then [2 pairs][16 units][36] outputs
     float* xch = reinterpret_cast<float*>(smem + plan.lds_total + 2 * WT * 1024) + pair * (16 * 36);
     if (role == 0)
-        sens_pair_body<MlpEngine<3, WT, true, true, false, 0, 1, kBf16Hidden && WT == 8>, 0>(P, plan, blob, smem, xch, true, X, U, dt, dt_per_unit, n,
+        sens_pair_body<MlpEngine<3, WT, true, true, false, 0, 1, HID>, 0>(P, plan, blob, smem, xch, true, X, U, dt, dt_per_unit, n,
                                                                       blk, unit0, pair, Xn, A, Bm, c);
     else
-        sens_pair_body<MlpEngine<3, WT, true, true, false, 2, 2, kBf16Hidden && WT == 8>, 2>(P, plan, blob, smem, xch, false, X, U, dt, dt_per_unit, n,
+        sens_pair_body<MlpEngine<3, WT, true, true, false, 2, 2, HID>, 2>(P, plan, blob, smem, xch, false, X, U, dt, dt_per_unit, n,
                                                                       blk, unit0, pair, Xn, A, Bm, c);
 }
 

@@ -48,6 +48,10 @@ constexpr bool kBf16Hidden = false;
 #else
 constexpr bool kBf16Hidden = true;
 #endif
+// How an engine runs its hidden layers: fp32 MFMA / vector ALUs (layer), three-plane bf16 MFMA or two-plane f16 MFMA (layer_bf).
+// The f16 form is a choice per NET (ac_set_mlp's range gate, ac_f16_pack.hpp); the bf16 kernels are its fall-back.
+constexpr int kHiddenFp32 = 0, kHiddenBf16 = 1, kHiddenF16 = 2;
+constexpr int kDefaultHidden = kBf16Hidden ? kHiddenBf16 : kHiddenFp32;
 
 // ---- 16x16x4 fp32 matrix-multiply-accumulate on one wave -------------------------------------
 // "MFMA off" validation path: the same contraction with cross-lane reads on the VALU.
@@ -130,8 +134,12 @@ template <> struct BfRingState<false> {};
 // (scale_from_hx).  Both roles meet at the same workgroup barriers: one at the head of every hidden layer, one after the second
 // slab of it (between the reader's load of h and the writer's next store), one before the last layer.
 template <int NSLAB, int WT, bool USE_MFMA, bool TANGENT = (NSLAB == 6), bool SECOND = false, int TOFF = 0, int PAIR = 0,
-          bool BF = false>
-struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
+          int HID = kHiddenFp32>
+struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHiddenFp32> {
+    static constexpr bool BF = HID != kHiddenFp32;   // hidden layers through layer_bf (plane operands, half-layer ring)
+    static constexpr bool F16 = HID == kHiddenF16;
+    static constexpr int NP = F16 ? 2 : 3;           // planes per operand
+    static constexpr int NPROD = F16 ? 3 : 6;        // plane products (MFMAs) per output tile and k-chunk
     using TripleHolder<SECOND && NSLAB <= 10>::tri;
     static constexpr bool kNoValue = PAIR == 2;  // every slab is a tangent slab
     static constexpr int kFirstTangent = kNoValue ? 0 : 1;  // slab index of tangent TOFF
@@ -431,7 +439,7 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     static constexpr int KC = WT / 2;  // 32-deep k-chunks
     static constexpr bool kPairRing = PAIR != 0;
-    static constexpr int kBfFront = (WT / 2) * KC * 3 * 1024 + 1024, kBfBack = (WT / 2) * KC * 3 * 1024;
+    static constexpr int kBfFront = (WT / 2) * KC * NP * 1024 + 1024, kBfBack = (WT / 2) * KC * NP * 1024;
 
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     AC_DI static unsigned cvt_pk_bf16(f32x2 xy) {
@@ -442,16 +450,47 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     // k-chunk c of slab s as the B operand: lane (col, g), element q = rows 4 g + q of tile 2c (q < 4) and 4 g + q - 4 of
     // tile 2c + 1 — the host permuted the weight columns to match (bf16_chunk_row) — in three planes q[0..2]; pair i =
     // elements 2 i, 2 i + 1 of the chunk (split_pair below; layer_bf runs it in stages, bf_stage)
-    AC_DI static f32x4 mfma_bf(const bf16x8& w, const bf16x8& x, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0);
+    // Two-plane f16 form (F16): hi = f16(x), lo' = f16((x - hi) S) with S = 2^11 — an f16 plane carries 11 significant bits,
+    // so two cover the fp32 significand to 2^-22 and THREE products replace six: lo' hi and hi lo' into `lo` (which then holds
+    // S times the small part), hi hi alone into `hi`, and the tile is hi + lo / S.  The dropped lo lo term is <= 2^-22 of a term.
+    // The scale keeps lo' out of f16's subnormal range wherever hi is out of it; the host gate (f16_gate, ac_f16_pack.hpp)
+    // keeps every operand under 2^15.  The bf16 form is the fall-back for nets the gate rejects.
+    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+    template <bool H, class A, class B> struct PickFrag { typedef A type; };
+    template <class A, class B> struct PickFrag<true, A, B> { typedef B type; };
+    typedef typename PickFrag<F16, bf16x8, f16x8>::type frag8;  // eight elements of one plane: an MFMA operand
+    static constexpr float kLoScale = 2048.0f, kLoInv = 1.0f / 2048.0f;
+    AC_DI static unsigned cvt_pk_f16(f32x2 xy) {
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+        return __builtin_bit_cast(unsigned, __builtin_convertvector(xy, f16x2));  // v_cvt_pk_f16_f32 (RNE)
+    }
+    // x - (the f16 in the low / high half of u), exact: the half is read as an operand, no conversion instruction
+    AC_DI static float sub_f16_lo(float x, unsigned u) {
+        float d;
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(u), "v"(x));
+        return d;
+    }
+    AC_DI static float sub_f16_hi(float x, unsigned u) {
+        float d;
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(u), "v"(x));
+        return d;
+    }
+    AC_DI static f32x4 mfma_bf(const frag8& w, const frag8& x, f32x4 c) {
+        if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, x, c, 0, 0, 0);
+        else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0);
+    }
+    // hi + lo of one accumulator element (f16: lo carries the scale S)
+    AC_DI static float bf_sum(float hi, float lo) {
+        if constexpr (F16) return fmaf(lo, kLoInv, hi);
+        else return hi + lo;
     }
     // One A fragment (16 B per lane) straight from LDS into accumulation registers: only the MFMA reads the weights, and in
     // the vector file they pushed the accumulators into AGPRs, which then cost a v_accvgpr_read per element for every
     // hi + lo sum and epilogue (~530 moves per layer call).  The waitcnt pass does not see this read: the caller waits
     // lgkmcnt(0) (wait_frags) before the first MFMA that uses it.  `lds_addr`: the LDS byte address of lane 0's piece + 16 lane.
     // `off` must fold to a constant (the fully unrolled loops of layer_bf): it is the instruction's 16-bit immediate offset.
-    AC_DI static bf16x8 ds_frag(unsigned lds_addr, int off) {
-        bf16x8 v;
+    AC_DI static frag8 ds_frag(unsigned lds_addr, int off) {
+        frag8 v;
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(v) : "v"(lds_addr), "i"(off));
         return v;
     }
@@ -493,7 +532,7 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     static constexpr int kTail = 2;           // groups walked k-chunk-outer (both in the back half: slab 0 waits where it did)
     static constexpr int kHead = (NG - kTail) * KC;  // blocks of the head groups
     static constexpr int NB = NG * KC;        // blocks per slab
-    static constexpr int NGAP = 6 * CH;       // MFMAs (gaps) per block
+    static constexpr int NGAP = NPROD * CH;   // MFMAs (gaps) per block
     static_assert(!BF || (kTail >= 2 && kTail < NG && NB % 2 == 0), "layer_bf walk");
     AC_DI static constexpr int blk_group(int b) { return b < kHead ? b / KC : NG - kTail + (b - kHead) % kTail; }
     AC_DI static constexpr int blk_chunk(int b) { return b < kHead ? b % KC : (b - kHead) / kTail; }
@@ -537,20 +576,26 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     }
 
     // pair i of k-chunk c of slab s in one piece (slab 0, in front of the first MFMA)
-    AC_DI void split_pair(int s, int c, int i, u32x4 (&q)[3]) const {
+    AC_DI void split_pair(int s, int c, int i, u32x4 (&q)[NP]) const {
         float x = a[s][2 * c + (i >> 1)][(2 * i) & 3], y = a[s][2 * c + (i >> 1)][(2 * i + 1) & 3];
+        if constexpr (F16) {
+            const unsigned h = cvt_pk_f16(f32x2{x, y});
+            q[0][i] = h;
+            q[1][i] = cvt_pk_f16(f32x2{sub_f16_lo(x, h) * kLoScale, sub_f16_hi(y, h) * kLoScale});
+            return;
+        }
         unsigned u = cvt_pk_bf16(x, y);
         q[0][i] = u;
         x -= __uint_as_float(u << 16); y -= __uint_as_float(u & 0xffff0000u);
         u = cvt_pk_bf16(x, y);
         q[1][i] = u;
         x -= __uint_as_float(u << 16); y -= __uint_as_float(u & 0xffff0000u);
-        q[2][i] = cvt_pk_bf16(x, y);
+        q[NP - 1][i] = cvt_pk_bf16(x, y);
     }
 
     // Work units of a block and their stages.  Unit u: [0, WT) hi + lo of tile u (2 stages); [WT, 2 WT) epilogue of tile u - WT
     // of the slab before (tangent: 4 stages, one element each; value: 12, three per element); [2 WT, 2 WT + 4 KC) pair
-    // (u - 2 WT) % 4 of the split of k-chunk (u - 2 WT) / 4 (6 stages).
+    // (u - 2 WT) % 4 of the split of k-chunk (u - 2 WT) / 4 (bf16: 6 stages; f16: 3).
     static constexpr int NU = 2 * WT + 4 * KC;
     // slab the unit works on when it runs in block B of slab S, or -1: not here
     AC_DI static constexpr int unit_slab(int S, int B, int u) {
@@ -573,19 +618,34 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
         return (pb == NB + B && S > 0) ? S : -1;
     }
     AC_DI static constexpr int unit_stages(int us, int u) {
-        return u < WT ? 2 : u < 2 * WT ? (!kNoValue && us == 0 ? 12 : 4) : 6;
+        return u < WT ? 2 : u < 2 * WT ? (!kNoValue && us == 0 ? 12 : 4) : (F16 ? 3 : 6);
     }
+    // Stages a gap takes before the next gap gets any: bf16 one (12 gaps to a block: its fullest block, a tanh tile, fills
+    // them one each).  f16 has the same units in the same blocks and half the gaps, so a block's stages are dealt level:
+    // ceil(stages of the block / gaps) to a gap.
+    AC_DI static constexpr int gap_share(int S, int B) {
+        if (!F16) return 1;
+        int t = 0;
+        for (int u = 0; u < NU; ++u) {
+            const int us = unit_slab(S, B, u);
+            if (us >= 0) t += unit_stages(us, u);
+        }
+        const int per = (t + NGAP - 1) / NGAP;
+        return per < 1 ? 1 : per;
+    }
+    static constexpr int kSumGap = F16 ? NGAP / 2 : 4;  // first gap of a block that may carry a hi + lo sum
     // n-th stage that runs in gap J of block B of slab S, as unit * 16 + stage; -1: none.  One stage after the other from gap 0,
     // the sums last
     AC_DI static constexpr int gap_stage(int S, int B, int J, int n) {
+        const int per = gap_share(S, B);
         int j = 0;
         for (int v = WT; v < NU + WT; ++v) {
             const int u = v % NU;  // epilogues, splits, then the sums
             const int us = unit_slab(S, B, u);
             if (us < 0) continue;
-            if (u < WT && j < 4) j = 4;
+            if (u < WT && j < kSumGap * per) j = kSumGap * per;
             for (int k = 0; k < unit_stages(us, u); ++k, ++j)
-                if ((j < NGAP ? j : NGAP - 1) == J && n-- == 0) return u * 16 + k;
+                if ((j / per < NGAP ? j / per : NGAP - 1) == J && n-- == 0) return u * 16 + k;
         }
         return -1;
     }
@@ -593,8 +653,8 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     // Registers of one layer_bf call (every index into them is a compile-time constant: they stay registers).
     struct BfRegs {
         f32x4 o[2][WT], hi[2][WT], lo[2][WT];  // ping-pong by slab parity: sums and epilogues of slab s - 1 run inside slab s
-        u32x4 xq[WT / 2][3];                   // the three planes of the KC k-chunks of the running slab
-        bf16x8 w[2][CH][3];                    // A fragments: the block running, the next one
+        u32x4 xq[WT / 2][NP];                  // the planes of the KC k-chunks of the running slab
+        frag8 w[2][CH][NP];                    // A fragments: the block running, the next one
         unsigned la0, la1;                     // LDS byte addresses of this lane's piece in the two halves
         const f32x4* bias4;
         f32x2 sxy[2 * WT]; float tt[WT][4];    // between the stages of a split pair / of a tanh
@@ -613,7 +673,7 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
         if constexpr (U < WT) {
 #pragma unroll
             for (int e = 2 * K; e < 2 * K + 2; ++e) {
-                float v = r.hi[us & 1][U][e] + r.lo[us & 1][U][e];
+                float v = bf_sum(r.hi[us & 1][U][e], r.lo[us & 1][U][e]);
                 bf_pin(v);
                 r.o[us & 1][U][e] = v;
             }
@@ -635,7 +695,24 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
             }
         } else {
             constexpr int p = U - 2 * WT, c = p / 4, i = p % 4;
-            if constexpr (K == 0) {
+            if constexpr (F16) {
+                // split_pair()'s f16 form in three stages of two instructions
+                if constexpr (K == 0) {
+                    r.sxy[p] = f32x2{a[us][2 * c + (i >> 1)][(2 * i) & 3], a[us][2 * c + (i >> 1)][(2 * i + 1) & 3]};
+                    r.su[p] = cvt_pk_f16(r.sxy[p]);
+                    r.xq[c][0][i] = r.su[p];
+                    float x = sub_f16_lo(r.sxy[p][0], r.su[p]);
+                    bf_pin(x);
+                    r.sxy[p][0] = x;
+                } else if constexpr (K == 1) {
+                    float y = sub_f16_hi(r.sxy[p][1], r.su[p]), x = r.sxy[p][0] * kLoScale;
+                    bf_pin(x); bf_pin(y);
+                    r.sxy[p] = f32x2{x, y};
+                } else {
+                    r.sxy[p][1] *= kLoScale;
+                    r.xq[c][1][i] = cvt_pk_f16(r.sxy[p]);
+                }
+            } else if constexpr (K == 0) {
                 r.sxy[p] = f32x2{a[us][2 * c + (i >> 1)][(2 * i) & 3], a[us][2 * c + (i >> 1)][(2 * i + 1) & 3]};
                 r.su[p] = cvt_pk_bf16(r.sxy[p]);
                 r.xq[c][0][i] = r.su[p];
@@ -665,26 +742,34 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
         }
     }
 
-    AC_DI bf16x8 bf_frag(const BfRegs& r, int nt, int c, int p) const {
-        return ds_frag(nt < WT / 2 ? r.la0 : r.la1, (((nt % (WT / 2)) * KC + c) * 3 + p) * 1024);
+    AC_DI frag8 bf_frag(const BfRegs& r, int nt, int c, int p) const {
+        return ds_frag(nt < WT / 2 ? r.la0 : r.la1, (((nt % (WT / 2)) * KC + c) * NP + p) * 1024);
+    }
+    // stages n, n + 1, ... of gap J (bf16: at most two)
+    template <int S, int B, int J, int N> AC_DI void bf_gap_stages(BfRegs& r) {
+        constexpr int e = gap_stage(S, B, J, N);
+        if constexpr (e >= 0) {
+            bf_stage<S, B, e / 16, e % 16>(r);
+            bf_gap_stages<S, B, J, N + 1>(r);
+        }
     }
 
     // MFMA J of block B of slab S and what its gap carries: one fragment read of the next block behind each of the first
-    // 3 CH MFMAs, and the gap's stages.  Products in the order (3,1), (1,3), (2,2), (2,1), (1,2) into lo, then (1,1) into hi.
+    // NP CH MFMAs, and the gap's stages.  Products in the order (3,1), (1,3), (2,2), (2,1), (1,2) into lo, then (1,1) into hi;
+    // f16: (lo', hi), (hi, lo') into lo, then (hi, hi) into hi.
     template <int S, int B, int J> AC_DI void bf_gap(BfRegs& r) {
         constexpr int nc = blk_group(B) * CH, c = blk_chunk(B), cur = B & 1, i = J % CH, m = J / CH;
         constexpr bool more = !(S + 1 == NSLAB && B + 1 == NB);
         constexpr int nb = (B + 1) % NB, nnc = blk_group(nb) * CH, nkc = blk_chunk(nb);
-        constexpr int wp = m == 0 ? 2 : (m == 1 || m == 4 || m == 5) ? 0 : 1, xp = m == 1 ? 2 : (m == 2 || m == 4) ? 1 : 0;
-        const bf16x8 x = __builtin_bit_cast(bf16x8, r.xq[c][xp]);
-        if constexpr (m < 5) r.lo[S & 1][nc + i] = mfma_bf(r.w[cur][i][wp], x, r.lo[S & 1][nc + i]);
+        constexpr int wp = F16 ? (m == 0 ? 1 : 0) : m == 0 ? 2 : (m == 1 || m == 4 || m == 5) ? 0 : 1;
+        constexpr int xp = F16 ? (m == 1 ? 1 : 0) : m == 1 ? 2 : (m == 2 || m == 4) ? 1 : 0;
+        const frag8 x = __builtin_bit_cast(frag8, r.xq[c][xp]);
+        if constexpr (m < NPROD - 1) r.lo[S & 1][nc + i] = mfma_bf(r.w[cur][i][wp], x, r.lo[S & 1][nc + i]);
         else r.hi[S & 1][nc + i] = mfma_bf(r.w[cur][i][wp], x, r.hi[S & 1][nc + i]);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (more && J < 3 * CH) r.w[cur ^ 1][J / 3][J % 3] = bf_frag(r, nnc + J / 3, nkc, J % 3);
-        constexpr int e0 = gap_stage(S, B, J, 0), e1 = gap_stage(S, B, J, 1);
-        static_assert(gap_stage(S, B, J, 2) < 0, "at most two stages to a gap");
-        if constexpr (e0 >= 0) bf_stage<S, B, e0 / 16, e0 % 16>(r);
-        if constexpr (e1 >= 0) bf_stage<S, B, e1 / 16, e1 % 16>(r);
+        if constexpr (more && J < NP * CH) r.w[cur ^ 1][J / NP][J % NP] = bf_frag(r, nnc + J / NP, nkc, J % NP);
+        static_assert(F16 || gap_stage(S, B, J, 2) < 0, "at most two stages to a gap");
+        bf_gap_stages<S, B, J, 0>(r);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (J + 1 < NGAP) bf_gap<S, B, J + 1>(r);
     }
@@ -726,10 +811,10 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
     }
 
     AC_DI void layer_bf(const char* wfront) {
-        const bf16x8* wf0 = reinterpret_cast<const bf16x8*>(wfront) + lane;
-        const bf16x8* wf1 = reinterpret_cast<const bf16x8*>(this->bf_back) + lane;
+        const frag8* wf0 = reinterpret_cast<const frag8*>(wfront) + lane;
+        const frag8* wf1 = reinterpret_cast<const frag8*>(this->bf_back) + lane;
         static_assert(WT % CH == 0 && (WT / 2) % CH == 0 && CH < KC, "a chunk of output tiles lies in one half");
-        static_assert((WT / 2) * KC * 3 * 1024 <= 65536, "a half-layer fits the ds_read immediate offset");
+        static_assert((WT / 2) * KC * NP * 1024 <= 65536, "a half-layer fits the ds_read immediate offset");
         BfRegs r;
         // LDS addresses of this lane's piece in the two halves (generic -> LDS pointer: the low 32 bits)
         r.la0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf0;
@@ -738,14 +823,14 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
 #pragma unroll
         for (int i = 0; i < CH; ++i)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) r.w[0][i][p] = bf_frag(r, i, 0, p);
+            for (int p = 0; p < NP; ++p) r.w[0][i][p] = bf_frag(r, i, 0, p);
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
-            u32x4 q[3];
+            u32x4 q[NP];
 #pragma unroll
             for (int i = 0; i < 4; ++i) split_pair(0, c, i, q);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) r.xq[c][k] = q[k];
+            for (int k = 0; k < NP; ++k) r.xq[c][k] = q[k];
         }
         bf_blocks<0>(r);
         __builtin_amdgcn_sched_barrier(0);
@@ -754,7 +839,14 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<BF> {
         for (int gi = 0; gi < NG; ++gi)
 #pragma unroll
             for (int i = 0; i < CH; ++i)
-                if (sum_blk(gi) >= NB) r.o[L][gi * CH + i] = r.hi[L][gi * CH + i] + r.lo[L][gi * CH + i];
+                if (sum_blk(gi) >= NB) {
+                    if constexpr (F16) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) r.o[L][gi * CH + i][e] = bf_sum(r.hi[L][gi * CH + i][e], r.lo[L][gi * CH + i][e]);
+                    } else {
+                        r.o[L][gi * CH + i] = r.hi[L][gi * CH + i] + r.lo[L][gi * CH + i];
+                    }
+                }
 #pragma unroll
         for (int nt = 0; nt < WT; ++nt)
             if (!epi_own(NSLAB - 1, nt)) epilogue_tile<WT, 1>(NSLAB - 1, nt, r.o[L], 1);

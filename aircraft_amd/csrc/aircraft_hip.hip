@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ac_bf16_pack.hpp"
+#include "ac_f16_pack.hpp"
 #include "ac_kernels_analytic.hpp"
 #include "ac_nn_decl.hpp"
 #include "ac_ilqr.hpp"
@@ -82,6 +83,10 @@ struct ac_handle {
     MlpPlan plan_bf;       // width 128 (wt 8), matrix cores: plan_sens with the hidden layers as three-plane bf16 images streamed
     MlpPlan plan_bf_pair;  // in half-layer regions — three rotating (k_nn_step_sens), two (k_nn_step_sens_pair); ac_set_mlp
     bool has_bf;
+    MlpPlan plan_f16;       // the same two plans over the two-plane f16 images (ac_f16_pack.hpp): the route of a net that
+    MlpPlan plan_f16_pair;  // passes the range gate (f16_gate); plan_bf / plan_bf_pair stay its fall-back
+    int f16_gate;           // F16Gate code of the net (0: passes); meaningful when has_bf
+    int hidden_route;       // ac_hidden_route (ac_set_hidden_route); 0 = AC_HIDDEN_AUTO
     bool has_rev;       // reverse sweep of k_nn_stage_tensors_rev (ac_hess_rev.hpp); rev_layers = layers of the net itself
     int rev_layers;
     float* d_rev_scratch;  // per-wave layer states of that kernel (ac_reserve_hess_workspace)
@@ -138,6 +143,17 @@ int model_ready(const ac_handle* h) {
 
 // Raise a kernel's dynamic-LDS limit once per (handle, kernel, size): the attribute is sticky per device, and the call
 // costs a driver round trip that does not belong in front of every launch.
+// why AC_HIDDEN_F16 cannot run on this handle's net
+const char* hidden_f16_refusal(const ac_handle* h) {
+    if (!(kBf16Hidden && h->use_mfma && h->wt == 8 && h->has_bf)) return "hidden route f16: only the width-128 matrix-core sensitivity kernels have an f16 form";
+    switch (h->f16_gate) {
+        case F16_GATE_WEIGHT: return "hidden route f16: a hidden-layer weight is outside the gate's range (|w| >= 2^15)";
+        case F16_GATE_TANGENT_BOUND: return "hidden route f16: the bound of the hidden-layer tangents reaches 2^15";
+        case F16_GATE_TANGENT_TINY: return "hidden route f16: the tangents entering a hidden layer are below 2^-14 (f16 subnormal range)";
+        default: return "hidden route f16: the net has non-finite weights";
+    }
+}
+
 template <class K> int set_lds_limit(ac_handle* h, K kernel, int bytes) {
     if (bytes <= 64 * 1024) return AC_OK;
     const void* fn = reinterpret_cast<const void*>(kernel);
@@ -280,6 +296,10 @@ int ac_create(const ac_params* params, ac_handle** out) {
         h->no_pair = e && e[0] == '1';
         const char* ea = getenv("AIRCRAFT_HIP_ALL_PAIR");
         h->all_pair = ea && ea[0] == '1';
+        // AIRCRAFT_HIP_HIDDEN_ROUTE=bf16|f16: the handle's initial hidden-layer route (ac_set_hidden_route overrides it)
+        const char* er = getenv("AIRCRAFT_HIP_HIDDEN_ROUTE");
+        if (er && !strcmp(er, "bf16")) h->hidden_route = AC_HIDDEN_BF16;
+        if (er && !strcmp(er, "f16")) h->hidden_route = AC_HIDDEN_F16;
     }
 #endif
 #if defined(AC_STAMPS) || defined(AC_CLOCKS)
@@ -427,14 +447,26 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
         for (int i = 0; i < n_hid; ++i) { rev_off[i] = total_floats; total_floats += rev_block_floats; }
     // Width 128 with hidden layers: their three-plane bf16 images (ac_bf16_pack.hpp) for the sensitivity kernels' layer_bf.
     const bool want_bf = wt == 8 && n_hid >= 1;
-    size_t bf_off[AC_MAX_LAYERS] = {0};
+    size_t bf_off[AC_MAX_LAYERS] = {0}, f16_off[AC_MAX_LAYERS] = {0};
     if (want_bf)
         for (int l = 1; l < n_layers - 1; ++l) { bf_off[l] = total_floats; total_floats += (size_t)bf16_layer_bytes(wt) / 4; }
+    // ... and their two-plane f16 images (ac_f16_pack.hpp) behind those: which of the two the kernels read is decided per net
+    // by the range gate below (and ac_set_hidden_route)
+    if (want_bf)
+        for (int l = 1; l < n_layers - 1; ++l) { f16_off[l] = total_floats; total_floats += (size_t)f16_layer_bytes(wt) / 4; }
     // Pack: [nt][kt][lane][4] with lane = col + 16 g -> W[16 nt + col][16 kt + 4 g + j]; then the padded bias.
     std::vector<float> blob(total_floats, 0.f);
     if (want_bf)
         for (int l = 1; l < n_layers - 1; ++l)
             bf16_pack_layer(fW[(size_t)l].data(), fb[(size_t)l].data(), widths[l], widths[l + 1], wt, blob.data() + bf_off[l]);
+    int gate = F16_GATE_OK;
+    if (want_bf) {
+        for (int l = 1; l < n_layers - 1; ++l)
+            f16_pack_layer(fW[(size_t)l].data(), fb[(size_t)l].data(), widths[l], widths[l + 1], wt, blob.data() + f16_off[l]);
+        std::vector<const float*> gw((size_t)n_layers), gb((size_t)n_layers);
+        for (int l = 0; l < n_layers; ++l) { gw[(size_t)l] = fW[(size_t)l].data(); gb[(size_t)l] = fb[(size_t)l].data(); }
+        gate = f16_gate(n_layers, widths, gw.data(), gb.data());
+    }
     if (want_rev)
         for (int i = 0; i < n_hid; ++i) {
             const int l = n_hid - i;  // forward layer l: h_l (nin) -> h_{l+1} (nout); the block multiplies by its transpose
@@ -551,6 +583,17 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
         pbp.bf_region[2] = -1;
         if (pb.lds_total > kLdsBudget) return fail(AC_ERR_UNSUPPORTED, "bf16 hidden-layer ring does not fit the LDS");
     }
+    // plan_f16 / plan_f16_pair: the same rings over the f16 images (two planes: regions of 33 KiB instead of 49)
+    MlpPlan pf = pb, pfp = pbp;
+    if (want_bf) {
+        const int edge = pb.bf_region[0], region = f16_front_bytes(wt);
+        for (int l = 1; l < n_layers - 1; ++l) { pf.g_off[l] = (int)f16_off[l]; pf.bytes[l] = f16_layer_bytes(wt); }
+        for (int i = 0; i < 3; ++i) pf.bf_region[i] = edge + i * region;
+        pfp = pf;
+        pf.lds_total = edge + 3 * region;
+        pfp.lds_total = edge + 2 * region;
+        pfp.bf_region[2] = -1;
+    }
     MlpPlan pr = ps;
     bool rev_ok = false;
     if (want_rev) {
@@ -626,6 +669,9 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
     h->plan_bf = pb;
     h->plan_bf_pair = pbp;
     h->has_bf = want_bf;
+    h->plan_f16 = pf;
+    h->plan_f16_pair = pfp;
+    h->f16_gate = gate;
     h->has_rev = rev_ok;
     h->rev_layers = n_layers;
     h->wt = wt;
@@ -982,7 +1028,12 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
         }
         // width 128 on the matrix cores: the hidden layers on bf16 MFMA (plan_bf; -DAC_HIDDEN_FP32: plan_sens, as round 4)
         const bool bf = kBf16Hidden && h->use_mfma && h->wt == 8 && h->has_bf;
-        const MlpPlan& plan_main = bf ? h->plan_bf : h->plan_sens;
+        // ... and on two-plane f16 MFMA where the net passed the range gate (ac_set_mlp); the bf16 kernels are the fall-back.
+        // AC_HIDDEN_F16 forced on a net the gate rejects (or on one without such kernels) is an error, never a fall-back.
+        const bool f16_ok = bf && h->f16_gate == F16_GATE_OK;
+        if (h->hidden_route == AC_HIDDEN_F16 && !f16_ok) return fail(AC_ERR_UNSUPPORTED, hidden_f16_refusal(h));
+        const bool f16 = f16_ok && h->hidden_route != AC_HIDDEN_BF16;
+        const MlpPlan& plan_main = f16 ? h->plan_f16 : bf ? h->plan_bf : h->plan_sens;
         if (h->use_mfma && h->wt == 2 && h->dp.p.substeps <= 1) {
             // small nets: two persistent workgroups per CU = two waves per SIMD (k_nn_step_sens_w2)
             const int lds = ((h->plan_sens.lds_total + 15) & ~15) + kSensW2AccBytes;
@@ -1007,7 +1058,8 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
             bool launched = false;
             AC_NN_CASE_SENS(2, true, (k_nn_step_sens<2, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
             AC_NN_CASE_SENS(4, true, (k_nn_step_sens<4, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
-            AC_NN_CASE_PLAN(plan_main, 8, true, (k_nn_step_sens<8, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
+            if (f16) { AC_NN_CASE_PLAN(plan_main, 8, true, (k_nn_step_sens<8, true, kHiddenF16>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c) }
+            else { AC_NN_CASE_PLAN(plan_main, 8, true, (k_nn_step_sens<8, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c) }
             AC_NN_CASE_SENS(2, false, (k_nn_step_sens<2, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
             AC_NN_CASE_SENS(4, false, (k_nn_step_sens<4, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
             AC_NN_CASE_SENS(8, false, (k_nn_step_sens<8, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
@@ -1017,7 +1069,7 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
         }
         if (n_pair > 0) {
             const int grid_p = (int)((n_pair + 31) / 32);
-            const MlpPlan& plan_p = bf ? h->plan_bf_pair : h->plan_sens;
+            const MlpPlan& plan_p = f16 ? h->plan_f16_pair : bf ? h->plan_bf_pair : h->plan_sens;
             const int lds_p = plan_p.lds_total + 2 * h->wt * 1024 + 2 * 16 * 36 * (int)sizeof(float);  // + the pairs' activation and output exchanges
             bool launched = false;
 #define AC_PAIR_CASE(WT_)                                                                                              \
@@ -1029,7 +1081,16 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
                                    blk, Xn, A, Bm, c, n_main);                                                          \
                 launched = true;                                                                                       \
             }
-            AC_PAIR_CASE(2) AC_PAIR_CASE(4) AC_PAIR_CASE(8)
+            if (f16) {
+                auto kern = k_nn_step_sens_pair<8, kHiddenF16>;
+                int rc_ = set_lds_limit(h, kern, lds_p);
+                if (rc_ != AC_OK) return rc_;
+                hipLaunchKernelGGL(kern, grid_p, kBlock, lds_p, st, h->dp, plan_p, h->d_blob, X, U, dt, dt_per_unit, n,
+                                   blk, Xn, A, Bm, c, n_main);
+                launched = true;
+            } else {
+                AC_PAIR_CASE(2) AC_PAIR_CASE(4) AC_PAIR_CASE(8)
+            }
 #undef AC_PAIR_CASE
             if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
             if (n_main == 0) note_launch(h, "k_nn_step_sens_pair", grid_p, kBlock, lds_p);
@@ -2019,6 +2080,25 @@ int ac_trim_f32(ac_handle* h, const ac_trim_opts* o, const float* target, const 
         AC_HIP(hipGetLastError());
     }
     note_launch(h, "k_trim_update", grid, kTrimBlock, 0);
+    return AC_OK;
+}
+
+int ac_set_hidden_route(ac_handle* h, int route) {
+    if (!h || route < AC_HIDDEN_AUTO || route > AC_HIDDEN_F16) return AC_ERR_BAD_ARG;
+    if (route == AC_HIDDEN_F16 && h->has_mlp) {
+        const bool ok = kBf16Hidden && h->use_mfma && h->wt == 8 && h->has_bf && h->f16_gate == F16_GATE_OK;
+        if (!ok) return fail(AC_ERR_UNSUPPORTED, hidden_f16_refusal(h));
+    }
+    h->hidden_route = route;
+    return AC_OK;
+}
+
+int ac_hidden_route_of(const ac_handle* h, int* route, int* gate) {
+    if (!h || !h->has_mlp) return AC_ERR_BAD_ARG;
+    const bool bf = kBf16Hidden && h->use_mfma && h->wt == 8 && h->has_bf;
+    const bool f16 = bf && h->f16_gate == F16_GATE_OK && h->hidden_route != AC_HIDDEN_BF16;
+    if (route) *route = f16 ? AC_HIDDEN_F16 : bf ? AC_HIDDEN_BF16 : AC_HIDDEN_AUTO;
+    if (gate) *gate = bf ? h->f16_gate : -1;
     return AC_OK;
 }
 

@@ -104,6 +104,10 @@ class SixDOF(ABC):
         self.mass = opts.mass
         self.normalise = False  # controllers flip this (control/base.py:182-185)
         self.vjp_route = "auto"  # reverse mode: "auto" (fused where a fused kernel exists), "fused" or "composed"
+        # hidden layers of the width-128 sensitivity kernels: "auto" (two-plane f16 MFMA where the net passes the range gate,
+        # else three-plane bf16), "bf16" or "f16" (an error on a net the gate rejects); ac_set_hidden_route
+        self.hidden_route = "auto"
+        self._installed_route = "auto"
         self.physical_integration_substeps: int = opts.physical_integration_substeps
         self.stall_scaling = False
         self._handle = C.c_void_p()
@@ -144,6 +148,11 @@ class SixDOF(ABC):
         elif key != self._installed_key:
             _lib.check(lib.ac_set_params(self._handle, C.byref(p)), "ac_set_params")
             self._installed_key = key
+        if self.hidden_route != self._installed_route:
+            if self.hidden_route not in _lib.HIDDEN_ROUTES:
+                raise ValueError(f"hidden_route: expected one of {sorted(_lib.HIDDEN_ROUTES)}, got {self.hidden_route!r}")
+            _lib.check(lib.ac_set_hidden_route(self._handle, _lib.HIDDEN_ROUTES[self.hidden_route]), "ac_set_hidden_route")
+            self._installed_route = self.hidden_route
         return lib
 
     def close(self):
@@ -156,6 +165,7 @@ class SixDOF(ABC):
             # the workspaces died with the handle: a re-created one must be reserved again
             self._hess_reserved = 0
             self._installed_key = None
+            self._installed_route = "auto"
         _drain_parked()
 
     def __del__(self):
@@ -539,6 +549,14 @@ class SixDOF(ABC):
     phi = property(lambda self: self._getter("phi", 19))
     theta = property(lambda self: self._getter("theta", 20))
     psi = property(lambda self: self._getter("psi", 21))
+
+    def hidden_route_in_use(self):
+        """(route, gate) of the handle's net: route "f16" / "bf16" for the width-128 matrix-core sensitivity kernels ("auto":
+        the net has none), gate = the range gate's verdict (0 passes, see ac_hidden_route_of; -1 no such kernels)."""
+        lib = self._sync()
+        r, g = C.c_int(), C.c_int()
+        _lib.check(lib.ac_hidden_route_of(self._handle, C.byref(r), C.byref(g)), "ac_hidden_route_of")
+        return {v: k for k, v in _lib.HIDDEN_ROUTES.items()}[r.value], g.value
 
     def last_launch(self):
         """(kernel name, grid, block, dynamic LDS bytes) of the most recent dispatch."""

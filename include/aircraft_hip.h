@@ -462,6 +462,18 @@ int ac_device_arch(char* buf, size_t len);  /* gcnArchName of the current device
 /* Device pointer and size (floats) of the handle's second-order workspace (tests poison it with NaNs to prove that every
  * element a second-order call reads was written by that call). */
 int ac_hess_workspace(const ac_handle* h, float** ptr, size_t* floats);
+/* Hidden layers of the width-128 matrix-core sensitivity kernels (k_nn_step_sens<8>, k_nn_step_sens_pair<8>):
+ *   AC_HIDDEN_F16   two-plane f16 MFMA, three products per fp32 product — for nets that pass the range gate of ac_set_mlp
+ *                   (every operand of the hidden layers provably under 2^15, tangents not uniformly under 2^-14)
+ *   AC_HIDDEN_BF16  three-plane bf16 MFMA, six products: any finite net; the fall-back of the gate
+ *   AC_HIDDEN_AUTO  f16 where the gate passes, else bf16 (the default)
+ * AC_HIDDEN_F16 on a net the gate rejects is AC_ERR_UNSUPPORTED — from this call if the net is already set, else from the
+ * compute calls — never a silent fall-back.  Other kernels and other nets are not affected by the setting.
+ * ac_hidden_route_of: the route the handle's net takes now (AC_HIDDEN_AUTO: it has no such kernels) and the gate's verdict
+ * (0 passes; 1 a weight >= 2^15, 2 tangent bound >= 2^15, 3 tangents under 2^-14, 4 non-finite; -1 no such kernels). */
+typedef enum ac_hidden_route { AC_HIDDEN_AUTO = 0, AC_HIDDEN_BF16 = 1, AC_HIDDEN_F16 = 2 } ac_hidden_route;
+int ac_set_hidden_route(ac_handle* h, int route);
+int ac_hidden_route_of(const ac_handle* h, int* route, int* gate);
 /* Name + launch geometry of the kernel the last call on this handle dispatched (for profiling). */
 int ac_last_launch(const ac_handle* h, char* name, size_t len, int* grid, int* block, int* lds_bytes);
 

@@ -11,6 +11,8 @@ role bodies of the pair kernel) are left out of the sums and counted.
     python tools/mfma_gaps.py                    # both headline units
     python tools/mfma_gaps.py UNIT [UNIT ...]    # named units
     python tools/mfma_gaps.py --asm FILE.s       # an assembly file made elsewhere
+    python tools/mfma_gaps.py --f16              # the two units of the two-plane f16 form (v_mfma_f32_16x16x32_f16)
+    python tools/mfma_gaps.py --mfma MNEMONIC UNIT [UNIT ...]
 
 analyse() is what tests/test_headline_issue_budget.py asserts on."""
 import collections
@@ -25,12 +27,16 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 MFMA = "v_mfma_f32_16x16x32_bf16"
+MFMA_F16 = "v_mfma_f32_16x16x32_f16"
 HEADLINE_UNITS = ("nn_inst_wt8_mfma_sens", "nn_inst_wt8_mfma_pair")
+F16_UNITS = ("nn_inst_wt8_f16_sens", "nn_inst_wt8_f16_pair")
 TRANS = ("v_exp", "v_log", "v_rcp", "v_rsq", "v_sqrt", "v_sin", "v_cos")
 MFMA_CYCLES = 16   # one v_mfma_f32_16x16x32_bf16 on the matrix pipe
 MFMA_ISSUE = 8     # of which the SIMD's vector issue is held
 BLOCK = 12         # MFMAs of one block of layer_bf (two output tiles x six plane products of one k-chunk)
 SLAB = 192         # MFMAs of one slab (eight output tiles x four k-chunks x six)
+# the f16 form: three plane products instead of six (same cycles per MFMA)
+SHAPES = {MFMA: (BLOCK, SLAB), MFMA_F16: (BLOCK // 2, SLAB // 2)}
 
 
 def cost(ins):
@@ -79,25 +85,27 @@ def basic_blocks(asm):
     return blocks
 
 
-def instructions(asm):
+def instructions(asm, mfma=MFMA):
     """The instruction stream in the order one trip of each loop executes it: the block placement pass may rotate a loop
     (header in the middle of its text, e.g. the hidden-layer loop cut at the mid-layer barrier), which would put the
     seam between two layer calls inside the region and shift every block and slab sum."""
     blocks = basic_blocks(asm)
     # loops whose own blocks issue the MFMAs: first .. last block of the loop in the text (child loops lie inside)
-    for h in sorted({b[1] for b in blocks if b[1] and any(i.startswith(MFMA) for i in b[2])}):
+    for h in sorted({b[1] for b in blocks if b[1] and any(i.startswith(mfma) for i in b[2])}):
         own = [k for k, b in enumerate(blocks) if b[1] == h]
         head = next((k for k in own if blocks[k][0] == h), own[0])
         blocks[own[0]:own[-1] + 1] = blocks[head:own[-1] + 1] + blocks[own[0]:head]
     return [i for b in blocks for i in b[2]]
 
 
-def analyse(asm):
-    """Figures of the region between the first and the last bf16 MFMA of an assembly text."""
-    ins = instructions(asm)
-    idx = [k for k, i in enumerate(ins) if i.startswith(MFMA)]
+def analyse(asm, mfma=MFMA):
+    """Figures of the region between the first and the last MFMA (`mfma`: its mnemonic, the bf16 form by default) of an
+    assembly text."""
+    block, slab = SHAPES.get(mfma, (BLOCK, SLAB))
+    ins = instructions(asm, mfma)
+    idx = [k for k, i in enumerate(ins) if i.startswith(mfma)]
     if len(idx) < 2:
-        raise ValueError("no bf16 MFMA region")
+        raise ValueError(f"no {mfma} region")
     gaps, kinds = [], collections.Counter()
     for a, b in zip(idx, idx[1:]):
         seg = ins[a + 1:b]
@@ -114,8 +122,8 @@ def analyse(asm):
     modelled = sum(max(MFMA_CYCLES, MFMA_ISSUE + g) for g in priced)
     floor = MFMA_CYCLES * len(priced)
     slabs = []
-    for s in range(0, len(filled), SLAB):
-        seg = filled[s:s + SLAB]
+    for s in range(0, len(filled), slab):
+        seg = filled[s:s + slab]
         slabs.append({"filler": sum(seg), "modelled": sum(max(MFMA_CYCLES, MFMA_ISSUE + g) for g in seg),
                       "floor": MFMA_CYCLES * len(seg)})
     return {
@@ -134,7 +142,8 @@ def analyse(asm):
         "floor": floor,
         "ratio": modelled / floor,
         "hist": dict(sorted(hist.items())),
-        "blocks": [sum(filled[k:k + BLOCK]) for k in range(0, len(filled), BLOCK)],
+        "blocks": [sum(filled[k:k + block]) for k in range(0, len(filled), block)],
+        "block": block,
         "slabs": slabs,
         "kinds": kinds.most_common(25),
         "acc_moves": sum(n for k, n in kinds.items() if k.startswith("v_accvgpr_")),
@@ -144,7 +153,7 @@ def analyse(asm):
 def report(name, r):
     p = print
     p(f"== {name}")
-    p(f"bf16 MFMAs {r['mfma']}; gaps {r['gaps']} ({r['excluded']} with a barrier or a branch left out)")
+    p(f"MFMAs {r['mfma']}; gaps {r['gaps']} ({r['excluded']} with a barrier or a branch left out)")
     p(f"gaps with no vector work {r['empty']}; carrying >= 40 cycles {r['ge40']}; above 32 cycles {r['gt32']} "
       f"({100 * r['gt32_share']:.1f} %)")
     p(f"filler {r['filler']} cycles ({4 * r['ds_read_b128']} of them ds_read_b128); free capacity (8 x gaps) {r['capacity']}; "
@@ -155,7 +164,7 @@ def report(name, r):
     p("filler per slab:   " + " ".join(str(s["filler"]) for s in r["slabs"]))
     p("histogram (filler cycles per gap, buckets of 8, last bucket open: gaps):")
     p("  " + "  ".join(f"{k}:{v}" for k, v in r["hist"].items()))
-    p(f"filler per {BLOCK}-MFMA block:")
+    p(f"filler per {r['block']}-MFMA block:")
     b = r["blocks"]
     for k in range(0, len(b), 16):
         p("  " + " ".join(f"{x:4d}" for x in b[k:k + 16]))
@@ -165,14 +174,19 @@ def report(name, r):
 
 
 def main(argv):
+    mfma, units = MFMA, HEADLINE_UNITS
+    if argv and argv[0] == "--f16":
+        mfma, units, argv = MFMA_F16, F16_UNITS, argv[1:]
+    elif len(argv) > 1 and argv[0] == "--mfma":
+        mfma, argv = argv[1], argv[2:]
     if argv and argv[0] == "--asm":
         for f in argv[1:]:
             with open(f) as fh:
-                report(f, analyse(fh.read()))
+                report(f, analyse(fh.read(), mfma))
         return
     with tempfile.TemporaryDirectory() as tmp:
-        for unit in argv or HEADLINE_UNITS:
-            report(unit, analyse(compile_unit(unit, tmp)))
+        for unit in argv or units:
+            report(unit, analyse(compile_unit(unit, tmp), mfma))
 
 
 if __name__ == "__main__":
