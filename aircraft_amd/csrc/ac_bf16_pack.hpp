@@ -1,5 +1,5 @@
 // ac_bf16_pack.hpp — host-side image of a hidden (width x width) layer for the bf16 matrix-core path of the
-// sensitivity engines (MlpEngine::layer_bf).  Plain C++: ac_set_mlp packs with it, and the CPU test
+// sensitivity engines (MlpEngine::layer_bf).  Plain C++: build_mlp_model (ac_mlp_model.hpp) packs with it, and the CPU test
 // (tests/test_mlp_bf16_planes.py) compiles it with g++ to check the split and the packing.
 //
 // Three-plane split: w1 = bf16(w), w2 = bf16(w - w1), w3 = bf16(w - w1 - w2), each rounded to nearest even.  Every
@@ -43,32 +43,42 @@ inline int bf16_chunk_row(int c, int kk) {
     const int g = kk >> 3, q = kk & 7;
     return 32 * c + ((q & 4) ? 16 : 0) + 4 * g + (q & 3);
 }
-inline int bf16_front_bytes(int wt) { return (wt / 2) * (wt / 2) * 3 * 1024 + 1024; }
-inline int bf16_back_bytes(int wt) { return (wt / 2) * (wt / 2) * 3 * 1024; }
-inline int bf16_layer_bytes(int wt) { return bf16_front_bytes(wt) + bf16_back_bytes(wt); }
+// Geometry and packing of a plane image, shared by the bf16 form (three planes) and the f16 form (two, ac_f16_pack.hpp).
+inline int plane_front_bytes(int wt, int planes) { return (wt / 2) * (wt / 2) * planes * 1024 + 1024; }
+inline int plane_back_bytes(int wt, int planes) { return (wt / 2) * (wt / 2) * planes * 1024; }
+inline int plane_layer_bytes(int wt, int planes) { return plane_front_bytes(wt, planes) + plane_back_bytes(wt, planes); }
 
-// W: [nout][nin] row-major fp32, b: [nout]; nin, nout <= 16 wt (zero padded).  dst: bf16_layer_bytes(wt) bytes.
-inline void bf16_pack_layer(const float* W, const float* b, int nin, int nout, int wt, void* dst) {
+// W: [nout][nin] row-major fp32, b: [nout]; nin, nout <= 16 wt (zero padded).  dst: plane_layer_bytes(wt, PLANES) bytes.
+// split(w, p) writes the PLANES 16-bit planes of one weight.
+template <int PLANES, class Split>
+inline void pack_plane_layer(const float* W, const float* b, int nin, int nout, int wt, void* dst, Split split) {
     unsigned char* img = static_cast<unsigned char*>(dst);
-    memset(img, 0, (size_t)bf16_layer_bytes(wt));
+    memset(img, 0, (size_t)plane_layer_bytes(wt, PLANES));
     const int half = wt / 2, kc = wt / 2;
     for (int nt = 0; nt < wt; ++nt) {
-        const size_t base = nt < half ? 0 : (size_t)bf16_front_bytes(wt);
+        const size_t base = nt < half ? 0 : (size_t)plane_front_bytes(wt, PLANES);
         for (int c = 0; c < kc; ++c)
             for (int lane = 0; lane < 64; ++lane)
                 for (int q = 0; q < 8; ++q) {
                     const int row = 16 * nt + (lane & 15), k = bf16_chunk_row(c, 8 * (lane >> 4) + q);
                     const float w = (row < nout && k < nin) ? W[(size_t)row * nin + k] : 0.f;
-                    uint16_t p[3];
-                    bf16_split3(w, p);
-                    for (int pl = 0; pl < 3; ++pl) {
-                        const size_t piece = (size_t)((nt % half) * kc + c) * 3 + pl;
+                    uint16_t p[PLANES];
+                    split(w, p);
+                    for (int pl = 0; pl < PLANES; ++pl) {
+                        const size_t piece = (size_t)((nt % half) * kc + c) * PLANES + pl;
                         memcpy(img + base + piece * 1024 + (size_t)lane * 16 + 2 * q, &p[pl], 2);
                     }
                 }
     }
-    float* bias = reinterpret_cast<float*>(img + (size_t)half * kc * 3 * 1024);
+    float* bias = reinterpret_cast<float*>(img + (size_t)half * kc * PLANES * 1024);
     for (int i = 0; i < 16 * wt; ++i) bias[i] = i < nout ? b[i] : 0.f;
+}
+
+inline int bf16_front_bytes(int wt) { return plane_front_bytes(wt, 3); }
+inline int bf16_back_bytes(int wt) { return plane_back_bytes(wt, 3); }
+inline int bf16_layer_bytes(int wt) { return plane_layer_bytes(wt, 3); }
+inline void bf16_pack_layer(const float* W, const float* b, int nin, int nout, int wt, void* dst) {
+    pack_plane_layer<3>(W, b, nin, nout, wt, dst, bf16_split3);
 }
 
 }  // namespace ac

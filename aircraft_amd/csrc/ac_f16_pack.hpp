@@ -1,6 +1,6 @@
 // ac_f16_pack.hpp — host-side image of a hidden (width x width) layer for the two-plane f16 matrix-core path of the
 // sensitivity engines (MlpEngine::layer_bf with HID == kHiddenF16), and the range gate that decides whether
-// a net may take that path.  Plain C++: ac_set_mlp packs and gates with it, and the CPU tests (tests/test_mlp_f16_planes.py)
+// a net may take that path.  Plain C++: build_mlp_model (ac_mlp_model.hpp) packs and gates with it, and the CPU tests (tests/test_mlp_f16_planes.py)
 // compile it with g++.
 //
 // Two-plane split: hi = f16(w) (round to nearest even), lo' = f16((w - hi) * S) with S = 2^11.  w - hi is exact in fp32 and
@@ -55,32 +55,12 @@ inline void f16_split2(float w, uint16_t p[2]) {
     p[0] = f16_rne(w);
     p[1] = f16_rne((w - f16_to_f32(p[0])) * kF16LoScale);
 }
-inline int f16_front_bytes(int wt) { return (wt / 2) * (wt / 2) * 2 * 1024 + 1024; }
-inline int f16_back_bytes(int wt) { return (wt / 2) * (wt / 2) * 2 * 1024; }
-inline int f16_layer_bytes(int wt) { return f16_front_bytes(wt) + f16_back_bytes(wt); }
-
+inline int f16_front_bytes(int wt) { return plane_front_bytes(wt, 2); }
+inline int f16_back_bytes(int wt) { return plane_back_bytes(wt, 2); }
+inline int f16_layer_bytes(int wt) { return plane_layer_bytes(wt, 2); }
 // W: [nout][nin] row-major fp32, b: [nout]; nin, nout <= 16 wt (zero padded).  dst: f16_layer_bytes(wt) bytes.
 inline void f16_pack_layer(const float* W, const float* b, int nin, int nout, int wt, void* dst) {
-    unsigned char* img = static_cast<unsigned char*>(dst);
-    memset(img, 0, (size_t)f16_layer_bytes(wt));
-    const int half = wt / 2, kc = wt / 2;
-    for (int nt = 0; nt < wt; ++nt) {
-        const size_t base = nt < half ? 0 : (size_t)f16_front_bytes(wt);
-        for (int c = 0; c < kc; ++c)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int q = 0; q < 8; ++q) {
-                    const int row = 16 * nt + (lane & 15), k = bf16_chunk_row(c, 8 * (lane >> 4) + q);
-                    const float w = (row < nout && k < nin) ? W[(size_t)row * nin + k] : 0.f;
-                    uint16_t p[2];
-                    f16_split2(w, p);
-                    for (int pl = 0; pl < 2; ++pl) {
-                        const size_t piece = (size_t)((nt % half) * kc + c) * 2 + pl;
-                        memcpy(img + base + piece * 1024 + (size_t)lane * 16 + 2 * q, &p[pl], 2);
-                    }
-                }
-    }
-    float* bias = reinterpret_cast<float*>(img + (size_t)half * kc * 2 * 1024);
-    for (int i = 0; i < 16 * wt; ++i) bias[i] = i < nout ? b[i] : 0.f;
+    pack_plane_layer<2>(W, b, nin, nout, wt, dst, f16_split2);
 }
 
 // ---- range gate -----------------------------------------------------------------------------------------------------

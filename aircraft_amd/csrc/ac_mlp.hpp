@@ -19,26 +19,11 @@
 //     streamed layer.
 #pragma once
 #include "ac_dynamics.hpp"
+#include "ac_mlp_plan.hpp"
 
 namespace ac {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct MlpPlan {
-    int n_layers;
-    int KT[AC_MAX_LAYERS];       // ceil(n_in / 16)
-    int NT[AC_MAX_LAYERS];       // ceil(n_out / 16)
-    int act[AC_MAX_LAYERS];      // 0 identity, 1 tanh; ac_set_mlp guarantees 1 on every layer but the last
-    int g_off[AC_MAX_LAYERS];    // float offset of the packed layer block in the global blob
-    int bytes[AC_MAX_LAYERS];    // block size: NT*KT*1024 (weights) + 1024 (bias piece)
-    int lds_off[AC_MAX_LAYERS];  // byte offset if resident, -1 if streamed through the ring
-    int ring_off[2];             // byte offsets of the two ring slots
-    int n_streamed;              // number of streamed layers per forward pass
-    int first_streamed;          // index of the first streamed layer (-1 if none)
-    int streamed[AC_MAX_LAYERS]; // layer index of the i-th streamed layer, i < n_streamed
-    int lds_total;               // dynamic LDS bytes to request
-    int bf_region[3];            // plan_bf / plan_bf_pair: byte offsets of the half-layer regions of the bf16 hidden layers
-};
 
 // The sensitivity engines of the two headline kernels (k_nn_step_sens<8, true>, k_nn_step_sens_pair<8>) run their hidden
 // layers on bf16 MFMA with three-plane operands (MlpEngine::layer_bf).  -DAC_HIDDEN_FP32 (in those two units

@@ -14,19 +14,11 @@
 // after the host-side fold; other nets keep the cross-lane validation path of ac_mlp.hpp.
 #pragma once
 #include "ac_kernels_nn.hpp"
+#include "ac_mlp_plan.hpp"
 
 namespace ac {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-struct ValuPlan {
-    int n_layers;                 // >= 2 (after the fold); layer 0: 8 (5 padded) -> W, hidden: W -> W, last: W -> 8 (6 padded)
-    int act_last;                 // tanh on the last layer?
-    int w_off[AC_MAX_LAYERS];     // float offset of the layer's weights in the image: [K][N] row-major (k-major) for all
-                                  // layers but the last, which is stored transposed [8][K + 4] (padded rows)
-    int b_off[AC_MAX_LAYERS];     // float offset of the bias (N floats, zero padded)
-    int image_floats;             // padded to a multiple of 256 (whole 1-KiB LDS-DMA pieces)
-};
 
 // acc.xy += a.{lo|hi} (broadcast) * w.xy
 AC_DI void pk_fma_alo(f32x2& acc, const f32x2& a, const f32x2& w) {

@@ -10,8 +10,7 @@
 #include <new>
 #include <vector>
 
-#include "ac_bf16_pack.hpp"
-#include "ac_f16_pack.hpp"
+#include "ac_mlp_model.hpp"
 #include "ac_kernels_analytic.hpp"
 #include "ac_nn_decl.hpp"
 #include "ac_ilqr.hpp"
@@ -65,11 +64,11 @@ int fail(int code, const char* msg) {
         if (e_ != hipSuccess) return hip_fail(e_, #call);      \
     } while (0)
 
-constexpr int kLdsBudget = 160 * 1024;  // gfx950 LDS per workgroup
-
 }  // namespace
 
-struct ac_handle {
+// The handle IS a model description (plans, wt, routes: MlpModelInfo, ac_mlp_model.hpp — what ac_set_mlp hands over from
+// build_mlp_model) plus the device state around it.
+struct ac_handle : MlpModelInfo {
     DevParams dp;
     int device;
     int num_cus;
@@ -77,29 +76,12 @@ struct ac_handle {
     bool no_pair;  // AIRCRAFT_HIP_NO_PAIR=1: never route a remainder to k_nn_step_sens_pair
     bool all_pair; // AIRCRAFT_HIP_ALL_PAIR=1: every unit through k_nn_step_sens_pair
     bool has_linear, has_poly, has_mlp;
-    MlpPlan plan;
-    MlpPlan plan_sens;  // the MFMA sensitivity engines' plan: last layer = [bias][wlt] for MlpEngine::last_valu (ac_set_mlp)
-    MlpPlan plan_rev;   // width 128 on the matrix cores, <= 3 hidden products: plan_sens + the TRANSPOSED hidden blocks for the
-    MlpPlan plan_bf;       // width 128 (wt 8), matrix cores: plan_sens with the hidden layers as three-plane bf16 images streamed
-    MlpPlan plan_bf_pair;  // in half-layer regions — three rotating (k_nn_step_sens), two (k_nn_step_sens_pair); ac_set_mlp
-    bool has_bf;
-    MlpPlan plan_f16;       // the same two plans over the two-plane f16 images (ac_f16_pack.hpp): the route of a net that
-    MlpPlan plan_f16_pair;  // passes the range gate (f16_gate); plan_bf / plan_bf_pair stay its fall-back
-    int f16_gate;           // F16Gate code of the net (0: passes); meaningful when has_bf
     int hidden_route;       // ac_hidden_route (ac_set_hidden_route); 0 = AC_HIDDEN_AUTO
-    bool has_rev;       // reverse sweep of k_nn_stage_tensors_rev (ac_hess_rev.hpp); rev_layers = layers of the net itself
-    int rev_layers;
-    float* d_rev_scratch;  // per-wave layer states of that kernel (ac_reserve_hess_workspace)
+    float* d_rev_scratch;  // per-wave layer states of k_nn_stage_tensors_rev (ac_reserve_hess_workspace)
     size_t rev_scratch_floats;
-    int wt;         // register tiles per slab the plan needs (2, 4 or 8)
-    int use_mfma;
     float* d_blob;  // packed MLP weights + biases (device)
     size_t blob_floats;
-    // "MFMA off" flavour on the tiled v_pk_fma_f32 engine (ac_mlp_valu.hpp): hidden widths <= 64, >= 2 layers
-    bool has_vplan;
-    ValuPlan vplan;
-    int vwidth;        // 32 or 64
-    float* d_vblob;    // weight image [layer][K][N] (+ biases), device
+    float* d_vblob;    // weight image [layer][K][N] (+ biases) of the "MFMA off" engine, device
     unsigned* d_queue; // ticket counter of the persistent tiled kernels (GroupQueue, ac_mlp_valu.hpp); 0 between launches
     float* d_hess_ws;  // [n][4][126] stage tensors of the MLP Hessian path (ac_reserve_hess_workspace)
     size_t hess_ws_floats;
@@ -234,22 +216,49 @@ void launch_hess(ac_handle* h, hipStream_t st, const float* X, const float* U, f
             default: hipLaunchKernelGGL(KERNEL<AC_MODEL_DEFAULT>, GRID, BLOCK, 0, st, h->dp, __VA_ARGS__); break;             \
         }                                                                                                   \
     } while (0)
-
-// Instantiate an NN kernel template for the (WT, MFMA) the handle needs.
-#define AC_NN_CASE_PLAN(PLAN_, WT_, MF_, KERNEL_EXPR, GRID, BLOCK, ...)                                \
-    if (h->wt == WT_ && (h->use_mfma != 0) == MF_) {                                                 \
-        auto kern = KERNEL_EXPR;                                                                     \
-        int rc_ = set_lds_limit(h, kern, (PLAN_).lds_total);                                         \
-        if (rc_ != AC_OK) return rc_;                                                                \
-        hipLaunchKernelGGL(kern, GRID, BLOCK, (PLAN_).lds_total, st, h->dp, PLAN_, h->d_blob, __VA_ARGS__); \
-        launched = true;                                                                             \
+// ... and as a function: f(std::integral_constant<int, MODEL>) for the handle's analytic model
+template <class F> void with_analytic_model(const ac_handle* h, F&& f) {
+    switch (h->dp.p.model_kind) {
+        case AC_MODEL_LINEAR: f(std::integral_constant<int, AC_MODEL_LINEAR>{}); break;
+        case AC_MODEL_POLY: f(std::integral_constant<int, AC_MODEL_POLY>{}); break;
+        case AC_MODEL_QUAD: f(std::integral_constant<int, AC_MODEL_QUAD>{}); break;
+        default: f(std::integral_constant<int, AC_MODEL_DEFAULT>{}); break;
     }
-#define AC_NN_CASE(WT_, MF_, KERNEL_EXPR, GRID, BLOCK, ...) AC_NN_CASE_PLAN(h->plan, WT_, MF_, KERNEL_EXPR, GRID, BLOCK, __VA_ARGS__)
-// kernels on MlpEngine (sensitivity and forward): the matrix-core flavour runs its edge layers on the vector ALUs and takes
-// plan_sens; the cross-lane validation flavour keeps plan.  (The second-order and the cooperative rollout engines: plan.)
-#define AC_NN_CASE_SENS(WT_, MF_, KERNEL_EXPR, GRID, BLOCK, ...)                                      \
-    if (MF_) { AC_NN_CASE_PLAN(h->plan_sens, WT_, MF_, KERNEL_EXPR, GRID, BLOCK, __VA_ARGS__) }       \
-    else { AC_NN_CASE_PLAN(h->plan, WT_, MF_, KERNEL_EXPR, GRID, BLOCK, __VA_ARGS__) }
+}
+
+// One launch of an NN kernel: raise the kernel's dynamic-LDS limit, launch, record the launch for ac_last_launch when a
+// name is given, and return the launch status.
+template <class K, class... Args>
+int launch_nn(ac_handle* h, hipStream_t st, const char* name, K kern, int grid, int block, int lds, const Args&... args) {
+    const int rc = set_lds_limit(h, kern, lds);
+    if (rc != AC_OK) return rc;
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    if (name) note_launch(h, name, grid, block, lds);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+
+// Instance selection: pick<Vs...>(v, f) hands the run-time v to the generic lambda f as a std::integral_constant and returns
+// f's status, or kNoInstance when v is none of Vs; instance() turns that into the caller's error.  Only instances declared in
+// ac_nn_decl.hpp may be named in f: every other one would be compiled into this unit.
+constexpr int kNoInstance = 1;  // (no ac_status is positive)
+const char* const kNoNnInstance = "no kernel instance for this MLP width / flavour";
+const char* const kNoTiledInstance = "no tiled vector-ALU kernel instance for this hidden width";
+template <int... Vs, class F> int pick(int v, F&& f) {
+    int rc = kNoInstance;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+// ... over the handle's (wt, use_mfma): f(WT, MF) with MF a std::bool_constant
+template <class F> int pick_wt_mfma(const ac_handle* h, F&& f) {
+    return pick<2, 4, 8>(h->wt, [&](auto WT) { return h->use_mfma ? f(WT, std::true_type{}) : f(WT, std::false_type{}); });
+}
+int instance(int rc, const char* missing) { return rc == kNoInstance ? fail(AC_ERR_UNSUPPORTED, missing) : rc; }
+
+// The plan of the kernels on MlpEngine (sensitivity and forward): the matrix-core flavour runs its edge layers on the vector
+// ALUs and takes plan_sens; the cross-lane validation flavour keeps plan.  (The second-order and the cooperative rollout
+// engines: plan.)
+const MlpPlan& engine_plan(const ac_handle* h) { return h->use_mfma ? h->plan_sens : h->plan; }
 
 }  // namespace
 
@@ -363,319 +372,29 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
                const float* out_std, int use_mfma) {
     AC_ENTER(h);
     if (!h || !widths || !act || !W || !b || !in_mean || !in_std || !out_mean || !out_std) return AC_ERR_BAD_ARG;
-    if (n_layers < 1 || n_layers > AC_MAX_LAYERS) return AC_ERR_BAD_ARG;
-    if (widths[0] != 5 || widths[n_layers] != 6) return AC_ERR_BAD_ARG;
-    for (int l = 0; l <= n_layers; ++l) {
-        if (widths[l] < 1) return AC_ERR_BAD_ARG;
-        if (widths[l] > AC_MAX_WIDTH) {
-            snprintf(g_err, sizeof(g_err), "MLP width %d > AC_MAX_WIDTH %d", widths[l], AC_MAX_WIDTH);
-            return AC_ERR_UNSUPPORTED;
-        }
-    }
-    // Fold every activation-free layer that is not the last into its successor (in float64):
-    //   W2 (W1 x + b1) + b2 = (W2 W1) x + (W2 b1 + b2).
-    // The device engines then see tanh on every layer but the last (a compile-time fact in the hidden-layer epilogues,
-    // which are exposed VALU time) and the reference checkpoint's Linear-Linear-Tanh-Linear net (surrogates/models.py:
-    // 114-123) runs as 5-32-6 instead of 5-16-32-6.
-    struct HostLayer { int nin, nout, act; std::vector<double> W, b; };
-    std::vector<HostLayer> net((size_t)n_layers);
-    for (int l = 0; l < n_layers; ++l) {
-        if (!W[l] || !b[l]) return AC_ERR_BAD_ARG;
-        HostLayer& L = net[(size_t)l];
-        L.nin = widths[l]; L.nout = widths[l + 1]; L.act = act[l] ? 1 : 0;
-        L.W.assign(W[l], W[l] + (size_t)L.nin * L.nout);
-        L.b.assign(b[l], b[l] + L.nout);
-    }
-    for (size_t l = 0; l + 1 < net.size();) {
-        if (net[l].act) { ++l; continue; }
-        const HostLayer &A = net[l], &B = net[l + 1];
-        HostLayer M;
-        M.nin = A.nin; M.nout = B.nout; M.act = B.act;
-        M.W.assign((size_t)M.nin * M.nout, 0.0);
-        M.b = B.b;
-        for (int i = 0; i < B.nout; ++i)
-            for (int k = 0; k < B.nin; ++k) {
-                const double w = B.W[(size_t)i * B.nin + k];
-                M.b[(size_t)i] += w * A.b[(size_t)k];
-                for (int j = 0; j < A.nin; ++j) M.W[(size_t)i * M.nin + j] += w * A.W[(size_t)k * A.nin + j];
-            }
-        net[l] = std::move(M);
-        net.erase(net.begin() + (long)l + 1);
-    }
-    n_layers = (int)net.size();
-    std::vector<int> fwidths((size_t)n_layers + 1);
-    std::vector<std::vector<float>> fW((size_t)n_layers), fb((size_t)n_layers);
-    fwidths[0] = net[0].nin;
-    for (int l = 0; l < n_layers; ++l) {
-        fwidths[(size_t)l + 1] = net[(size_t)l].nout;
-        fW[(size_t)l].assign(net[(size_t)l].W.begin(), net[(size_t)l].W.end());
-        fb[(size_t)l].assign(net[(size_t)l].b.begin(), net[(size_t)l].b.end());
-    }
-    widths = fwidths.data();
-    MlpPlan pl;
-    memset(&pl, 0, sizeof(pl));
-    pl.n_layers = n_layers;
-    // Hidden widths are zero-padded to one common multiple of 16 (wt tiles): padded neurons get zero weights
-    // and zero bias, so they output act(0) = 0 and feed nothing forward.  Input (5) pads to one tile, output (6)
-    // to one tile.  The engine then only meets the static shapes <1,wt>, <wt,wt>, <wt,1>, <1,1>.
-    int maxh = 0;
-    for (int l = 1; l < n_layers; ++l) maxh = std::max(maxh, widths[l]);
-    const int maxt = (maxh + 15) / 16;
-    const int wt = maxt <= 2 ? 2 : (maxt <= 4 ? 4 : 8);
-    size_t total_floats = 0;
-    const int wlt_bytes = ((wt * 384 + 1023) / 1024) * 1024;  // [wt tiles][4 lane groups][6 float4], whole LDS-DMA pieces
-    for (int l = 0; l < n_layers; ++l) {
-        pl.KT[l] = (l == 0) ? 1 : wt;
-        pl.NT[l] = (l == n_layers - 1) ? 1 : wt;
-        pl.act[l] = net[(size_t)l].act;  // 1 for every l < n_layers - 1 after the fold
-        pl.bytes[l] = pl.NT[l] * pl.KT[l] * 1024 + 1024;  // weights + one 1-KiB bias piece (whole LDS-DMA pieces only)
-        // first layer of a multi-layer net: + W0 transposed [5][16*wt] for the MFMA-free tangent slabs
-        if (l == 0 && n_layers > 1) pl.bytes[l] += ((5 * wt * 64 + 1023) / 1024) * 1024;
-        pl.g_off[l] = (int)total_floats;
-        total_floats += (size_t)pl.bytes[l] / 4;
-        // last layer of a multi-layer net: + wlt, the per-lane weight pairs of MlpEngine::last_valu — in the global blob only;
-        // plan_sens (below) copies [bias][wlt] to LDS, `pl` the fragments and the bias as before
-        if (l == n_layers - 1 && n_layers > 1) total_floats += (size_t)wlt_bytes / 4;
-    }
-    // Width 128 on the matrix cores with one to three hidden products: the transposed hidden blocks of the reverse sweep
-    // (k_nn_stage_tensors_rev), top hidden layer first, behind the net's own blocks.
-    const int n_hid = n_layers - 2;
-    const bool want_rev = wt == 8 && n_hid >= 1 && n_layers + n_hid <= AC_MAX_LAYERS;  // (both flavours of the matrix product)
-    size_t rev_off[AC_MAX_LAYERS] = {0};
-    const size_t rev_block_floats = (size_t)wt * wt * 256 + 256;  // fragments + a (zero) bias piece: the hidden blocks' size class
-    if (want_rev)
-        for (int i = 0; i < n_hid; ++i) { rev_off[i] = total_floats; total_floats += rev_block_floats; }
-    // Width 128 with hidden layers: their three-plane bf16 images (ac_bf16_pack.hpp) for the sensitivity kernels' layer_bf.
-    const bool want_bf = wt == 8 && n_hid >= 1;
-    size_t bf_off[AC_MAX_LAYERS] = {0}, f16_off[AC_MAX_LAYERS] = {0};
-    if (want_bf)
-        for (int l = 1; l < n_layers - 1; ++l) { bf_off[l] = total_floats; total_floats += (size_t)bf16_layer_bytes(wt) / 4; }
-    // ... and their two-plane f16 images (ac_f16_pack.hpp) behind those: which of the two the kernels read is decided per net
-    // by the range gate below (and ac_set_hidden_route)
-    if (want_bf)
-        for (int l = 1; l < n_layers - 1; ++l) { f16_off[l] = total_floats; total_floats += (size_t)f16_layer_bytes(wt) / 4; }
-    // Pack: [nt][kt][lane][4] with lane = col + 16 g -> W[16 nt + col][16 kt + 4 g + j]; then the padded bias.
-    std::vector<float> blob(total_floats, 0.f);
-    if (want_bf)
-        for (int l = 1; l < n_layers - 1; ++l)
-            bf16_pack_layer(fW[(size_t)l].data(), fb[(size_t)l].data(), widths[l], widths[l + 1], wt, blob.data() + bf_off[l]);
-    int gate = F16_GATE_OK;
-    if (want_bf) {
-        for (int l = 1; l < n_layers - 1; ++l)
-            f16_pack_layer(fW[(size_t)l].data(), fb[(size_t)l].data(), widths[l], widths[l + 1], wt, blob.data() + f16_off[l]);
-        std::vector<const float*> gw((size_t)n_layers), gb((size_t)n_layers);
-        for (int l = 0; l < n_layers; ++l) { gw[(size_t)l] = fW[(size_t)l].data(); gb[(size_t)l] = fb[(size_t)l].data(); }
-        gate = f16_gate(n_layers, widths, gw.data(), gb.data());
-    }
-    if (want_rev)
-        for (int i = 0; i < n_hid; ++i) {
-            const int l = n_hid - i;  // forward layer l: h_l (nin) -> h_{l+1} (nout); the block multiplies by its transpose
-            const int nin = widths[l], nout = widths[l + 1];
-            float* dst = blob.data() + rev_off[i];
-            for (int nt = 0; nt < wt; ++nt)
-                for (int kt = 0; kt < wt; ++kt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j) {
-                            const int row = 16 * nt + (lane & 15), k = 16 * kt + 4 * (lane >> 4) + j;
-                            dst[((size_t)(nt * wt + kt) * 64 + lane) * 4 + j] =
-                                (row < nin && k < nout) ? fW[(size_t)l][(size_t)k * nin + row] : 0.f;
-                        }
-        }
-    for (int l = 0; l < n_layers; ++l) {
-        const int nin = widths[l], nout = widths[l + 1], KT = pl.KT[l], NT = pl.NT[l];
-        float* dst = blob.data() + pl.g_off[l];
-        for (int nt = 0; nt < NT; ++nt)
-            for (int kt = 0; kt < KT; ++kt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const int row = 16 * nt + (lane & 15), k = 16 * kt + 4 * (lane >> 4) + j;
-                        dst[((size_t)(nt * KT + kt) * 64 + lane) * 4 + j] =
-                            (row < nout && k < nin) ? fW[(size_t)l][(size_t)row * nin + k] : 0.f;
-                    }
-        float* bd = dst + (size_t)NT * KT * 256;
-        for (int i = 0; i < NT * 16; ++i) bd[i] = i < nout ? fb[(size_t)l][(size_t)i] : 0.f;
-        if (l == 0 && n_layers > 1) {
-            float* wt0 = bd + 256;  // after the 1-KiB bias piece
-            for (int j = 0; j < 5; ++j)
-                for (int n = 0; n < wt * 16; ++n) wt0[j * wt * 16 + n] = n < nout ? fW[(size_t)l][(size_t)n * nin + j] : 0.f;
-        }
-        if (l == n_layers - 1 && n_layers > 1) {
-            float* wl = bd + 256;  // after the 1-KiB bias piece
-            auto wv = [&](int k, int n) { return (k < nout && n < nin) ? fW[(size_t)l][(size_t)k * nin + n] : 0.f; };
-            for (int t = 0; t < wt; ++t)
-                for (int g = 0; g < 4; ++g)
-                    for (int kp = 0; kp < 3; ++kp)
-                        for (int rp = 0; rp < 2; ++rp) {
-                            float* q = wl + (size_t)(((t * 4 + g) * 6) + 2 * kp + rp) * 4;
-                            const int n0 = 16 * t + 4 * g + 2 * rp;
-                            q[0] = wv(2 * kp, n0); q[1] = wv(2 * kp + 1, n0); q[2] = wv(2 * kp, n0 + 1); q[3] = wv(2 * kp + 1, n0 + 1);
-                        }
-        }
-    }
-    // LDS plan: everything resident if it fits; otherwise the largest layers stream through a 2-slot ring.
-    // force_stream: the largest size class goes through the ring even when everything would fit (plan_rev of a net with ONE
-    // hidden product: the reverse-sweep kernel sequences its hidden and transposed blocks through the ring by hand)
-    auto plan_lds = [&](MlpPlan& pl, bool force_stream = false) -> int {
-        const int n_layers = pl.n_layers;  // (plan_rev carries more blocks than the net has layers)
-        pl.n_streamed = 0; pl.first_streamed = -1;
-        int total = 0;
-        for (int l = 0; l < n_layers; ++l) total += pl.bytes[l];
-        for (int l = 0; l < n_layers; ++l) pl.lds_off[l] = 0;
-        if (total <= kLdsBudget && !force_stream) {
-            int off = 0;
-            for (int l = 0; l < n_layers; ++l) { pl.lds_off[l] = off; off += pl.bytes[l]; }
-            pl.n_streamed = 0; pl.first_streamed = -1; pl.lds_total = off;
-        } else {
-            int big = 0;
-            for (int l = 0; l < n_layers; ++l) big = std::max(big, pl.bytes[l]);
-            // stream every layer of the maximal size class; keep the rest resident
-            int off = 0, resident = 0;
-            for (int l = 0; l < n_layers; ++l) if (pl.bytes[l] < big) resident += pl.bytes[l];
-            if (resident + 2 * big > kLdsBudget) {
-                snprintf(g_err, sizeof(g_err), "MLP does not fit the LDS plan (%d resident + 2 x %d ring)", resident, big);
-                return (int)AC_ERR_UNSUPPORTED;
-            }
-            pl.first_streamed = -1;
-            for (int l = 0; l < n_layers; ++l) {
-                if (pl.bytes[l] < big) { pl.lds_off[l] = off; off += pl.bytes[l]; }
-                else { pl.lds_off[l] = -1; pl.n_streamed++; if (pl.first_streamed < 0) pl.first_streamed = l; }
-            }
-            pl.ring_off[0] = off; pl.ring_off[1] = off + big;
-            pl.lds_total = off + 2 * big;
-        }
-        for (int l = 0, i = 0; l < n_layers; ++l)
-            if (pl.lds_off[l] < 0) pl.streamed[i++] = l;
-        return AC_OK;
-    };
-    { const int rc = plan_lds(pl); if (rc != AC_OK) return rc; }
-    // plan_sens: the first and last layers run on the vector ALUs there (MlpEngine::first_valu / last_valu), so their LDS
-    // copies leave the MFMA fragments out: [bias 1 KiB][W0 transposed] and [bias 1 KiB][wlt] (the blob keeps the fragments
-    // in front of them for the other kernels)
-    MlpPlan ps = pl;
-    if (n_layers > 1) {
-        const int last = n_layers - 1;
-        ps.g_off[0] = pl.g_off[0] + pl.NT[0] * pl.KT[0] * 256;
-        ps.bytes[0] = pl.bytes[0] - pl.NT[0] * pl.KT[0] * 1024;
-        ps.g_off[last] = pl.g_off[last] + pl.NT[last] * pl.KT[last] * 256;
-        ps.bytes[last] = 1024 + wlt_bytes;
-        const int rc = plan_lds(ps);
-        if (rc != AC_OK) return rc;
-    }
-    // plan_bf: the edge blocks of plan_sens resident where they are, every hidden layer streamed through half-layer regions
-    // behind them (MlpEngine::acquire, BF engines)
-    MlpPlan pb = ps, pbp = ps;
-    if (want_bf) {
-        int off = 0;
-        for (int l = 0; l < n_layers; ++l) {
-            if (l == 0 || l == n_layers - 1) { pb.lds_off[l] = off; off += ps.bytes[l]; continue; }
-            pb.lds_off[l] = -1;
-            pb.g_off[l] = (int)bf_off[l];
-            pb.bytes[l] = bf16_layer_bytes(wt);
-        }
-        pb.n_streamed = 0; pb.first_streamed = 1;
-        for (int l = 1; l < n_layers - 1; ++l) pb.streamed[pb.n_streamed++] = l;
-        const int region = bf16_front_bytes(wt);
-        for (int i = 0; i < 3; ++i) pb.bf_region[i] = off + i * region;
-        pb.ring_off[0] = pb.ring_off[1] = -1;
-        pbp = pb;
-        pb.lds_total = off + 3 * region;
-        pbp.lds_total = off + 2 * region;
-        pbp.bf_region[2] = -1;
-        if (pb.lds_total > kLdsBudget) return fail(AC_ERR_UNSUPPORTED, "bf16 hidden-layer ring does not fit the LDS");
-    }
-    // plan_f16 / plan_f16_pair: the same rings over the f16 images (two planes: regions of 33 KiB instead of 49)
-    MlpPlan pf = pb, pfp = pbp;
-    if (want_bf) {
-        const int edge = pb.bf_region[0], region = f16_front_bytes(wt);
-        for (int l = 1; l < n_layers - 1; ++l) { pf.g_off[l] = (int)f16_off[l]; pf.bytes[l] = f16_layer_bytes(wt); }
-        for (int i = 0; i < 3; ++i) pf.bf_region[i] = edge + i * region;
-        pfp = pf;
-        pf.lds_total = edge + 3 * region;
-        pfp.lds_total = edge + 2 * region;
-        pfp.bf_region[2] = -1;
-    }
-    MlpPlan pr = ps;
-    bool rev_ok = false;
-    if (want_rev) {
-        for (int i = 0; i < n_hid; ++i) {
-            const int e = n_layers + i;
-            pr.KT[e] = wt; pr.NT[e] = wt; pr.act[e] = 0;
-            pr.g_off[e] = (int)rev_off[i];
-            pr.bytes[e] = (int)(rev_block_floats * 4);
-        }
-        pr.n_layers = n_layers + n_hid;
-        // the kernel expects the hidden and the transposed blocks to stream (one size class) and the edge blocks to stay
-        rev_ok = plan_lds(pr, /*force_stream=*/true) == AC_OK && pr.n_streamed == 2 * n_hid && pr.lds_off[0] >= 0 && pr.lds_off[n_layers - 1] >= 0;
-    }
-    // "MFMA off": weight image of the tiled vector-ALU engine, k-major [K][N] per layer (the last layer transposed [8][K]),
-    // hidden widths zero-padded to 32 or 64.  Nets it does not cover (wider than 64, or a single layer after the fold)
-    // keep the cross-lane validation path.
-    ValuPlan vp;
-    memset(&vp, 0, sizeof(vp));
-    std::vector<float> vimg;
-    bool vok = !use_mfma && n_layers >= 2 && maxh <= 64;
-    const int vw = maxh <= 32 ? 32 : 64;
-    if (vok) {
-        vp.n_layers = n_layers;
-        vp.act_last = net[(size_t)n_layers - 1].act;
-        size_t off = 0;
-        for (int l = 0; l < n_layers; ++l) {
-            const bool last = l == n_layers - 1;
-            const int K = l == 0 ? 8 : vw, N = last ? 8 : vw;
-            vp.w_off[l] = (int)off; off += last ? (size_t)N * (K + 4) : (size_t)K * N;  // last layer: transposed, rows padded
-            vp.b_off[l] = (int)off; off += (size_t)N;
-        }
-        vp.image_floats = (int)((off + 255) / 256 * 256);
-        vimg.assign((size_t)vp.image_floats, 0.f);
-        for (int l = 0; l < n_layers; ++l) {
-            const bool last = l == n_layers - 1;
-            const int nin = widths[l], nout = widths[l + 1], K = l == 0 ? 8 : vw, N = last ? 8 : vw;
-            float* wd = vimg.data() + vp.w_off[l];
-            for (int k = 0; k < nin; ++k)
-                for (int nn = 0; nn < nout; ++nn) {
-                    const float wv = fW[(size_t)l][(size_t)nn * nin + k];
-                    if (last) wd[(size_t)nn * (K + 4) + k] = wv;   // Wt[j][k], row stride K + 4
-                    else wd[(size_t)k * N + nn] = wv;        // W[k][n]
-                }
-            for (int nn = 0; nn < nout; ++nn) vimg[(size_t)vp.b_off[l] + nn] = fb[(size_t)l][(size_t)nn];
-        }
-        const int lds_need = vp.image_floats * 4 + 4 * 96 * (vw + 4) * 4;
-        if (lds_need > kLdsBudget) vok = false;
-    }
+    // the folded net, the packed blob, the LDS plans and the vector-ALU image: host arithmetic, ac_mlp_model.hpp
+    MlpModel m;
+    const int rc = build_mlp_model(n_layers, widths, act, W, b, use_mfma, m, g_err, sizeof(g_err));
+    if (rc != AC_OK) return rc;
     float* dv = nullptr;
-    if (vok) {
-        AC_HIP(hipMalloc(&dv, vimg.size() * sizeof(float)));
-        hipError_t ev = hipMemcpy(dv, vimg.data(), vimg.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (m.has_vplan) {
+        AC_HIP(hipMalloc(&dv, m.vimage.size() * sizeof(float)));
+        hipError_t ev = hipMemcpy(dv, m.vimage.data(), m.vimage.size() * sizeof(float), hipMemcpyHostToDevice);
         if (ev != hipSuccess) { (void)hipFree(dv); return hip_fail(ev, "hipMemcpy(valu image)"); }
     }
     float* d = nullptr;
     {
-        hipError_t em = hipMalloc(&d, total_floats * sizeof(float));
+        hipError_t em = hipMalloc(&d, m.blob.size() * sizeof(float));
         if (em != hipSuccess) { if (dv) (void)hipFree(dv); return hip_fail(em, "hipMalloc(mlp blob)"); }
     }
-    hipError_t e = hipMemcpy(d, blob.data(), total_floats * sizeof(float), hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(d, m.blob.data(), m.blob.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); if (dv) (void)hipFree(dv); return hip_fail(e, "hipMemcpy(mlp blob)"); }
     if (h->d_vblob) (void)hipFree(h->d_vblob);
     h->d_vblob = dv;
-    h->has_vplan = vok;
-    h->vplan = vp;
-    h->vwidth = vw;
     if (h->d_blob) (void)hipFree(h->d_blob);
     h->d_blob = d;
-    h->blob_floats = total_floats;
-    h->plan = pl;
-    h->plan_sens = ps;
-    h->plan_rev = pr;
-    h->plan_bf = pb;
-    h->plan_bf_pair = pbp;
-    h->has_bf = want_bf;
-    h->plan_f16 = pf;
-    h->plan_f16_pair = pfp;
-    h->f16_gate = gate;
-    h->has_rev = rev_ok;
-    h->rev_layers = n_layers;
-    h->wt = wt;
-    h->use_mfma = use_mfma ? 1 : 0;
+    h->blob_floats = m.blob.size();
+    static_cast<MlpModelInfo&>(*h) = m;
     memcpy(h->dp.mlp_in_mean, in_mean, 5 * sizeof(float));
     memcpy(h->dp.mlp_in_std, in_std, 5 * sizeof(float));
     memcpy(h->dp.mlp_out_mean, out_mean, 6 * sizeof(float));
@@ -689,27 +408,18 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
 // ---- compute entry points ------------------------------------------------------------------------
 static int launch_nn_fwd(ac_handle* h, int op, const float* X, const float* U, float dt, const float* dtp, long n,
                          long blk, float* out, hipStream_t st) {
-    bool launched = false;
+    auto name = [&](const char* deriv, const char* step, const char* aero) { return op == OP_DERIV ? deriv : (op == OP_STEP ? step : aero); };
     if (!h->use_mfma && h->has_vplan) {
         // "MFMA off": the value-only tile of ac_mlp_valu.hpp, 64 units per wave, 256 per workgroup
         const int grid = (int)((n + kBlock - 1) / kBlock);
         const int lds = h->vplan.image_floats * 4 + 4 * 64 * (h->vwidth + 4) * 4;
-#define AC_TILED_FWD(W_, OP_)                                                                                      \
-        if (h->vwidth == W_ && op == OP_) {                                                                        \
-            auto kern = k_nn_fwd_tiled<W_, OP_>;                                                                   \
-            int rc_ = set_lds_limit(h, kern, lds);                                                                 \
-            if (rc_ != AC_OK) return rc_;                                                                          \
-            hipLaunchKernelGGL(kern, grid, kBlock, lds, st, h->dp, h->vplan, h->d_vblob, X, U, dt, dtp, n, blk, out); \
-            launched = true;                                                                                       \
-        }
-        AC_TILED_FWD(32, OP_DERIV) AC_TILED_FWD(32, OP_STEP) AC_TILED_FWD(32, OP_AERO)
-        AC_TILED_FWD(64, OP_DERIV) AC_TILED_FWD(64, OP_STEP) AC_TILED_FWD(64, OP_AERO)
-#undef AC_TILED_FWD
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "no tiled vector-ALU kernel instance for this hidden width");
-        note_launch(h, op == OP_DERIV ? "k_nn_fwd_tiled<deriv>" : (op == OP_STEP ? "k_nn_fwd_tiled<step>" : "k_nn_fwd_tiled<aero>"), grid,
-                    kBlock, lds);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        return instance(pick<OP_DERIV, OP_STEP, OP_AERO>(op, [&](auto o) {
+            constexpr int OP = o;
+            return pick<32, 64>(h->vwidth, [&](auto W) {
+                return launch_nn(h, st, name("k_nn_fwd_tiled<deriv>", "k_nn_fwd_tiled<step>", "k_nn_fwd_tiled<aero>"),
+                                 k_nn_fwd_tiled<W(), OP>, grid, kBlock, lds, h->dp, h->vplan, h->d_vblob, X, U, dt, dtp, n, blk, out);
+            });
+        }), kNoTiledInstance);
     }
     // Two kernels: k_nn_fwd (16 units per wave, 64 per workgroup) and k_nn_fwd4 (four value slabs per wave, 256 units per
     // workgroup: the per-layer fixed costs are shared, measured 3.4x the time of a 64-unit workgroup for 4x the units).
@@ -727,38 +437,27 @@ static int launch_nn_fwd(ac_handle* h, int op, const float* X, const float* U, f
     long n4 = 0;  // units [0, n4) take k_nn_fwd4, [n4, n) take k_nn_fwd
     if (cost_fwd4 <= cost_fwd && cost_fwd4 <= cost_split) n4 = n;
     else if (cost_split < cost_fwd) n4 = full4;
+    const MlpPlan& plan = engine_plan(h);
     if (n4 > 0) {
         const int grid4 = (int)((n4 + kBlock - 1) / kBlock);
         const long zero = 0;
-#define AC_FWD4_CASE(WT_)                                                                                        \
-        if (h->wt == WT_) {                                                                                      \
-            if (op == OP_DERIV) { AC_NN_CASE_SENS(WT_, true, (k_nn_fwd4<WT_, OP_DERIV>), grid4, kBlock, X, U, dt, dtp, n4, blk, out, zero) } \
-            else if (op == OP_STEP) { AC_NN_CASE_SENS(WT_, true, (k_nn_fwd4<WT_, OP_STEP>), grid4, kBlock, X, U, dt, dtp, n4, blk, out, zero) } \
-            else { AC_NN_CASE_SENS(WT_, true, (k_nn_fwd4<WT_, OP_AERO>), grid4, kBlock, X, U, dt, dtp, n4, blk, out, zero) }    \
-        }
-        AC_FWD4_CASE(2) AC_FWD4_CASE(4) AC_FWD4_CASE(8)
-#undef AC_FWD4_CASE
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-        note_launch(h, op == OP_DERIV ? "k_nn_fwd4<deriv>" : (op == OP_STEP ? "k_nn_fwd4<step>" : "k_nn_fwd4<aero>"), grid4,
-                    kBlock, (h->use_mfma ? h->plan_sens : h->plan).lds_total);
-        AC_HIP(hipGetLastError());
-        if (n4 == n) return AC_OK;
-        launched = false;
+        const int rc = instance(pick<OP_DERIV, OP_STEP, OP_AERO>(op, [&](auto o) {
+            constexpr int OP = o;
+            return pick<2, 4, 8>(h->wt, [&](auto WT) {
+                return launch_nn(h, st, name("k_nn_fwd4<deriv>", "k_nn_fwd4<step>", "k_nn_fwd4<aero>"), k_nn_fwd4<WT(), OP>, grid4,
+                                 kBlock, plan.lds_total, h->dp, plan, h->d_blob, X, U, dt, dtp, n4, blk, out, zero);
+            });
+        }), kNoNnInstance);
+        if (rc != AC_OK || n4 == n) return rc;
     }
     const int grid = (int)((n - n4 + 63) / 64);
-#define AC_FWD_OPS(WT_, MF_)                                                                                   \
-    if (op == OP_DERIV) { AC_NN_CASE_SENS(WT_, MF_, (k_nn_fwd<WT_, MF_, OP_DERIV>), grid, kBlock, X, U, dt, dtp, n, blk, out, n4) } \
-    else if (op == OP_STEP) { AC_NN_CASE_SENS(WT_, MF_, (k_nn_fwd<WT_, MF_, OP_STEP>), grid, kBlock, X, U, dt, dtp, n, blk, out, n4) } \
-    else { AC_NN_CASE_SENS(WT_, MF_, (k_nn_fwd<WT_, MF_, OP_AERO>), grid, kBlock, X, U, dt, dtp, n, blk, out, n4) }
-    AC_FWD_OPS(2, true) AC_FWD_OPS(4, true) AC_FWD_OPS(8, true)
-    AC_FWD_OPS(2, false) AC_FWD_OPS(4, false) AC_FWD_OPS(8, false)
-#undef AC_FWD_OPS
-    if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-    if (n4 == 0)
-        note_launch(h, op == OP_DERIV ? "k_nn_fwd<deriv>" : (op == OP_STEP ? "k_nn_fwd<step>" : "k_nn_fwd<aero>"), grid,
-                    kBlock, (h->use_mfma ? h->plan_sens : h->plan).lds_total);
-    AC_HIP(hipGetLastError());
-    return AC_OK;
+    return instance(pick<OP_DERIV, OP_STEP, OP_AERO>(op, [&](auto o) {
+        constexpr int OP = o;
+        return pick_wt_mfma(h, [&](auto WT, auto MF) {  // (ac_last_launch keeps k_nn_fwd4 when it ran)
+            return launch_nn(h, st, n4 == 0 ? name("k_nn_fwd<deriv>", "k_nn_fwd<step>", "k_nn_fwd<aero>") : nullptr,
+                             k_nn_fwd<WT(), MF(), OP>, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob, X, U, dt, dtp, n, blk, out, n4);
+        });
+    }), kNoNnInstance);
 }
 
 static int derivative_impl(ac_handle* h, const float* X, const float* U, long n, long blk, float* Xdot, void* stream) {
@@ -885,92 +584,49 @@ int ac_rollout_f32(ac_handle* h, const float* X0, const float* U, float dt, long
         // the value-only tile with 4 or 8 instances per wave, four waves per workgroup
         const int grid = (int)((B + 4 * roll_units - 1) / (4 * roll_units));
         const int lds = h->vplan.image_floats * 4 + 4 * (int)roll_units * (h->vwidth + 4) * 4;
-        bool launched = false;
-#define AC_TILED_ROLL8(W_)                                                                                         \
-        if (h->vwidth == W_) {                                                                                     \
-            auto kern = k_nn_rollout_tiled8<W_>;                                                                   \
-            int rc_ = set_lds_limit(h, kern, lds);                                                                 \
-            if (rc_ != AC_OK) return rc_;                                                                          \
-            hipLaunchKernelGGL(kern, grid, kBlock, lds, st, h->dp, h->vplan, h->d_vblob, X0, U, dt, B, H, Xout);   \
-            launched = true;                                                                                       \
-        }
-        AC_TILED_ROLL8(32) AC_TILED_ROLL8(64)
-#undef AC_TILED_ROLL8
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "no tiled vector-ALU kernel instance for this hidden width");
-        note_launch(h, "k_nn_rollout_tiled8", grid, kBlock, lds);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        return instance(pick<32, 64>(h->vwidth, [&](auto W) {
+            return launch_nn(h, st, "k_nn_rollout_tiled8", k_nn_rollout_tiled8<W()>, grid, kBlock, lds, h->dp, h->vplan, h->d_vblob,
+                             X0, U, dt, B, H, Xout);
+        }), kNoTiledInstance);
     }
     if (h->dp.p.model_kind == AC_MODEL_NN && !h->use_mfma && h->has_vplan) {
         const int grid = (int)((B + kBlock - 1) / kBlock);
         const int lds = h->vplan.image_floats * 4 + 4 * 64 * (h->vwidth + 4) * 4;
-        bool launched = false;
-#define AC_TILED_ROLL(W_)                                                                                          \
-        if (h->vwidth == W_) {                                                                                     \
-            auto kern = k_nn_rollout_tiled<W_>;                                                                    \
-            int rc_ = set_lds_limit(h, kern, lds);                                                                 \
-            if (rc_ != AC_OK) return rc_;                                                                          \
-            hipLaunchKernelGGL(kern, grid, kBlock, lds, st, h->dp, h->vplan, h->d_vblob, X0, U, dt, B, H, Xout);   \
-            launched = true;                                                                                       \
-        }
-        AC_TILED_ROLL(32) AC_TILED_ROLL(64)
-#undef AC_TILED_ROLL
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "no tiled vector-ALU kernel instance for this hidden width");
-        note_launch(h, "k_nn_rollout_tiled", grid, kBlock, lds);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        return instance(pick<32, 64>(h->vwidth, [&](auto W) {
+            return launch_nn(h, st, "k_nn_rollout_tiled", k_nn_rollout_tiled<W()>, grid, kBlock, lds, h->dp, h->vplan, h->d_vblob,
+                             X0, U, dt, B, H, Xout);
+        }), kNoTiledInstance);
     }
     if (h->dp.p.model_kind == AC_MODEL_NN) {
         const long groups = (B + 15) / 16;  // 16 instances per wave-slab
-        bool launched = false;
         const int nh = h->plan.n_layers - 2;  // hidden (width x width) layers
         if (h->use_mfma && groups < 4096 && nh >= 1 && nh <= 3) {
             // cooperative with register-resident weights: each wave keeps the fragments of its own output tiles
             const int grid = (int)groups;
             const int lds = 2 * h->wt * 1024;  // double-buffered activation exchange only
-#define AC_REG_CASE(WT_, NH_)                                                                                \
-            if (h->wt == WT_ && nh == NH_) {                                                                \
-                hipLaunchKernelGGL((k_nn_rollout_reg<WT_, NH_>), grid, kBlock, lds, st, h->dp, h->plan, h->d_blob, X0, U, dt, B, H, Xout); \
-                launched = true;                                                                            \
-            }
-            AC_REG_CASE(2, 1) AC_REG_CASE(2, 2) AC_REG_CASE(2, 3) AC_REG_CASE(4, 1) AC_REG_CASE(4, 2) AC_REG_CASE(4, 3)
-            AC_REG_CASE(8, 1) AC_REG_CASE(8, 2) AC_REG_CASE(8, 3)
-#undef AC_REG_CASE
-            if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-            note_launch(h, "k_nn_rollout_reg", grid, kBlock, lds);
-            AC_HIP(hipGetLastError());
-            return AC_OK;
+            return instance(pick<2, 4, 8>(h->wt, [&](auto wt) {
+                constexpr int WT = wt;
+                return pick<1, 2, 3>(nh, [&](auto NH) {
+                    return launch_nn(h, st, "k_nn_rollout_reg", k_nn_rollout_reg<WT, NH()>, grid, kBlock, lds, h->dp, h->plan,
+                                     h->d_blob, X0, U, dt, B, H, Xout);
+                });
+            }), kNoNnInstance);
         }
         if (h->use_mfma && groups < 4096) {
             // cooperative: one 4-wave workgroup per 16 instances (4x the parallelism per instance)
             const int grid = (int)groups;
             const int lds = h->plan.lds_total + h->wt * 1024;  // + the activation exchange buffer
-#define AC_COOP_CASE(WT_)                                                                                   \
-            if (h->wt == WT_) {                                                                             \
-                auto kern = k_nn_rollout_coop<WT_, true>;                                                   \
-                int rc_ = set_lds_limit(h, kern, lds);                                                         \
-                if (rc_ != AC_OK) return rc_;                                                               \
-                hipLaunchKernelGGL(kern, grid, kBlock, lds, st, h->dp, h->plan, h->d_blob, X0, U, dt, B, H, Xout); \
-                launched = true;                                                                            \
-            }
-            AC_COOP_CASE(2) AC_COOP_CASE(4) AC_COOP_CASE(8)
-#undef AC_COOP_CASE
-            if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-            note_launch(h, "k_nn_rollout_coop", grid, kBlock, lds);
-            AC_HIP(hipGetLastError());
-            return AC_OK;
+            return instance(pick<2, 4, 8>(h->wt, [&](auto WT) {
+                return launch_nn(h, st, "k_nn_rollout_coop", k_nn_rollout_coop<WT(), true>, grid, kBlock, lds, h->dp, h->plan,
+                                 h->d_blob, X0, U, dt, B, H, Xout);
+            }), kNoNnInstance);
         }
         const int grid = (int)((groups + 3) / 4);
-        AC_NN_CASE_SENS(2, true, (k_nn_rollout<2, true>), grid, kBlock, X0, U, dt, B, H, Xout)
-        AC_NN_CASE_SENS(4, true, (k_nn_rollout<4, true>), grid, kBlock, X0, U, dt, B, H, Xout)
-        AC_NN_CASE_SENS(8, true, (k_nn_rollout<8, true>), grid, kBlock, X0, U, dt, B, H, Xout)
-        AC_NN_CASE_SENS(2, false, (k_nn_rollout<2, false>), grid, kBlock, X0, U, dt, B, H, Xout)
-        AC_NN_CASE_SENS(4, false, (k_nn_rollout<4, false>), grid, kBlock, X0, U, dt, B, H, Xout)
-        AC_NN_CASE_SENS(8, false, (k_nn_rollout<8, false>), grid, kBlock, X0, U, dt, B, H, Xout)
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-        note_launch(h, "k_nn_rollout", grid, kBlock, (h->use_mfma ? h->plan_sens : h->plan).lds_total);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        const MlpPlan& plan = engine_plan(h);
+        return instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
+            return launch_nn(h, st, "k_nn_rollout", k_nn_rollout<WT(), MF()>, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob,
+                             X0, U, dt, B, H, Xout);
+        }), kNoNnInstance);
     }
     const int grid = (int)((B + 63) / 64);
     AC_LAUNCH_ANALYTIC(k_rollout, grid, 64, X0, U, dt, B, H, Xout);
@@ -994,27 +650,16 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
         // units, 32 units per workgroup, ~0.73 of a full workgroup's time) instead of paying a full round for it.
         if (!h->use_mfma && h->has_vplan) {
             // "MFMA off": the tiled v_pk_fma_f32 engine (ac_mlp_valu.hpp)
-            bool launched = false;
             // 8 units per wave, eight waves per workgroup (two per SIMD), persistent: at most one workgroup per CU
             const long cus_t = h->num_cus > 0 ? h->num_cus : 256;
             // (a batch smaller than the chip fills whole workgroups: 200 full ones ran cfg2's 12 800 units in 0.120 ms, 256 of
             // six or seven working waves in 0.135)
             const int grid = (int)std::min<long>((n + 63) / 64, cus_t);
             const int lds = h->vplan.image_floats * 4 + 8 * 48 * (h->vwidth + 4) * 4;
-#define AC_TILED_SENS(W_)                                                                                          \
-            if (h->vwidth == W_) {                                                                                 \
-                auto kern = k_nn_step_sens_tiled8<W_>;                                                             \
-                int rc_ = set_lds_limit(h, kern, lds);                                                             \
-                if (rc_ != AC_OK) return rc_;                                                                      \
-                hipLaunchKernelGGL(kern, grid, kBlock8, lds, st, h->dp, h->vplan, h->d_vblob, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c, h->d_queue); \
-                launched = true;                                                                                   \
-            }
-            AC_TILED_SENS(32) AC_TILED_SENS(64)
-#undef AC_TILED_SENS
-            if (!launched) return fail(AC_ERR_UNSUPPORTED, "no tiled vector-ALU kernel instance for this hidden width");
-            note_launch(h, "k_nn_step_sens_tiled8", grid, kBlock8, lds);
-            AC_HIP(hipGetLastError());
-            return AC_OK;
+            return instance(pick<32, 64>(h->vwidth, [&](auto W) {
+                return launch_nn(h, st, "k_nn_step_sens_tiled8", k_nn_step_sens_tiled8<W()>, grid, kBlock8, lds, h->dp, h->vplan,
+                                 h->d_vblob, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c, h->d_queue);
+            }), kNoTiledInstance);
         }
         const long cus = h->num_cus > 0 ? h->num_cus : 256;
         const long per_round = 64 * cus;
@@ -1033,19 +678,13 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
         const bool f16_ok = bf && h->f16_gate == F16_GATE_OK;
         if (h->hidden_route == AC_HIDDEN_F16 && !f16_ok) return fail(AC_ERR_UNSUPPORTED, hidden_f16_refusal(h));
         const bool f16 = f16_ok && h->hidden_route != AC_HIDDEN_BF16;
-        const MlpPlan& plan_main = f16 ? h->plan_f16 : bf ? h->plan_bf : h->plan_sens;
         if (h->use_mfma && h->wt == 2 && h->dp.p.substeps <= 1) {
             // small nets: two persistent workgroups per CU = two waves per SIMD (k_nn_step_sens_w2)
             const int lds = ((h->plan_sens.lds_total + 15) & ~15) + kSensW2AccBytes;
             if (lds <= 80 * 1024) {
                 const int grid = (int)std::min<long>((n + 63) / 64, 2 * cus);
-                auto kern = k_nn_step_sens_w2<2>;
-                int rc_ = set_lds_limit(h, kern, lds);
-                if (rc_ != AC_OK) return rc_;
-                hipLaunchKernelGGL(kern, grid, kBlock, lds, st, h->dp, h->plan_sens, h->d_blob, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c);
-                note_launch(h, "k_nn_step_sens_w2", grid, kBlock, lds);
-                AC_HIP(hipGetLastError());
-                return AC_OK;
+                return launch_nn(h, st, "k_nn_step_sens_w2", k_nn_step_sens_w2<2>, grid, kBlock, lds, h->dp, h->plan_sens, h->d_blob,
+                                 X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c);
             }
         }
         if (n_main > 0) {
@@ -1055,46 +694,26 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
 #else
             const int grid = (int)((n_main + 63) / 64);  // (A/B flavour: a workgroup per task, as in round 2)
 #endif
-            bool launched = false;
-            AC_NN_CASE_SENS(2, true, (k_nn_step_sens<2, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
-            AC_NN_CASE_SENS(4, true, (k_nn_step_sens<4, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
-            if (f16) { AC_NN_CASE_PLAN(plan_main, 8, true, (k_nn_step_sens<8, true, kHiddenF16>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c) }
-            else { AC_NN_CASE_PLAN(plan_main, 8, true, (k_nn_step_sens<8, true>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c) }
-            AC_NN_CASE_SENS(2, false, (k_nn_step_sens<2, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
-            AC_NN_CASE_SENS(4, false, (k_nn_step_sens<4, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
-            AC_NN_CASE_SENS(8, false, (k_nn_step_sens<8, false>), grid, kBlock, X, U, dt, dt_per_unit, n_main, blk, Xn, A, Bm, c)
-            if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-            note_launch(h, "k_nn_step_sens", grid, kBlock, (h->use_mfma ? plan_main : h->plan).lds_total);
-            AC_HIP(hipGetLastError());
+            const MlpPlan& plan = f16 ? h->plan_f16 : bf ? h->plan_bf : engine_plan(h);
+            auto launch_main = [&](auto kern) {
+                return launch_nn(h, st, "k_nn_step_sens", kern, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob, X, U, dt,
+                                 dt_per_unit, n_main, blk, Xn, A, Bm, c);
+            };
+            const int rc_m = f16 ? launch_main(k_nn_step_sens<8, true, kHiddenF16>)
+                                 : instance(pick_wt_mfma(h, [&](auto WT, auto MF) { return launch_main(k_nn_step_sens<WT(), MF()>); }),
+                                            kNoNnInstance);
+            if (rc_m != AC_OK) return rc_m;
         }
         if (n_pair > 0) {
             const int grid_p = (int)((n_pair + 31) / 32);
             const MlpPlan& plan_p = f16 ? h->plan_f16_pair : bf ? h->plan_bf_pair : h->plan_sens;
             const int lds_p = plan_p.lds_total + 2 * h->wt * 1024 + 2 * 16 * 36 * (int)sizeof(float);  // + the pairs' activation and output exchanges
-            bool launched = false;
-#define AC_PAIR_CASE(WT_)                                                                                              \
-            if (h->wt == WT_) {                                                                                        \
-                auto kern = k_nn_step_sens_pair<WT_>;                                                                  \
-                int rc_ = set_lds_limit(h, kern, lds_p);                                                                  \
-                if (rc_ != AC_OK) return rc_;                                                                          \
-                hipLaunchKernelGGL(kern, grid_p, kBlock, lds_p, st, h->dp, plan_p, h->d_blob, X, U, dt, dt_per_unit, n,      \
-                                   blk, Xn, A, Bm, c, n_main);                                                          \
-                launched = true;                                                                                       \
-            }
-            if (f16) {
-                auto kern = k_nn_step_sens_pair<8, kHiddenF16>;
-                int rc_ = set_lds_limit(h, kern, lds_p);
-                if (rc_ != AC_OK) return rc_;
-                hipLaunchKernelGGL(kern, grid_p, kBlock, lds_p, st, h->dp, plan_p, h->d_blob, X, U, dt, dt_per_unit, n,
-                                   blk, Xn, A, Bm, c, n_main);
-                launched = true;
-            } else {
-                AC_PAIR_CASE(2) AC_PAIR_CASE(4) AC_PAIR_CASE(8)
-            }
-#undef AC_PAIR_CASE
-            if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-            if (n_main == 0) note_launch(h, "k_nn_step_sens_pair", grid_p, kBlock, lds_p);
-            AC_HIP(hipGetLastError());
+            auto launch_pair = [&](auto kern) {  // (ac_last_launch keeps the main kernel when there is one)
+                return launch_nn(h, st, n_main == 0 ? "k_nn_step_sens_pair" : nullptr, kern, grid_p, kBlock, lds_p, h->dp, plan_p,
+                                 h->d_blob, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c, n_main);
+            };
+            return f16 ? launch_pair(k_nn_step_sens_pair<8, kHiddenF16>)
+                       : instance(pick<2, 4, 8>(h->wt, [&](auto WT) { return launch_pair(k_nn_step_sens_pair<WT()>); }), kNoNnInstance);
         }
         return AC_OK;
     }
@@ -1103,21 +722,10 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
     static_assert(AnalyticSensN<AC_MODEL_DEFAULT>::value == AnalyticSensN<AC_MODEL_LINEAR>::value, "grid size below");
     const int grid_an = (int)((n + upb - 1) / upb);
     // (sub-stepped updates: a kernel of its own, so that the composition code does not set the registers of the common one)
-    if (h->dp.p.substeps > 1) {
-        switch (h->dp.p.model_kind) {
-            case AC_MODEL_LINEAR: hipLaunchKernelGGL((k_step_sens<AC_MODEL_LINEAR, true>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c); break;
-            case AC_MODEL_POLY: hipLaunchKernelGGL((k_step_sens<AC_MODEL_POLY, true>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c); break;
-            case AC_MODEL_QUAD: hipLaunchKernelGGL((k_step_sens<AC_MODEL_QUAD, true>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c); break;
-            default: hipLaunchKernelGGL((k_step_sens<AC_MODEL_DEFAULT, true>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c); break;
-        }
-    } else {
-        switch (h->dp.p.model_kind) {
-            case AC_MODEL_LINEAR: hipLaunchKernelGGL((k_step_sens<AC_MODEL_LINEAR, false>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c); break;
-            case AC_MODEL_POLY: hipLaunchKernelGGL((k_step_sens<AC_MODEL_POLY, false>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c); break;
-            case AC_MODEL_QUAD: hipLaunchKernelGGL((k_step_sens<AC_MODEL_QUAD, false>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c); break;
-            default: hipLaunchKernelGGL((k_step_sens<AC_MODEL_DEFAULT, false>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c); break;
-        }
-    }
+    with_analytic_model(h, [&](auto M) {
+        if (h->dp.p.substeps > 1) hipLaunchKernelGGL((k_step_sens<M(), true>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c);
+        else hipLaunchKernelGGL((k_step_sens<M(), false>), grid_an, kBlock, 0, st, h->dp, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c);
+    });
     note_launch(h, "k_step_sens", grid_an, kBlock, 0);
     AC_HIP(hipGetLastError());
     return AC_OK;
@@ -1147,35 +755,18 @@ static int deriv_sens_impl(ac_handle* h, const float* X, const float* U, long n,
         const long cus_t = h->num_cus > 0 ? h->num_cus : 256;
         const int grid = (int)std::min<long>((n + 63) / 64, cus_t);  // persistent workgroups + work queue (GroupQueue, ac_mlp_valu.hpp)
         const int lds = h->vplan.image_floats * 4 + 8 * 48 * (h->vwidth + 4) * 4;
-        bool launched = false;
-#define AC_TILED_DS(W_)                                                                                            \
-        if (h->vwidth == W_) {                                                                                     \
-            auto kern = k_nn_deriv_sens_tiled8<W_>;                                                                \
-            int rc_ = set_lds_limit(h, kern, lds);                                                                 \
-            if (rc_ != AC_OK) return rc_;                                                                          \
-            hipLaunchKernelGGL(kern, grid, kBlock8, lds, st, h->dp, h->vplan, h->d_vblob, X, U, n, blk, Xdot, Fx, Fu, h->d_queue); \
-            launched = true;                                                                                       \
-        }
-        AC_TILED_DS(32) AC_TILED_DS(64)
-#undef AC_TILED_DS
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "no tiled vector-ALU kernel instance for this hidden width");
-        note_launch(h, "k_nn_deriv_sens_tiled8", grid, kBlock8, lds);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        return instance(pick<32, 64>(h->vwidth, [&](auto W) {
+            return launch_nn(h, st, "k_nn_deriv_sens_tiled8", k_nn_deriv_sens_tiled8<W()>, grid, kBlock8, lds, h->dp, h->vplan,
+                             h->d_vblob, X, U, n, blk, Xdot, Fx, Fu, h->d_queue);
+        }), kNoTiledInstance);
     }
     if (h->dp.p.model_kind == AC_MODEL_NN) {
         const int grid = (int)((n + 63) / 64);
-        bool launched = false;
-        AC_NN_CASE_SENS(2, true, (k_nn_deriv_sens<2, true>), grid, kBlock, X, U, n, blk, Xdot, Fx, Fu)
-        AC_NN_CASE_SENS(4, true, (k_nn_deriv_sens<4, true>), grid, kBlock, X, U, n, blk, Xdot, Fx, Fu)
-        AC_NN_CASE_SENS(8, true, (k_nn_deriv_sens<8, true>), grid, kBlock, X, U, n, blk, Xdot, Fx, Fu)
-        AC_NN_CASE_SENS(2, false, (k_nn_deriv_sens<2, false>), grid, kBlock, X, U, n, blk, Xdot, Fx, Fu)
-        AC_NN_CASE_SENS(4, false, (k_nn_deriv_sens<4, false>), grid, kBlock, X, U, n, blk, Xdot, Fx, Fu)
-        AC_NN_CASE_SENS(8, false, (k_nn_deriv_sens<8, false>), grid, kBlock, X, U, n, blk, Xdot, Fx, Fu)
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-        note_launch(h, "k_nn_deriv_sens", grid, kBlock, (h->use_mfma ? h->plan_sens : h->plan).lds_total);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        const MlpPlan& plan = engine_plan(h);
+        return instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
+            return launch_nn(h, st, "k_nn_deriv_sens", k_nn_deriv_sens<WT(), MF()>, grid, kBlock, plan.lds_total, h->dp, plan,
+                             h->d_blob, X, U, n, blk, Xdot, Fx, Fu);
+        }), kNoNnInstance);
     }
     const int upb = 16 * (h->dp.p.model_kind == AC_MODEL_POLY ? AnalyticSensN<AC_MODEL_POLY>::value : AnalyticSensN<AC_MODEL_DEFAULT>::value);
     const int grid = (int)((n + upb - 1) / upb);
@@ -1308,7 +899,6 @@ static int hess_single(ac_handle* h, const float* X, const float* U, float dt, c
         if ((size_t)n * kStageFloats > h->hess_ws_floats)
             return fail(AC_ERR_WORKSPACE, "second-order workspace too small: call ac_reserve_hess_workspace(h, n) first");
         const int grid_t = (int)((n + 63) / 64);
-        bool launched = false;
 #ifndef AC_NO_HESS_REV
         if (h->has_rev && h->wt == 8) {
             // width 128: forward tangents + reverse sweep (12 slab-layer products per hidden layer instead of 29), persistent grid
@@ -1316,48 +906,37 @@ static int hess_single(ac_handle* h, const float* X, const float* U, float dt, c
             const size_t need_r = (size_t)grid_r * (kBlock / 64) * (size_t)rev_scratch_f32x4(h->wt, h->rev_layers - 2) * 4;
             if (need_r > h->rev_scratch_floats)
                 return fail(AC_ERR_WORKSPACE, "second-order workspace too small: call ac_reserve_hess_workspace(h, n) first");
-#define AC_REV_LAUNCH(KERN_)                                                                                        \
-            {                                                                                                       \
-                auto kern = KERN_;                                                                                  \
-                int rc_ = set_lds_limit(h, kern, h->plan_rev.lds_total);                                            \
-                if (rc_ != AC_OK) return rc_;                                                                       \
-                hipLaunchKernelGGL(kern, grid_r, kBlock, h->plan_rev.lds_total, st, h->dp, h->plan_rev, h->d_blob, X, U, dt,    \
-                                   dt_per_unit, n, blk, h->rev_layers, h->d_rev_scratch, h->d_hess_ws);            \
-            }
-            if (!h->use_mfma) AC_REV_LAUNCH((k_nn_stage_tensors_rev3<8, false>))  // the cross-lane validation form of the product
+            auto launch_rev = [&](auto kern) {
+                return launch_nn(h, st, "k_nn_stage_tensors_rev", kern, grid_r, kBlock, h->plan_rev.lds_total, h->dp, h->plan_rev,
+                                 h->d_blob, X, U, dt, dt_per_unit, n, blk, h->rev_layers, h->d_rev_scratch, h->d_hess_ws);
+            };
 #ifdef AC_HESS_REV6  // (A/B flavour: the six-slab reverse sweep, tools/archive/variant_lib.sh)
-            else AC_REV_LAUNCH(k_nn_stage_tensors_rev<8>)
-#else
-            else AC_REV_LAUNCH((k_nn_stage_tensors_rev3<8, true>))
+            const int rc = h->use_mfma ? launch_rev(k_nn_stage_tensors_rev<8>) : launch_rev(k_nn_stage_tensors_rev3<8, false>);
+#else           // (MFMA off: the cross-lane validation form of the product)
+            const int rc = h->use_mfma ? launch_rev(k_nn_stage_tensors_rev3<8, true>) : launch_rev(k_nn_stage_tensors_rev3<8, false>);
 #endif
-#undef AC_REV_LAUNCH
-            note_launch(h, "k_nn_stage_tensors_rev", grid_r, kBlock, h->plan_rev.lds_total);
-            launched = true;
-        } else {
+            if (rc != AC_OK) return rc;
+        } else
 #endif
-        AC_NN_CASE(2, true, (k_nn_stage_tensors<2, true, 0>), grid_t, kBlock, X, U, dt, dt_per_unit, n, blk, h->d_hess_ws)
-        AC_NN_CASE(4, true, (k_nn_stage_tensors<4, true, 0>), grid_t, kBlock, X, U, dt, dt_per_unit, n, blk, h->d_hess_ws)
-        AC_NN_CASE(8, true, (k_nn_stage_tensors<8, true, 0>), grid_t, kBlock, X, U, dt, dt_per_unit, n, blk, h->d_hess_ws)
-        AC_NN_CASE(2, false, (k_nn_stage_tensors<2, false, 0>), grid_t, kBlock, X, U, dt, dt_per_unit, n, blk, h->d_hess_ws)
-        AC_NN_CASE(4, false, (k_nn_stage_tensors<4, false, 0>), grid_t, kBlock, X, U, dt, dt_per_unit, n, blk, h->d_hess_ws)
-        // width 128 on the matrix cores: the cross pairs between inputs {0, 1} and {3, 4} come from a second launch
-        AC_NN_CASE(8, true, (k_nn_stage_tensors<8, true, 1>), grid_t, kBlock, X, U, dt, dt_per_unit, n, blk, h->d_hess_ws)
-#ifndef AC_NO_HESS_REV
+        {
+            auto launch_t = [&](auto kern) {
+                return launch_nn(h, st, nullptr, kern, grid_t, kBlock, h->plan.lds_total, h->dp, h->plan, h->d_blob, X, U, dt,
+                                 dt_per_unit, n, blk, h->d_hess_ws);
+            };
+            int rc = instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
+                if constexpr (WT() == 8 && !MF()) return (int)kNoInstance;
+                else return launch_t(k_nn_stage_tensors<WT(), MF(), 0>);
+            }), "second-order blocks at width > 64 need the MFMA path (use_mfma = 1)");
+            // width 128 on the matrix cores: the cross pairs between inputs {0, 1} and {3, 4} come from a second launch
+            if (rc == AC_OK && h->wt == 8) rc = launch_t(k_nn_stage_tensors<8, true, 1>);
+            if (rc != AC_OK) return rc;
         }
-#endif
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "second-order blocks at width > 64 need the MFMA path (use_mfma = 1)");
-        AC_HIP(hipGetLastError());
         launch_hess<AC_MODEL_NN>(h, st, X, U, dt, dt_per_unit, Lam, n, blk, Hout, &grid);
         note_launch(h, "k_step_hess", grid, kBlock, 0);
         AC_HIP(hipGetLastError());
         return AC_OK;
     }
-    switch (h->dp.p.model_kind) {
-        case AC_MODEL_LINEAR: launch_hess<AC_MODEL_LINEAR>(h, st, X, U, dt, dt_per_unit, Lam, n, blk, Hout, &grid); break;
-        case AC_MODEL_POLY: launch_hess<AC_MODEL_POLY>(h, st, X, U, dt, dt_per_unit, Lam, n, blk, Hout, &grid); break;
-        case AC_MODEL_QUAD: launch_hess<AC_MODEL_QUAD>(h, st, X, U, dt, dt_per_unit, Lam, n, blk, Hout, &grid); break;
-        default: launch_hess<AC_MODEL_DEFAULT>(h, st, X, U, dt, dt_per_unit, Lam, n, blk, Hout, &grid); break;
-    }
+    with_analytic_model(h, [&](auto M) { launch_hess<M()>(h, st, X, U, dt, dt_per_unit, Lam, n, blk, Hout, &grid); });
     note_launch(h, "k_step_hess", grid, kBlock, 0);
     AC_HIP(hipGetLastError());
     return AC_OK;
@@ -1802,63 +1381,31 @@ int ac_rollout_policy_f32(ac_handle* h, const ac_ilqr_cost* limits, const float*
             const long roll_units = h->vwidth == 64 ? kRolloutUnits<64> : kRolloutUnits<32>;
             const int grid = (int)((Bout + 4 * roll_units - 1) / (4 * roll_units));
             const int lds = h->vplan.image_floats * 4 + 4 * (int)roll_units * (h->vwidth + 4) * 4;
-            bool launched = false;
-#define AC_TILED_POL8(W_)                                                                                          \
-            if (h->vwidth == W_) {                                                                                 \
-                auto kern = k_nn_rollout_policy_tiled8<W_>;                                                        \
-                int rc_ = set_lds_limit(h, kern, lds);                                                             \
-                if (rc_ != AC_OK) return rc_;                                                                      \
-                hipLaunchKernelGGL(kern, grid, kBlock, lds, st, h->dp, h->vplan, h->d_vblob, pol, X0, dt, Bout, H, Xout, Uout); \
-                launched = true;                                                                                   \
-            }
-            AC_TILED_POL8(32) AC_TILED_POL8(64)
-#undef AC_TILED_POL8
-            if (!launched) return fail(AC_ERR_UNSUPPORTED, "no tiled vector-ALU kernel instance for this hidden width");
-            note_launch(h, "k_nn_rollout_policy_tiled8", grid, kBlock, lds);
-            AC_HIP(hipGetLastError());
-            return AC_OK;
+            return instance(pick<32, 64>(h->vwidth, [&](auto W) {
+                return launch_nn(h, st, "k_nn_rollout_policy_tiled8", k_nn_rollout_policy_tiled8<W()>, grid, kBlock, lds, h->dp,
+                                 h->vplan, h->d_vblob, pol, X0, dt, Bout, H, Xout, Uout);
+            }), kNoTiledInstance);
         }
         const int grid = (int)((Bout + 15) / 16);
-        bool launched = false;
         const int nh = h->plan.n_layers - 2;
         if (nh >= 1 && nh <= 3) {
             const int ldsr = 2 * h->wt * 1024;
-#define AC_POLREG_CASE(WT_, NH_)                                                                                \
-            if (h->wt == WT_ && nh == NH_) {                                                                    \
-                hipLaunchKernelGGL((k_nn_rollout_policy_reg<WT_, NH_>), grid, kBlock, ldsr, st, h->dp, h->plan, h->d_blob, pol, X0, dt, Bout, H, Xout, Uout); \
-                launched = true;                                                                                \
-            }
-            AC_POLREG_CASE(2, 1) AC_POLREG_CASE(2, 2) AC_POLREG_CASE(2, 3) AC_POLREG_CASE(4, 1) AC_POLREG_CASE(4, 2)
-            AC_POLREG_CASE(4, 3) AC_POLREG_CASE(8, 1) AC_POLREG_CASE(8, 2) AC_POLREG_CASE(8, 3)
-#undef AC_POLREG_CASE
-            if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-            note_launch(h, "k_nn_rollout_policy_reg", grid, kBlock, ldsr);
-            AC_HIP(hipGetLastError());
-            return AC_OK;
+            return instance(pick<2, 4, 8>(h->wt, [&](auto wt) {
+                constexpr int WT = wt;
+                return pick<1, 2, 3>(nh, [&](auto NH) {
+                    return launch_nn(h, st, "k_nn_rollout_policy_reg", k_nn_rollout_policy_reg<WT, NH()>, grid, kBlock, ldsr, h->dp,
+                                     h->plan, h->d_blob, pol, X0, dt, Bout, H, Xout, Uout);
+                });
+            }), kNoNnInstance);
         }
         const int lds = h->plan.lds_total + h->wt * 1024;
-#define AC_POL_CASE(WT_)                                                                                        \
-        if (h->wt == WT_) {                                                                                     \
-            auto kern = k_nn_rollout_policy_coop<WT_, true>;                                                    \
-            int rc_ = set_lds_limit(h, kern, lds);                                                                 \
-            if (rc_ != AC_OK) return rc_;                                                                       \
-            hipLaunchKernelGGL(kern, grid, kBlock, lds, st, h->dp, h->plan, h->d_blob, pol, X0, dt, Bout, H, Xout, Uout); \
-            launched = true;                                                                                    \
-        }
-        AC_POL_CASE(2) AC_POL_CASE(4) AC_POL_CASE(8)
-#undef AC_POL_CASE
-        if (!launched) return fail(AC_ERR_UNSUPPORTED, "no kernel instance for this MLP width / flavour");
-        note_launch(h, "k_nn_rollout_policy_coop", grid, kBlock, lds);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        return instance(pick<2, 4, 8>(h->wt, [&](auto WT) {
+            return launch_nn(h, st, "k_nn_rollout_policy_coop", k_nn_rollout_policy_coop<WT(), true>, grid, kBlock, lds, h->dp,
+                             h->plan, h->d_blob, pol, X0, dt, Bout, H, Xout, Uout);
+        }), kNoNnInstance);
     }
     const int grid = (int)((Bout + 63) / 64);
-    switch (h->dp.p.model_kind) {
-        case AC_MODEL_LINEAR: hipLaunchKernelGGL(k_rollout_policy<AC_MODEL_LINEAR>, grid, 64, 0, st, h->dp, pol, X0, dt, Bout, H, Xout, Uout); break;
-        case AC_MODEL_POLY: hipLaunchKernelGGL(k_rollout_policy<AC_MODEL_POLY>, grid, 64, 0, st, h->dp, pol, X0, dt, Bout, H, Xout, Uout); break;
-        case AC_MODEL_QUAD: hipLaunchKernelGGL(k_rollout_policy<AC_MODEL_QUAD>, grid, 64, 0, st, h->dp, pol, X0, dt, Bout, H, Xout, Uout); break;
-        default: hipLaunchKernelGGL(k_rollout_policy<AC_MODEL_DEFAULT>, grid, 64, 0, st, h->dp, pol, X0, dt, Bout, H, Xout, Uout); break;
-    }
+    with_analytic_model(h, [&](auto M) { hipLaunchKernelGGL(k_rollout_policy<M()>, grid, 64, 0, st, h->dp, pol, X0, dt, Bout, H, Xout, Uout); });
     note_launch(h, "k_rollout_policy", grid, 64, 0);
     AC_HIP(hipGetLastError());
     return AC_OK;
