@@ -19,6 +19,7 @@ MODEL_KINDS = {"default": 0, "linear": 1, "nn": 2, "poly": 3, "quad": 4}
 VJP_ROUTES = {"auto": 0, "fused": 1, "composed": 2}   # ac_vjp_route
 HIDDEN_ROUTES = {"auto": 0, "bf16": 1, "f16": 2}      # ac_hidden_route
 VJP_STEP, VJP_ROLLOUT, VJP_DERIVATIVE = 0, 1, 2       # ac_vjp_which
+WGRAD_SEEDS, WGRAD_STEP, WGRAD_ROLLOUT = 0, 1, 2      # ac_wgrad_which
 TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac_trim_f32 status per instance
 NUM_STATES = 13
 NUM_CONTROLS = 7
@@ -138,6 +139,12 @@ PROTOTYPES = {
     "ac_step_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_rollout_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_state_derivative_vjp_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_mlp_folded_shape": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ac_mlp_grad_floats": (C.c_int, [_VP, C.POINTER(C.c_size_t)]),
+    "ac_wgrad_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_step_wgrad_seeds_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_step_wgrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_rollout_wgrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_trim_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_trim_f32": (C.c_int, [_VP, C.POINTER(TrimOpts), _VP, _VP, _VP, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
                               _VP]),

@@ -12,13 +12,98 @@ Conventions: tensors only (NumPy arrays are refused: autograd cannot track them)
 dtype and on the device of the state input (the kernels compute in float32 on the handle's GPU); dt may be a Python number,
 a 0-d tensor or, for `step`, a per-unit tensor (n,) — a tensor dt that requires grad receives one.  First order only:
 differentiating a backward pass again raises.
+
+With the MLP surrogate the loss also back-propagates to the network's weights:
+
+    params = autodiff.MlpParameters(ac)          # a torch.nn.Module over the aircraft's net
+    opt = torch.optim.Adam(params.parameters(), lr=1e-3)
+    X = autodiff.rollout(ac, x0, U, dt, params=params)
+    ((X - X_measured) ** 2).mean().backward()    # fills .grad of every weight and bias (ac_rollout_wgrad_f32)
+    opt.step()                                   # the next forward pass re-installs the changed weights (params.sync())
 """
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["step", "rollout", "state_derivative"]
+__all__ = ["step", "rollout", "state_derivative", "MlpParameters"]
+
+
+class MlpParameters(torch.nn.Module):
+    """The weights of an aircraft's MLP surrogate as torch Parameters: one float32 Parameter per weight matrix and bias of the
+    net AS THE USER GAVE IT (activation-free layers included); the four scalers are buffers.  Passed as `params=` to `step` /
+    `rollout`, a loss back-propagates into their `.grad`.
+
+    The library runs the FOLDED net (every activation-free layer that is not the last merged into its successor, in float64:
+    ac_set_mlp) and its weight-gradient kernels differentiate that; `folded()` performs the same fold in torch, so autograd
+    carries the folded gradient back to the original tensors."""
+
+    def __init__(self, ac):
+        super().__init__()
+        model = getattr(ac, "coefficient_model", None)
+        if getattr(ac, "model_kind", None) != "nn" or model is None or not hasattr(model, "data"):
+            raise ValueError("MlpParameters: the aircraft's coefficient model is not the MLP surrogate (coeff_model_type 'nn')")
+        d = model.data
+        self._ac = ac
+        self.act = [int(a) for a in d.act]
+        self.weights = torch.nn.ParameterList([torch.nn.Parameter(torch.from_numpy(w.copy())) for w in d.weights])
+        self.biases = torch.nn.ParameterList([torch.nn.Parameter(torch.from_numpy(b.copy())) for b in d.biases])
+        for name in ("input_mean", "input_std", "output_mean", "output_std"):
+            self.register_buffer(name, torch.from_numpy(getattr(d, name).copy()))
+        self._installed = self._versions()  # the aircraft holds exactly these values
+
+    def _versions(self):
+        return tuple((id(p), p._version) for p in self.parameters())
+
+    def folded(self):
+        """[(W, b), ...] of the folded net, float32 (the fold itself in float64: fold_linear_layers of the library)."""
+        net = [(w.double(), b.double(), a) for w, b, a in zip(self.weights, self.biases, self.act)]
+        l = 0
+        while l + 1 < len(net):
+            (Wa, ba, aa), (Wb, bb, ab) = net[l], net[l + 1]
+            if aa:
+                l += 1
+                continue
+            net[l:l + 2] = [(Wb @ Wa, Wb @ ba + bb, ab)]
+        return [(W.float(), b.float()) for W, b, _ in net]
+
+    def flat(self):
+        """The folded net in the layout of the weight-gradient vector: per layer W (nout, nin) row-major, then b."""
+        return torch.cat([t.reshape(-1) for W, b in self.folded() for t in (W, b)])
+
+    def sync(self):
+        """Install the current parameter values in the aircraft (ac_set_mlp).  Called by `step` / `rollout` before a forward
+        pass when a parameter changed since the last installation."""
+        from .dynamics.base import _capturing
+        from .utils import MlpData
+
+        if _capturing():
+            raise RuntimeError("MlpParameters.sync(): the weights changed and ac_set_mlp allocates and copies — not possible "
+                               "while a stream is capturing; call params.sync() before the capture")
+        ac, model = self._ac, self._ac.coefficient_model
+        old = model.data
+        model.data = MlpData([w.detach().cpu().numpy() for w in self.weights], [b.detach().cpu().numpy() for b in self.biases],
+                             self.act, old.input_mean, old.input_std, old.output_mean, old.output_std)
+        ac._sync()
+        with torch.cuda.device(ac._device_obj()):
+            model.install(ac._handle)
+        self._installed = self._versions()
+
+    def sync_if_changed(self):
+        if self._versions() != self._installed:
+            self.sync()
+
+
+def _theta(ac, params):
+    """-> the flattened folded weights (an autograd input) after making sure the aircraft runs on the current values"""
+    if params is None:
+        return None
+    if not isinstance(params, MlpParameters):
+        raise TypeError(f"params: expected an MlpParameters, got {type(params).__name__}")
+    if params._ac is not ac:
+        raise ValueError("params: this MlpParameters was built from another aircraft")
+    params.sync_if_changed()
+    return params.flat()
 
 
 def _tensor(a, name):
@@ -66,46 +151,50 @@ def _dt_grad(gdt, dt_t):
 
 class _Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, u, dt_t, ac, dt_val):
+    def forward(ctx, x, u, dt_t, theta, ac, dt_val):
         ctx.ac, ctx.dt_val = ac, dt_val
-        ctx.save_for_backward(x, u, dt_t)
+        ctx.save_for_backward(x, u, dt_t, theta)
         y = ac.state_update(x.detach(), u.detach(), dt_val)
         return y.to(device=x.device, dtype=x.dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        x, u, dt_t = ctx.saved_tensors
-        need_x, need_u, need_dt = ctx.needs_input_grad[:3]
-        if not (need_x or need_u or need_dt):
-            return None, None, None, None, None
-        xb, ub, db = ctx.ac.step_vjp(x.detach(), u.detach(), ctx.dt_val, gy.contiguous())
+        x, u, dt_t, theta = ctx.saved_tensors
+        need_x, need_u, need_dt, need_w = ctx.needs_input_grad[:4]
+        xb = ub = db = wb = None
+        if need_x or need_u or need_dt:
+            xb, ub, db = ctx.ac.step_vjp(x.detach(), u.detach(), ctx.dt_val, gy.contiguous())
+        if need_w:
+            wb = ctx.ac.step_wgrad(x.detach(), u.detach(), ctx.dt_val, gy.contiguous()).to(device=theta.device, dtype=theta.dtype)
         return (_grad_like(xb, x) if need_x else None, _grad_like(ub, u) if need_u else None,
-                _dt_grad(db, dt_t) if need_dt else None, None, None)
+                _dt_grad(db, dt_t) if need_dt else None, wb, None, None)
 
 
 class _Rollout(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x0, U, dt_t, ac, dt_val):
+    def forward(ctx, x0, U, dt_t, theta, ac, dt_val):
         ctx.ac, ctx.dt_val = ac, dt_val
         X = ac.rollout(x0.detach(), U.detach(), dt_val)  # float32 on the handle's device: saved as the kernels read it
-        ctx.save_for_backward(x0, U, X, dt_t)
+        ctx.save_for_backward(x0, U, X, dt_t, theta)
         return X.to(device=x0.device, dtype=x0.dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gX):
-        x0, U, X, dt_t = ctx.saved_tensors
-        need_x, need_u, need_dt = ctx.needs_input_grad[:3]
-        if not (need_x or need_u or need_dt):
-            return None, None, None, None, None
+        x0, U, X, dt_t, theta = ctx.saved_tensors
+        need_x, need_u, need_dt, need_w = ctx.needs_input_grad[:4]
         vec = x0.dim() == 1
         Xs, Us, G = (X, U, gX) if not vec else (X.unsqueeze(-1), U.unsqueeze(-1), gX.unsqueeze(-1))
-        x0b, ub, db = ctx.ac.rollout_vjp(Xs, Us.detach(), ctx.dt_val, G.contiguous())
-        if vec:
-            x0b, ub, db = x0b[..., 0], ub[..., 0], db[0:1]
+        x0b = ub = db = wb = None
+        if need_x or need_u or need_dt:
+            x0b, ub, db = ctx.ac.rollout_vjp(Xs, Us.detach(), ctx.dt_val, G.contiguous())
+            if vec:
+                x0b, ub, db = x0b[..., 0], ub[..., 0], db[0:1]
+        if need_w:
+            wb = ctx.ac.rollout_wgrad(Xs, Us.detach(), ctx.dt_val, G.contiguous()).to(device=theta.device, dtype=theta.dtype)
         return (_grad_like(x0b, x0) if need_x else None, _grad_like(ub, U) if need_u else None,
-                _dt_grad(db, dt_t) if need_dt else None, None, None)
+                _dt_grad(db, dt_t) if need_dt else None, wb, None, None)
 
 
 class _Derivative(torch.autograd.Function):
@@ -127,27 +216,27 @@ class _Derivative(torch.autograd.Function):
         return _grad_like(xb, x) if need_x else None, _grad_like(ub, u) if need_u else None, None
 
 
-def step(ac, x, u, dt):
+def step(ac, x, u, dt, params=None):
     """x+ = F(x, u, dt) (SixDOF.state_update) with a grad_fn.  x (13, n) or (13,), u (num_controls, n), dt a number, a 0-d
-    tensor or a per-unit tensor (n,)."""
+    tensor or a per-unit tensor (n,).  params: an MlpParameters of `ac` — the loss then reaches the surrogate's weights too."""
     _tensor(x, "x"); _tensor(u, "u")
     _check_states(ac, x, ac.num_states, "x")
     if u.dim() != x.dim() or u.shape[0] not in (ac.num_controls, 7) or u.shape[1:] != x.shape[1:]:
         raise ValueError(f"u: expected ({ac.num_controls},{' n' if x.dim() == 2 else ''}) matching x, got {tuple(u.shape)}")
     n = x.shape[1] if x.dim() == 2 else 1
     dt_val, dt_t = _dt(dt, n, per_unit_ok=True)
-    return _Step.apply(x, u, dt_t, ac, dt_val)
+    return _Step.apply(x, u, dt_t, _theta(ac, params), ac, dt_val)
 
 
-def rollout(ac, x0, U, dt):
+def rollout(ac, x0, U, dt, params=None):
     """X[k+1] = F(X[k], U[k], dt) (SixDOF.rollout) with a grad_fn.  x0 (13, B) or (13,), U (H, num_controls, B) or
-    (H, num_controls), dt a number or a 0-d tensor -> X (H+1, 13, B)."""
+    (H, num_controls), dt a number or a 0-d tensor -> X (H+1, 13, B).  params: an MlpParameters of `ac` (see `step`)."""
     _tensor(x0, "x0"); _tensor(U, "U")
     _check_states(ac, x0, ac.num_states, "x0")
     if U.dim() != x0.dim() + 1 or U.shape[1] not in (ac.num_controls, 7) or U.shape[2:] != x0.shape[1:]:
         raise ValueError(f"U: expected (H, {ac.num_controls}, B) matching x0, got {tuple(U.shape)}")
     dt_val, dt_t = _dt(dt, 1, per_unit_ok=False)
-    return _Rollout.apply(x0, U, dt_t, ac, dt_val)
+    return _Rollout.apply(x0, U, dt_t, _theta(ac, params), ac, dt_val)
 
 
 def state_derivative(ac, x, u):

@@ -211,7 +211,7 @@ __global__ void k_vjp_contract(const float* __restrict__ A, const float* __restr
                                float* __restrict__ dtbar);
 __global__ void k_vjp_recur(const float* __restrict__ A, const float* __restrict__ Bm, const float* __restrict__ c,
                             const float* __restrict__ G, long B, long H, float* __restrict__ X0bar, float* __restrict__ Ubar,
-                            float* __restrict__ dtbar);
+                            float* __restrict__ dtbar, float* __restrict__ LamTraj);
 #ifdef AC_VJP_INSTANTIATE
 // One unit per lane:  Xbar = A' lam, Ubar = B' lam, dtbar = c . lam  (c, dtbar nullable).  A [13][13][n], Bm [13][7][n],
 // c [13][n] (ac_step_sens_f32's layout; Fx / Fu of ac_state_derivative_sens_f32 with c = NULL).
@@ -246,16 +246,21 @@ __global__ __launch_bounds__(kBlock) void k_vjp_contract(const float* __restrict
 // Reverse recurrence of a rollout over per-node Jacobians (ac_shoot_sens_f32's layout: A [H][13][13][B], Bm [H][13][7][B],
 // c [H][13][B]), one instance per lane, with an arbitrary external cotangent G [H+1][13][B]:
 //   lambda_H = G_H;  lambda_k = G_k + A_k' lambda_{k+1},  Ubar_k = B_k' lambda_{k+1},  dtbar += c_k . lambda_{k+1}
+// LamTraj (nullable) [H][13][B]: node k receives lambda_{k+1}.
 __global__ __launch_bounds__(kBlock) void k_vjp_recur(const float* __restrict__ A, const float* __restrict__ Bm,
                                                       const float* __restrict__ c, const float* __restrict__ G, long B, long H,
                                                       float* __restrict__ X0bar, float* __restrict__ Ubar,
-                                                      float* __restrict__ dtbar) {
+                                                      float* __restrict__ dtbar, float* __restrict__ LamTraj) {
     const long i = (long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= B) return;
     float lam[13];
     load_rows<13>(G + H * 13 * B, B, i, lam);
     float gdt = 0.f;
     for (long k = H - 1; k >= 0; --k) {
+        if (LamTraj) {  // (the weight gradient's units are (X_k, U_k, lambda_{k+1}), ac_wgrad.hpp)
+#pragma unroll
+            for (int j = 0; j < 13; ++j) LamTraj[(k * 13 + j) * B + i] = lam[j];
+        }
         const float* Ak = A + k * 169 * B;
         const float* Bk = Bm + k * 91 * B;
         const float* ck = c + k * 13 * B;

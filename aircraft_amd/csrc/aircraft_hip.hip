@@ -23,6 +23,7 @@
 #include "ac_select.hpp"
 #include "ac_vjp.hpp"
 #include "ac_trim.hpp"
+#include "ac_wgrad.hpp"
 
 using namespace ac;
 
@@ -82,6 +83,8 @@ struct ac_handle : MlpModelInfo {
     float* d_blob;  // packed MLP weights + biases (device)
     size_t blob_floats;
     float* d_vblob;    // weight image [layer][K][N] (+ biases) of the "MFMA off" engine, device
+    float* d_wgimg;    // fragments of the folded net for the weight gradient (build_wgrad_image, ac_wgrad.hpp), device
+    WgradPlan wg;
     unsigned* d_queue; // ticket counter of the persistent tiled kernels (GroupQueue, ac_mlp_valu.hpp); 0 between launches
     float* d_hess_ws;  // [n][4][126] stage tensors of the MLP Hessian path (ac_reserve_hess_workspace)
     size_t hess_ws_floats;
@@ -328,6 +331,7 @@ int ac_destroy(ac_handle* h) {
     if (!h) return AC_ERR_BAD_ARG;
     if (h->d_blob) (void)hipFree(h->d_blob);
     if (h->d_vblob) (void)hipFree(h->d_vblob);
+    if (h->d_wgimg) (void)hipFree(h->d_wgimg);
     if (h->d_queue) (void)hipFree(h->d_queue);
     if (h->d_track) (void)hipFree(h->d_track);
     if (h->d_poly_tab) (void)hipFree(h->d_poly_tab);
@@ -382,13 +386,25 @@ int ac_set_mlp(ac_handle* h, int n_layers, const int* widths, const int* act, co
         hipError_t ev = hipMemcpy(dv, m.vimage.data(), m.vimage.size() * sizeof(float), hipMemcpyHostToDevice);
         if (ev != hipSuccess) { (void)hipFree(dv); return hip_fail(ev, "hipMemcpy(valu image)"); }
     }
+    WgradPlan wg;
+    float* dw = nullptr;
+    {
+        std::vector<float> wimg;
+        build_wgrad_image(m, wg, wimg);
+        hipError_t ew = hipMalloc(&dw, wimg.size() * sizeof(float));
+        if (ew == hipSuccess) ew = hipMemcpy(dw, wimg.data(), wimg.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (ew != hipSuccess) { if (dw) (void)hipFree(dw); if (dv) (void)hipFree(dv); return hip_fail(ew, "hipMalloc/hipMemcpy(wgrad image)"); }
+    }
     float* d = nullptr;
     {
         hipError_t em = hipMalloc(&d, m.blob.size() * sizeof(float));
-        if (em != hipSuccess) { if (dv) (void)hipFree(dv); return hip_fail(em, "hipMalloc(mlp blob)"); }
+        if (em != hipSuccess) { if (dv) (void)hipFree(dv); (void)hipFree(dw); return hip_fail(em, "hipMalloc(mlp blob)"); }
     }
     hipError_t e = hipMemcpy(d, m.blob.data(), m.blob.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); if (dv) (void)hipFree(dv); return hip_fail(e, "hipMemcpy(mlp blob)"); }
+    if (e != hipSuccess) { (void)hipFree(d); if (dv) (void)hipFree(dv); (void)hipFree(dw); return hip_fail(e, "hipMemcpy(mlp blob)"); }
+    if (h->d_wgimg) (void)hipFree(h->d_wgimg);
+    h->d_wgimg = dw;
+    h->wg = wg;
     if (h->d_vblob) (void)hipFree(h->d_vblob);
     h->d_vblob = dv;
     if (h->d_blob) (void)hipFree(h->d_blob);
@@ -1538,7 +1554,7 @@ int ac_rollout_vjp_f32(ac_handle* h, const float* Xtraj, const float* U, float d
     rc = sens_impl(h, Xtraj, U, dt, nullptr, B * H, B, Xn, A, Bm, c, stream);
     if (rc != AC_OK) return rc;
     const int grid = (int)((B + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_vjp_recur, grid, kBlock, 0, st, A, Bm, c, G, B, H, X0bar, Ubar, dtbar);
+    hipLaunchKernelGGL(k_vjp_recur, grid, kBlock, 0, st, A, Bm, c, G, B, H, X0bar, Ubar, dtbar, (float*)nullptr);
     note_launch(h, "k_vjp_recur", grid, kBlock, 0);
     AC_HIP(hipGetLastError());
     return AC_OK;
@@ -1577,6 +1593,164 @@ int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, lo
     note_launch(h, "k_vjp_contract", grid, kBlock, 0);
     AC_HIP(hipGetLastError());
     return AC_OK;
+}
+
+// ---- reverse mode to the weights of the MLP surrogate (ac_wgrad.hpp) ----------------------------------------------------------
+namespace {
+// why the weight gradient cannot run on this handle (nullptr: it can); sets *code
+const char* wgrad_refusal(const ac_handle* h, int* code) {
+    *code = AC_ERR_UNSUPPORTED;
+    if (h->dp.p.model_kind != AC_MODEL_NN) return "weight gradients exist for the MLP surrogate only (model_kind nn)";
+    if (!h->has_mlp) { *code = AC_ERR_NO_MODEL; return "no MLP installed: call ac_set_mlp first"; }
+    if (h->dp.p.substeps > 1) return "weight gradients run one RK4 sub-step (physical_integration_substeps = 1)";
+    if (h->wg.act_last) return "weight gradients: tanh on the last layer is not supported";
+    if (h->wg.n_layers - 2 > wgrad_max_hidden_products(h->wt))
+        return "weight gradients: too many hidden-to-hidden layers for the accumulators of one workgroup (3 at width 128, 6 below)";
+    return nullptr;
+}
+int wgrad_parts(const ac_handle* h, size_t units) {
+    const size_t tiles = (4 * units + kWgSamples - 1) / kWgSamples, cus = h->num_cus > 0 ? (size_t)h->num_cus : 256;
+    return (int)std::max<size_t>(1, std::min(tiles, cus));
+}
+// [stage table 144 n][Z 20 n][Ybar 24 n][partials]
+size_t wgrad_seed_floats(size_t n) { return n * (size_t)kJacFloats; }
+size_t wgrad_step_floats(const ac_handle* h, size_t n) {
+    return wgrad_seed_floats(n) + 44 * n + (size_t)wgrad_parts(h, n) * (size_t)h->wg.grad_floats;
+}
+// rollout: [max(composed VJP workspace, step workspace) over the B H units][lambda 13 B H][X0bar 13 B][Ubar 7 B H][dtbar B]
+size_t wgrad_rollout_head(const ac_handle* h, size_t N) { return std::max(N * kVjpStepWs, wgrad_step_floats(h, N)); }
+
+int wgrad_seeds_impl(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, long blk,
+                     const float* Lam, float* Z, float* Ybar, float* table, hipStream_t st) {
+    const int grid_t = (int)((n + 63) / 64);
+    const MlpPlan& plan = engine_plan(h);
+    int rc = instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
+        return launch_nn(h, st, "k_nn_stage_jac", k_nn_stage_jac<WT(), MF()>, grid_t, kBlock, plan.lds_total, h->dp, plan, h->d_blob,
+                         X, U, dt, dt_per_unit, n, blk, table);
+    }), kNoNnInstance);
+    if (rc != AC_OK) return rc;
+    const int grid = (int)((n + kVjpBlock - 1) / kVjpBlock);
+    hipLaunchKernelGGL(k_wgrad_seeds, grid, kVjpBlock, 0, st, h->dp, X, U, dt, dt_per_unit, Lam, (const float*)table, n, blk, Z, Ybar);
+    note_launch(h, "k_wgrad_seeds", grid, kVjpBlock, 0);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+
+// seeds, weight gradient, reduction over n units; ws: wgrad_step_floats(h, n)
+int wgrad_step_impl(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, long blk,
+                    const float* Lam, float* Wbar, float* ws, hipStream_t st) {
+    const size_t N = (size_t)n;
+    float* table = ws;
+    float* Z = table + wgrad_seed_floats(N);
+    float* Ybar = Z + 20 * N;
+    float* partial = Ybar + 24 * N;
+    int rc = wgrad_seeds_impl(h, X, U, dt, dt_per_unit, n, blk, Lam, Z, Ybar, table, st);
+    if (rc != AC_OK) return rc;
+    const int parts = wgrad_parts(h, N), lds = wgrad_lds_bytes(h->wg.n_layers, h->wt);
+    rc = instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
+        return launch_nn(h, st, "k_mlp_wgrad", k_mlp_wgrad<WT(), MF()>, parts, kWgBlock, lds, h->wg, (const float*)h->d_wgimg,
+                         (const float*)Z, (const float*)Ybar, n, 4 * n, partial);
+    }), kNoNnInstance);
+    if (rc != AC_OK) return rc;
+    const int F = h->wg.grad_floats;
+    hipLaunchKernelGGL(k_wgrad_reduce, (F + kBlock - 1) / kBlock, kBlock, 0, st, (const float*)partial, parts, F, Wbar);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+}  // namespace
+
+int ac_mlp_folded_shape(const ac_handle* h, int* n_layers, int* widths) {
+    if (!h || !n_layers || !widths) return AC_ERR_BAD_ARG;
+    g_err[0] = 0;
+    if (!h->has_mlp) return fail(AC_ERR_NO_MODEL, "no MLP installed: call ac_set_mlp first");
+    *n_layers = h->wg.n_layers;
+    widths[0] = h->wg.nin[0];
+    for (int l = 0; l < h->wg.n_layers; ++l) widths[l + 1] = h->wg.nout[l];
+    return AC_OK;
+}
+
+int ac_mlp_grad_floats(const ac_handle* h, size_t* floats) {
+    if (!h || !floats) return AC_ERR_BAD_ARG;
+    g_err[0] = 0;
+    if (!h->has_mlp) return fail(AC_ERR_NO_MODEL, "no MLP installed: call ac_set_mlp first");
+    *floats = (size_t)h->wg.grad_floats;
+    return AC_OK;
+}
+
+int ac_wgrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats) {
+    if (!h || !floats || n_or_B < 0 || H < 0 || which < AC_WGRAD_SEEDS || which > AC_WGRAD_ROLLOUT) return AC_ERR_BAD_ARG;
+    g_err[0] = 0;
+    int code;
+    if (const char* why = wgrad_refusal(h, &code)) return fail(code, why);
+    const size_t n = (size_t)n_or_B;
+    if (which == AC_WGRAD_SEEDS) *floats = wgrad_seed_floats(n);
+    else if (which == AC_WGRAD_STEP) *floats = wgrad_step_floats(h, n);
+    else {
+        const size_t N = n * (size_t)H;
+        *floats = wgrad_rollout_head(h, N) + 13 * N + 13 * n + 7 * N + n;
+    }
+    return AC_OK;
+}
+
+int ac_step_wgrad_seeds_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n,
+                            const float* Lam, float* Z, float* Ybar, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (h && n == 0) return AC_OK;
+    if (!h || !X || !U || !Lam || !Z || !Ybar || n < 0) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = wgrad_refusal(h, &code)) return fail(code, why);
+    if (!ws || ws_floats < wgrad_seed_floats((size_t)n))
+        return fail(AC_ERR_WORKSPACE, "weight-gradient workspace too small: see ac_wgrad_workspace_floats");
+    return wgrad_seeds_impl(h, X, U, dt, dt_per_unit, n, n, Lam, Z, Ybar, ws, (hipStream_t)stream);
+}
+
+int ac_step_wgrad_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+                      float* Wbar, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !Wbar || n < 0 || (n > 0 && (!X || !U || !Lam))) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = wgrad_refusal(h, &code)) return fail(code, why);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        AC_HIP(hipMemsetAsync(Wbar, 0, (size_t)h->wg.grad_floats * sizeof(float), st));
+        return AC_OK;
+    }
+    if (!ws || ws_floats < wgrad_step_floats(h, (size_t)n))
+        return fail(AC_ERR_WORKSPACE, "weight-gradient workspace too small: see ac_wgrad_workspace_floats");
+    return wgrad_step_impl(h, X, U, dt, dt_per_unit, n, n, Lam, Wbar, ws, st);
+}
+
+int ac_rollout_wgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* Wbar,
+                         float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !Wbar || B < 0 || H < 0 || (B > 0 && H > 0 && (!Xtraj || !U || !G))) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = wgrad_refusal(h, &code)) return fail(code, why);
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0 || H == 0) {  // no step, no weight enters
+        AC_HIP(hipMemsetAsync(Wbar, 0, (size_t)h->wg.grad_floats * sizeof(float), st));
+        return AC_OK;
+    }
+    const size_t Bs = (size_t)B, N = Bs * (size_t)H, head = wgrad_rollout_head(h, N);
+    if (!ws || ws_floats < head + 13 * N + 13 * Bs + 7 * N + Bs)
+        return fail(AC_ERR_WORKSPACE, "weight-gradient workspace too small: see ac_wgrad_workspace_floats");
+    float* lam = ws + head;
+    float* X0bar = lam + 13 * N;
+    float* Ubar = X0bar + 13 * Bs;
+    float* dtbar = Ubar + 7 * N;
+    {   // the reverse recurrence of the composed VJP route, with lambda_{k+1} kept per node
+        float* Xn = ws;
+        float* A = Xn + 13 * N;
+        float* Bm = A + 169 * N;
+        float* c = Bm + 91 * N;
+        const int rc = sens_impl(h, Xtraj, U, dt, nullptr, B * H, B, Xn, A, Bm, c, stream);
+        if (rc != AC_OK) return rc;
+        const int grid = (int)((B + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_vjp_recur, grid, kBlock, 0, st, A, Bm, c, G, B, H, X0bar, Ubar, dtbar, lam);
+        AC_HIP(hipGetLastError());
+    }
+    // (the Jacobians are consumed: the step gradient's buffers reuse their place)
+    return wgrad_step_impl(h, Xtraj, U, dt, nullptr, B * H, B, lam, Wbar, ws, st);
 }
 
 // ---- steady-flight trim (ac_trim.hpp) -----------------------------------------------------------------------------------------

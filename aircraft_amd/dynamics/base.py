@@ -513,6 +513,110 @@ class SixDOF(ABC):
             Xb, Ub = Xb[..., 0], Ub[..., 0]
         return Xb, Ub
 
+    # ---- reverse mode to the weights of the MLP surrogate (include/aircraft_hip.h, ac_*_wgrad_*) -------------------------
+    _WGRAD_KINDS = {"seeds": _lib.WGRAD_SEEDS, "step": _lib.WGRAD_STEP, "rollout": _lib.WGRAD_ROLLOUT}
+
+    def mlp_folded_shape(self):
+        """Widths [5, ..., 6] of the net as the handle holds it (activation-free layers folded into their successors)."""
+        lib = self._sync()
+        nl = C.c_int()
+        widths = (C.c_int * (_lib.MAX_LAYERS + 1))()
+        _lib.check(lib.ac_mlp_folded_shape(self._handle, C.byref(nl), widths), "ac_mlp_folded_shape")
+        return [int(widths[i]) for i in range(nl.value + 1)]
+
+    def mlp_grad_floats(self):
+        """Length of the weight-gradient vector: per folded layer W[l] (nout, nin) row-major, then b[l]."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_mlp_grad_floats(self._handle, C.byref(need)), "ac_mlp_grad_floats")
+        return int(need.value)
+
+    def wgrad_workspace(self, kind, n, H=0):
+        """Device workspace of the weight-gradient call `kind` ("seeds", "step", "rollout" with n = B).  Allocate it before
+        capturing a graph and pass it as `ws=`."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_wgrad_workspace_floats(self._handle, self._WGRAD_KINDS[kind], int(n), int(H), C.byref(need)),
+                   "ac_wgrad_workspace_floats")
+        return _torch().empty(max(int(need.value), 1), device=self._device_obj(), dtype=_torch().float32)
+
+    def _wgrad_units(self, x, u, lam):
+        X, _, _ = self._in(x, self.num_states, "x")
+        U, _, _ = self._in_u(u)
+        L, _, _ = self._in(lam, self.num_states, "lam")
+        n = X.shape[1]
+        if U.shape[1] != n or L.shape[1] != n:
+            raise ValueError("x, u and lam must have the same number of columns")
+        return X, U, L, n
+
+    def step_wgrad_seeds(self, x, u, dt, lam, ws=None):
+        """Per RK4 stage, the normalised network input Z (4, 5, n) and the cotangent Ybar (4, 6, n) of the raw network output
+        for the loss sum(lam * F(x, u, dt)): the weight gradient of any surrogate evaluated at Z is its backward pass with
+        Ybar (device tensors)."""
+        torch = _torch()
+        X, U, L, n = self._wgrad_units(x, u, lam)
+        if ws is None:
+            ws = self.wgrad_workspace("seeds", n)
+        lib = self._sync()
+        dts, dtp, keep = self._dt_args(dt, n)
+        Z = torch.empty((4, 5, n), device=X.device, dtype=torch.float32)
+        Yb = torch.empty((4, 6, n), device=X.device, dtype=torch.float32)
+        _lib.check(lib.ac_step_wgrad_seeds_f32(self._handle, X.data_ptr(), U.data_ptr(), dts, dtp, n, L.data_ptr(), Z.data_ptr(),
+                                               Yb.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                   "ac_step_wgrad_seeds_f32")
+        del keep
+        return Z, Yb
+
+    def step_wgrad(self, x, u, dt, lam, ws=None, out=None):
+        """Gradient of sum(lam * F(x, u, dt)) over the weights of the folded MLP surrogate: a device tensor
+        (mlp_grad_floats(),), per folded layer W[l] (nout, nin) row-major followed by b[l]."""
+        torch = _torch()
+        X, U, L, n = self._wgrad_units(x, u, lam)
+        if ws is None:
+            ws = self.wgrad_workspace("step", n)
+        lib = self._sync()
+        dts, dtp, keep = self._dt_args(dt, n)
+        if out is None:
+            out = torch.empty((self.mlp_grad_floats(),), device=X.device, dtype=torch.float32)
+        _lib.check(lib.ac_step_wgrad_f32(self._handle, X.data_ptr(), U.data_ptr(), dts, dtp, n, L.data_ptr(), out.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), self._stream()), "ac_step_wgrad_f32")
+        del keep
+        return out
+
+    def rollout_wgrad(self, X, U, dt, G, ws=None, out=None):
+        """Gradient of sum(G * X) over the weights of the folded MLP surrogate, X (H+1, 13, B) the trajectory rollout()
+        returned for (x0, U, dt) and G (H+1, 13, B) the cotangent of every node: the layout of step_wgrad."""
+        torch = _torch()
+        dev = self._device_obj()
+
+        def t3(a, name, rows):
+            t = torch.as_tensor(np.asarray(a, dtype=np.float32) if not isinstance(a, torch.Tensor) else a)
+            if t.dim() != 3 or t.shape[1] not in rows:
+                raise ValueError(f"{name}: expected (., {rows[0]}, B), got {tuple(t.shape)}")
+            return t.to(device=dev, dtype=torch.float32)
+
+        Xt = t3(X, "X", (self.num_states,)).contiguous()
+        Gt = t3(G, "G", (self.num_states,)).contiguous()
+        Hp1, _, B = Xt.shape
+        H = Hp1 - 1
+        Ut = t3(U, "U", (self.num_controls, _lib.NUM_CONTROLS)) if H > 0 else torch.zeros((0, _lib.NUM_CONTROLS, B), device=dev)
+        if Gt.shape != Xt.shape or Ut.shape[0] != H or Ut.shape[2] != B:
+            raise ValueError(f"X {tuple(Xt.shape)}, U {tuple(Ut.shape)} and G {tuple(Gt.shape)} do not describe one rollout")
+        if Ut.shape[1] < _lib.NUM_CONTROLS:
+            Ut = torch.cat([Ut, torch.zeros((H, _lib.NUM_CONTROLS - Ut.shape[1], B), device=dev)], dim=1)
+        Ut = Ut.contiguous()
+        if np.ndim(dt) > 0 or (isinstance(dt, torch.Tensor) and dt.numel() != 1):
+            raise ValueError("rollout_wgrad: dt must be a scalar (as in rollout)")
+        if ws is None:
+            ws = self.wgrad_workspace("rollout", B, H)
+        lib = self._sync()
+        if out is None:
+            out = torch.empty((self.mlp_grad_floats(),), device=dev, dtype=torch.float32)
+        _lib.check(lib.ac_rollout_wgrad_f32(self._handle, Xt.data_ptr(), Ut.data_ptr() if H else None, C.c_float(float(dt)), B, H,
+                                            Gt.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                   "ac_rollout_wgrad_f32")
+        return out
+
     # ---- getters (reference dynamics/base.py:147-278, aircraft.py:255-330) ------------------------
     def _aero(self, x, u):
         lib = self._sync()

@@ -422,6 +422,37 @@ int ac_rollout_vjp_f32(ac_handle* h, const float* Xtraj, const float* U, float d
 int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, long n, const float* W, float* Xbar, float* Ubar,
                                 float* ws, size_t ws_floats, void* stream);
 
+/* ---- Reverse mode to the WEIGHTS of the MLP surrogate --------------------------------------------------------
+ * The gradient of  sum over units of Lam . F(x, u, dt; theta)  over the weights and biases of the net AS THE HANDLE HOLDS IT:
+ * ac_set_mlp folds every activation-free layer that is not the last into its successor, so the folded net has tanh on every
+ * layer but the last.
+ *   ac_mlp_folded_shape     n_layers and widths [n_layers + 1] (5 ... 6; room for AC_MAX_LAYERS + 1) of the folded net
+ *   ac_mlp_grad_floats      length of the gradient vector: per folded layer W[l] ([nout][nin] row-major, logical sizes, no
+ *                           padding) followed by b[l]
+ *   ac_step_wgrad_seeds_f32 Lam [13][n] -> per RK4 stage s the normalised network input Z [4][5][n] and the cotangent of the
+ *                           raw network output Ybar [4][6][n] (output scale and stall factors applied): the weight gradient of
+ *                           ANY differentiable surrogate evaluated at Z is its ordinary backward pass with Ybar
+ *   ac_step_wgrad_f32       Wbar [ac_mlp_grad_floats] (overwritten): the seeds, then the net's backward pass over the 4 n
+ *                           samples on the matrix cores (k_mlp_wgrad), one partial per workgroup in the workspace, added in a
+ *                           fixed order: the same inputs give the same bits
+ *   ac_rollout_wgrad_f32    Xtraj, U, G as ac_rollout_vjp_f32: the reverse recurrence lambda_k = G_k + A_k' lambda_{k+1} (the
+ *                           composed route, lambda kept in the workspace), then the step gradient over the B H units
+ *                           (X_k, U_k, lambda_{k+1})
+ * One RK4 sub-step only: physical_integration_substeps > 1 returns AC_ERR_UNSUPPORTED, as do a net with tanh on its last layer
+ * and a width-128 net with more than three hidden-to-hidden layers.  A model other than the MLP: AC_ERR_UNSUPPORTED.
+ * ws / ws_floats: caller-owned device scratch of at least ac_wgrad_workspace_floats(h, which, n or B, H) floats, else
+ * AC_ERR_WORKSPACE.  Asynchronous on `stream`, no allocation, no synchronisation, hipGraph-capturable. */
+typedef enum ac_wgrad_which { AC_WGRAD_SEEDS = 0, AC_WGRAD_STEP = 1, AC_WGRAD_ROLLOUT = 2 } ac_wgrad_which;
+int ac_mlp_folded_shape(const ac_handle* h, int* n_layers, int* widths);
+int ac_mlp_grad_floats(const ac_handle* h, size_t* floats);
+int ac_wgrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats);
+int ac_step_wgrad_seeds_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n,
+                            const float* Lam, float* Z, float* Ybar, float* ws, size_t ws_floats, void* stream);
+int ac_step_wgrad_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+                      float* Wbar, float* ws, size_t ws_floats, void* stream);
+int ac_rollout_wgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* Wbar,
+                         float* ws, size_t ws_floats, void* stream);
+
 /* ---- steady-flight trim (fixed-wing models) ------------------------------------------------------------------
  * Per instance, find z = (alpha, theta, phi [rad], aileron, elevator [deg], rudder [deg] | beta [rad]) such that the flight
  * given by target (p, V, psi, turn rate psid about NED down, and beta or rudder) is steady:
