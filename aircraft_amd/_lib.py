@@ -20,6 +20,7 @@ VJP_ROUTES = {"auto": 0, "fused": 1, "composed": 2}   # ac_vjp_route
 HIDDEN_ROUTES = {"auto": 0, "bf16": 1, "f16": 2}      # ac_hidden_route
 VJP_STEP, VJP_ROLLOUT, VJP_DERIVATIVE = 0, 1, 2       # ac_vjp_which
 WGRAD_SEEDS, WGRAD_STEP, WGRAD_ROLLOUT = 0, 1, 2      # ac_wgrad_which
+CGRAD_STEP, CGRAD_ROLLOUT = 0, 1                      # ac_cgrad_which
 TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac_trim_f32 status per instance
 NUM_STATES = 13
 NUM_CONTROLS = 7
@@ -145,6 +146,12 @@ PROTOTYPES = {
     "ac_step_wgrad_seeds_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_step_wgrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_rollout_wgrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_coef_grad_floats": (C.c_int, [_VP, C.POINTER(C.c_size_t)]),
+    "ac_cgrad_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_set_cgrad_grid": (C.c_int, [_VP, C.c_int]),
+    "ac_step_cgrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_rollout_cgrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
+                                       _VP]),
     "ac_trim_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_trim_f32": (C.c_int, [_VP, C.POINTER(TrimOpts), _VP, _VP, _VP, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
                               _VP]),

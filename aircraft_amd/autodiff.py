@@ -20,13 +20,19 @@ With the MLP surrogate the loss also back-propagates to the network's weights (D
     X = autodiff.rollout(ac, x0, U, dt, params=params)
     ((X - X_measured) ** 2).mean().backward()    # fills .grad of every weight and bias (ac_rollout_wgrad_f32)
     opt.step()                                   # the next forward pass re-installs the changed weights (params.sync())
+
+With the cubic-fit ("poly") or the linear model it reaches the model's coefficients the same way, through
+any number of RK4 sub-steps, and the backward pass is one fused sweep (ac_step_cgrad_f32 / ac_rollout_cgrad_f32) that yields
+the state, control, dt and coefficient gradients together:
+
+    params = autodiff.CoefficientParameters(ac)  # coef (6, 34) and intercept (6,), or W (6, 6)
 """
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["step", "rollout", "state_derivative", "MlpParameters"]
+__all__ = ["step", "rollout", "state_derivative", "MlpParameters", "CoefficientParameters"]
 
 
 class MlpParameters(torch.nn.Module):
@@ -94,16 +100,71 @@ class MlpParameters(torch.nn.Module):
             self.sync()
 
 
+class CoefficientParameters(torch.nn.Module):
+    """The coefficients of an aircraft's cubic-fit or linear model as float32 torch Parameters, copied from the model:
+    `coef` (6, 34) and `intercept` (6,) for "poly", `W` (6, 6) (the last column the bias) for "linear".  Passed as `params=` to
+    `step` / `rollout`, a loss back-propagates into their `.grad`."""
+
+    def __init__(self, ac):
+        super().__init__()
+        kind, model = getattr(ac, "model_kind", None), getattr(ac, "coefficient_model", None)
+        if kind not in ("poly", "linear") or model is None:
+            raise ValueError("CoefficientParameters: the aircraft's coefficient model is neither the cubic fits "
+                             "(coeff_model_type 'poly') nor the linear model ('linear')")
+        self._ac, self.kind = ac, kind
+
+        def par(a):
+            return torch.nn.Parameter(torch.tensor(a, dtype=torch.float32))
+
+        if kind == "poly":
+            self.coef, self.intercept = par(model.coef), par(model.intercept)
+        else:
+            self.W = par(model.W)
+        self._installed = self._versions()  # the aircraft holds exactly these values (its float32 rounding of the model data)
+
+    def _versions(self):
+        return tuple((id(p), p._version) for p in self.parameters())
+
+    def flat(self):
+        """The parameters in the layout of the coefficient-gradient vector (ac_coef_grad_floats): coef row-major then
+        intercept, or W row-major."""
+        if self.kind == "poly":
+            return torch.cat([self.coef.reshape(-1), self.intercept.reshape(-1)])
+        return self.W.reshape(-1)
+
+    def sync(self):
+        """Install the current parameter values in the aircraft through the model's own `install` (ac_set_poly rebuilds the
+        gradient and second-derivative tables).  Called by `step` / `rollout` before a forward pass when a parameter changed
+        since the last installation."""
+        from .dynamics.base import _capturing
+
+        if _capturing():
+            raise RuntimeError("CoefficientParameters.sync(): the coefficients changed and installing them copies to the device "
+                               "— not possible while a stream is capturing; call params.sync() before the capture")
+        ac, model = self._ac, self._ac.coefficient_model
+        for name in (("coef", "intercept") if self.kind == "poly" else ("W",)):
+            setattr(model, name, getattr(self, name).detach().cpu().numpy().astype("float64"))
+        ac._sync()
+        with torch.cuda.device(ac._device_obj()):
+            model.install(ac._handle)
+        self._installed = self._versions()
+
+    def sync_if_changed(self):
+        if self._versions() != self._installed:
+            self.sync()
+
+
 def _theta(ac, params):
-    """-> the flattened folded weights (an autograd input) after making sure the aircraft runs on the current values"""
+    """-> (the flattened parameters (an autograd input), True for coefficient parameters) after making sure the aircraft runs
+    on the current values"""
     if params is None:
-        return None
-    if not isinstance(params, MlpParameters):
-        raise TypeError(f"params: expected an MlpParameters, got {type(params).__name__}")
+        return None, False
+    if not isinstance(params, (MlpParameters, CoefficientParameters)):
+        raise TypeError(f"params: expected an MlpParameters or a CoefficientParameters, got {type(params).__name__}")
     if params._ac is not ac:
-        raise ValueError("params: this MlpParameters was built from another aircraft")
+        raise ValueError(f"params: this {type(params).__name__} was built from another aircraft")
     params.sync_if_changed()
-    return params.flat()
+    return params.flat(), isinstance(params, CoefficientParameters)
 
 
 def _tensor(a, name):
@@ -151,8 +212,8 @@ def _dt_grad(gdt, dt_t):
 
 class _Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, u, dt_t, theta, ac, dt_val):
-        ctx.ac, ctx.dt_val = ac, dt_val
+    def forward(ctx, x, u, dt_t, theta, ac, dt_val, coef):
+        ctx.ac, ctx.dt_val, ctx.coef = ac, dt_val, coef
         ctx.save_for_backward(x, u, dt_t, theta)
         y = ac.state_update(x.detach(), u.detach(), dt_val)
         return y.to(device=x.device, dtype=x.dtype)
@@ -163,18 +224,25 @@ class _Step(torch.autograd.Function):
         x, u, dt_t, theta = ctx.saved_tensors
         need_x, need_u, need_dt, need_w = ctx.needs_input_grad[:4]
         xb = ub = db = wb = None
-        if need_x or need_u or need_dt:
-            xb, ub, db = ctx.ac.step_vjp(x.detach(), u.detach(), ctx.dt_val, gy.contiguous())
-        if need_w:
-            wb = ctx.ac.step_wgrad(x.detach(), u.detach(), ctx.dt_val, gy.contiguous()).to(device=theta.device, dtype=theta.dtype)
+        if need_w and ctx.coef:  # ONE fused sweep: the coefficient gradient and whichever of x, u, dt are needed
+            wb, xb, ub, db = ctx.ac.step_coef_grad(x.detach(), u.detach(), ctx.dt_val, gy.contiguous(),
+                                                   need=(need_x, need_u, need_dt))
+            if x.dim() == 1:
+                xb, ub, db = (None if t is None else t[..., 0] for t in (xb, ub, db))
+            wb = wb.to(device=theta.device, dtype=theta.dtype)
+        else:
+            if need_x or need_u or need_dt:
+                xb, ub, db = ctx.ac.step_vjp(x.detach(), u.detach(), ctx.dt_val, gy.contiguous())
+            if need_w:
+                wb = ctx.ac.step_wgrad(x.detach(), u.detach(), ctx.dt_val, gy.contiguous()).to(device=theta.device, dtype=theta.dtype)
         return (_grad_like(xb, x) if need_x else None, _grad_like(ub, u) if need_u else None,
-                _dt_grad(db, dt_t) if need_dt else None, wb, None, None)
+                _dt_grad(db, dt_t) if need_dt else None, wb, None, None, None)
 
 
 class _Rollout(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x0, U, dt_t, theta, ac, dt_val):
-        ctx.ac, ctx.dt_val = ac, dt_val
+    def forward(ctx, x0, U, dt_t, theta, ac, dt_val, coef):
+        ctx.ac, ctx.dt_val, ctx.coef = ac, dt_val, coef
         X = ac.rollout(x0.detach(), U.detach(), dt_val)  # float32 on the handle's device: saved as the kernels read it
         ctx.save_for_backward(x0, U, X, dt_t, theta)
         return X.to(device=x0.device, dtype=x0.dtype)
@@ -187,14 +255,20 @@ class _Rollout(torch.autograd.Function):
         vec = x0.dim() == 1
         Xs, Us, G = (X, U, gX) if not vec else (X.unsqueeze(-1), U.unsqueeze(-1), gX.unsqueeze(-1))
         x0b = ub = db = wb = None
-        if need_x or need_u or need_dt:
-            x0b, ub, db = ctx.ac.rollout_vjp(Xs, Us.detach(), ctx.dt_val, G.contiguous())
+        if need_w and ctx.coef:  # ONE fused sweep (see _Step.backward)
+            wb, x0b, ub, db = ctx.ac.rollout_coef_grad(Xs, Us.detach(), ctx.dt_val, G.contiguous(), need=(need_x, need_u, need_dt))
             if vec:
-                x0b, ub, db = x0b[..., 0], ub[..., 0], db[0:1]
-        if need_w:
-            wb = ctx.ac.rollout_wgrad(Xs, Us.detach(), ctx.dt_val, G.contiguous()).to(device=theta.device, dtype=theta.dtype)
+                x0b, ub = (None if t is None else t[..., 0] for t in (x0b, ub))
+            wb = wb.to(device=theta.device, dtype=theta.dtype)
+        else:
+            if need_x or need_u or need_dt:
+                x0b, ub, db = ctx.ac.rollout_vjp(Xs, Us.detach(), ctx.dt_val, G.contiguous())
+                if vec:
+                    x0b, ub, db = x0b[..., 0], ub[..., 0], db[0:1]
+            if need_w:
+                wb = ctx.ac.rollout_wgrad(Xs, Us.detach(), ctx.dt_val, G.contiguous()).to(device=theta.device, dtype=theta.dtype)
         return (_grad_like(x0b, x0) if need_x else None, _grad_like(ub, U) if need_u else None,
-                _dt_grad(db, dt_t) if need_dt else None, wb, None, None)
+                _dt_grad(db, dt_t) if need_dt else None, wb, None, None, None)
 
 
 class _Derivative(torch.autograd.Function):
@@ -218,25 +292,29 @@ class _Derivative(torch.autograd.Function):
 
 def step(ac, x, u, dt, params=None):
     """x+ = F(x, u, dt) (SixDOF.state_update) with a grad_fn.  x (13, n) or (13,), u (num_controls, n), dt a number, a 0-d
-    tensor or a per-unit tensor (n,).  params: an MlpParameters of `ac` — the loss then reaches the surrogate's weights too."""
+    tensor or a per-unit tensor (n,).  params: an MlpParameters or a CoefficientParameters of `ac` — the loss then reaches the
+    surrogate's weights, or the coefficients of the cubic-fit / linear model, too."""
     _tensor(x, "x"); _tensor(u, "u")
     _check_states(ac, x, ac.num_states, "x")
     if u.dim() != x.dim() or u.shape[0] not in (ac.num_controls, 7) or u.shape[1:] != x.shape[1:]:
         raise ValueError(f"u: expected ({ac.num_controls},{' n' if x.dim() == 2 else ''}) matching x, got {tuple(u.shape)}")
     n = x.shape[1] if x.dim() == 2 else 1
     dt_val, dt_t = _dt(dt, n, per_unit_ok=True)
-    return _Step.apply(x, u, dt_t, _theta(ac, params), ac, dt_val)
+    theta, coef = _theta(ac, params)
+    return _Step.apply(x, u, dt_t, theta, ac, dt_val, coef)
 
 
 def rollout(ac, x0, U, dt, params=None):
     """X[k+1] = F(X[k], U[k], dt) (SixDOF.rollout) with a grad_fn.  x0 (13, B) or (13,), U (H, num_controls, B) or
-    (H, num_controls), dt a number or a 0-d tensor -> X (H+1, 13, B).  params: an MlpParameters of `ac` (see `step`)."""
+    (H, num_controls), dt a number or a 0-d tensor -> X (H+1, 13, B).  params: an MlpParameters or a CoefficientParameters of
+    `ac` (see `step`)."""
     _tensor(x0, "x0"); _tensor(U, "U")
     _check_states(ac, x0, ac.num_states, "x0")
     if U.dim() != x0.dim() + 1 or U.shape[1] not in (ac.num_controls, 7) or U.shape[2:] != x0.shape[1:]:
         raise ValueError(f"U: expected (H, {ac.num_controls}, B) matching x0, got {tuple(U.shape)}")
     dt_val, dt_t = _dt(dt, 1, per_unit_ok=False)
-    return _Rollout.apply(x0, U, dt_t, _theta(ac, params), ac, dt_val)
+    theta, coef = _theta(ac, params)
+    return _Rollout.apply(x0, U, dt_t, theta, ac, dt_val, coef)
 
 
 def state_derivative(ac, x, u):

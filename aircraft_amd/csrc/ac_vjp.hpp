@@ -58,10 +58,11 @@ struct VjpColumn {
 };
 
 // One full state_update (all sub-steps, the final normalisation) pulled back:  gx = A' lam, gu = B' lam, gdt = c . lam.
-template <int MODEL>
-AC_DI void step_vjp_unit(const DevParams& P, const float x[13], const float u[7], float dt, const float lam[13],
+// `coeffs`: the coefficient provider of the sweep; its vjp() is called once per RK4 stage of every sub-step, in reverse order
+// (a recording provider, ac_cgrad.hpp, sees the samples of all 4 ns stages there).
+template <class Coeffs>
+AC_DI void step_vjp_unit(const DevParams& P, Coeffs& coeffs, const float x[13], const float u[7], float dt, const float lam[13],
                          const VjpColumn& col, float gx[13], float gu[7], float& gdt) {
-    AdjAnalyticCoeffs<MODEL> coeffs;
     const int ns = P.p.substeps < 1 ? 1 : P.p.substeps;
     const float h = (ns == 1) ? dt : dt / (float)ns;
     // forward: the inputs of sub-steps 1 .. ns-1 exactly as state_update_carry forms them
@@ -106,6 +107,12 @@ AC_DI void step_vjp_unit(const DevParams& P, const float x[13], const float u[7]
         gh += ghs;
     }
     gdt = (ns == 1) ? gh : gh * (1.0f / (float)ns);  // h = dt / ns
+}
+template <int MODEL>
+AC_DI void step_vjp_unit(const DevParams& P, const float x[13], const float u[7], float dt, const float lam[13],
+                         const VjpColumn& col, float gx[13], float gu[7], float& gdt) {
+    AdjAnalyticCoeffs<MODEL> coeffs;
+    step_vjp_unit(P, coeffs, x, u, dt, lam, col, gx, gu, gdt);
 }
 
 // f itself pulled back:  gx = (df/dx)' w,  gu = (df/du)' w

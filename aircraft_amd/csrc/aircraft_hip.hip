@@ -24,6 +24,7 @@
 #include "ac_vjp.hpp"
 #include "ac_trim.hpp"
 #include "ac_wgrad.hpp"
+#include "ac_cgrad.hpp"
 
 using namespace ac;
 
@@ -98,6 +99,7 @@ struct ac_handle : MlpModelInfo {
     int lds_bytes_set[48];
     int n_lds_fn;
     int vjp_route;   // ac_vjp_route (ac_set_vjp_route); 0 = AC_VJP_AUTO
+    int cgrad_grid;  // most workgroups of the coefficient-gradient kernels (ac_set_cgrad_grid); 0 = auto
     // last launch (profiling aid)
     char last_name[64];
     int last_grid, last_block, last_lds;
@@ -1751,6 +1753,126 @@ int ac_rollout_wgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float
     }
     // (the Jacobians are consumed: the step gradient's buffers reuse their place)
     return wgrad_step_impl(h, Xtraj, U, dt, nullptr, B * H, B, lam, Wbar, ws, st);
+}
+
+// ---- reverse mode to the coefficients of the cubic-fit and the linear model (ac_cgrad.hpp) ------------------------------------
+namespace {
+int cgrad_floats_of(const ac_handle* h) {
+    const int mk = h->dp.p.model_kind;
+    return mk == AC_MODEL_POLY ? CgradFloats<AC_MODEL_POLY>::value : (mk == AC_MODEL_LINEAR ? CgradFloats<AC_MODEL_LINEAR>::value : 0);
+}
+// why the coefficient gradient cannot run on this handle (nullptr: it can); sets *code
+const char* cgrad_refusal(const ac_handle* h, int* code) {
+    *code = AC_ERR_UNSUPPORTED;
+    if (!cgrad_floats_of(h)) return "coefficient gradients exist for the cubic-fit (poly) and the linear model only";
+    if (model_ready(h) != AC_OK) { *code = AC_ERR_NO_MODEL; return "no coefficients installed: call ac_set_poly / ac_set_linear first"; }
+    if (h->dp.p.substeps > kCgradMaxSubsteps)
+        return "coefficient gradients: at most 30 RK4 sub-steps (240 + 13 sub-steps <= 640 words of LDS per lane)";
+    return nullptr;
+}
+int cgrad_lds_bytes(const ac_handle* h) {
+    return cgrad_lane_words(cgrad_floats_of(h), h->dp.p.substeps) * kVjpBlock * (int)sizeof(float);
+}
+// Workgroups of a launch over `units` lanes: one per tile of 64 up to the handle's cap — the CU count read at creation times
+// the workgroups whose LDS fits one CU (at most 8), or ac_set_cgrad_grid's value.  Never the runtime's occupancy: the same
+// inputs on the same handle give the same partials.
+int cgrad_grid_of(const ac_handle* h, long units) {
+    const long tiles = (units + kVjpBlock - 1) / kVjpBlock;
+    long cap = h->cgrad_grid;
+    if (cap <= 0) {
+        const long per_cu = std::max(1, std::min(8, 160 * 1024 / cgrad_lds_bytes(h)));
+        cap = (h->num_cus > 0 ? h->num_cus : 256) * per_cu;
+    }
+    return (int)std::max<long>(1, std::min(tiles, cap));
+}
+int cgrad_finish(ac_handle* h, hipStream_t st, const char* name, int grid, int lds, const float* partial, float* Thetabar) {
+    note_launch(h, name, grid, kVjpBlock, lds);
+    AC_HIP(hipGetLastError());
+    const int F = cgrad_floats_of(h);
+    hipLaunchKernelGGL(k_wgrad_reduce, (F + kBlock - 1) / kBlock, kBlock, 0, st, partial, grid, F, Thetabar);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+}  // namespace
+
+int ac_coef_grad_floats(const ac_handle* h, size_t* floats) {
+    if (!h || !floats) return AC_ERR_BAD_ARG;
+    g_err[0] = 0;
+    const int F = cgrad_floats_of(h);
+    if (!F) return fail(AC_ERR_UNSUPPORTED, "coefficient gradients exist for the cubic-fit (poly) and the linear model only");
+    *floats = (size_t)F;
+    return AC_OK;
+}
+
+int ac_set_cgrad_grid(ac_handle* h, int max_workgroups) {
+    if (!h || max_workgroups < 0) return AC_ERR_BAD_ARG;
+    h->cgrad_grid = max_workgroups;
+    return AC_OK;
+}
+
+int ac_cgrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats) {
+    if (!h || !floats || n_or_B < 0 || H < 0 || which < AC_CGRAD_STEP || which > AC_CGRAD_ROLLOUT) return AC_ERR_BAD_ARG;
+    g_err[0] = 0;
+    int code;
+    if (const char* why = cgrad_refusal(h, &code)) return fail(code, why);
+    *floats = (size_t)cgrad_grid_of(h, n_or_B) * (size_t)cgrad_floats_of(h);
+    return AC_OK;
+}
+
+int ac_step_cgrad_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+                      float* Xbar, float* Ubar, float* dtbar, float* Thetabar, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !Thetabar || n < 0 || (n > 0 && (!X || !U || !Lam))) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = cgrad_refusal(h, &code)) return fail(code, why);
+    hipStream_t st = (hipStream_t)stream;
+    const int F = cgrad_floats_of(h);
+    if (n == 0) {
+        AC_HIP(hipMemsetAsync(Thetabar, 0, (size_t)F * sizeof(float), st));
+        return AC_OK;
+    }
+    const int grid = cgrad_grid_of(h, n), lds = cgrad_lds_bytes(h);
+    if (!ws || ws_floats < (size_t)grid * (size_t)F)
+        return fail(AC_ERR_WORKSPACE, "coefficient-gradient workspace too small: see ac_cgrad_workspace_floats");
+#define AC_CGRAD_STEP_CASE(M_)                                                                                          \
+        case M_: {                                                                                                      \
+            const int rc = set_lds_limit(h, k_step_cgrad<M_>, lds);                                                     \
+            if (rc != AC_OK) return rc;                                                                                 \
+            hipLaunchKernelGGL(k_step_cgrad<M_>, grid, kVjpBlock, lds, st, h->dp, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar, ws); \
+            break;                                                                                                      \
+        }
+    switch (h->dp.p.model_kind) { AC_CGRAD_STEP_CASE(AC_MODEL_LINEAR) default: AC_CGRAD_STEP_CASE(AC_MODEL_POLY) }
+#undef AC_CGRAD_STEP_CASE
+    return cgrad_finish(h, st, "k_step_cgrad", grid, lds, ws, Thetabar);
+}
+
+int ac_rollout_cgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
+                         float* Ubar, float* dtbar, float* Thetabar, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !Thetabar || B < 0 || H < 0 || (B > 0 && (!Xtraj || !G || (H > 0 && !U)))) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = cgrad_refusal(h, &code)) return fail(code, why);
+    hipStream_t st = (hipStream_t)stream;
+    const int F = cgrad_floats_of(h);
+    if (B == 0 || H == 0) {  // no step, no coefficient enters; X[0] = x0: the cotangent passes through
+        AC_HIP(hipMemsetAsync(Thetabar, 0, (size_t)F * sizeof(float), st));
+        if (B > 0 && X0bar) AC_HIP(hipMemcpyAsync(X0bar, G, (size_t)B * 13 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (B > 0 && dtbar) AC_HIP(hipMemsetAsync(dtbar, 0, (size_t)B * sizeof(float), st));
+        return AC_OK;
+    }
+    const int grid = cgrad_grid_of(h, B), lds = cgrad_lds_bytes(h);
+    if (!ws || ws_floats < (size_t)grid * (size_t)F)
+        return fail(AC_ERR_WORKSPACE, "coefficient-gradient workspace too small: see ac_cgrad_workspace_floats");
+#define AC_CGRAD_ROLL_CASE(M_)                                                                                          \
+        case M_: {                                                                                                      \
+            const int rc = set_lds_limit(h, k_rollout_cgrad<M_>, lds);                                                  \
+            if (rc != AC_OK) return rc;                                                                                 \
+            hipLaunchKernelGGL(k_rollout_cgrad<M_>, grid, kVjpBlock, lds, st, h->dp, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, ws); \
+            break;                                                                                                      \
+        }
+    switch (h->dp.p.model_kind) { AC_CGRAD_ROLL_CASE(AC_MODEL_LINEAR) default: AC_CGRAD_ROLL_CASE(AC_MODEL_POLY) }
+#undef AC_CGRAD_ROLL_CASE
+    return cgrad_finish(h, st, "k_rollout_cgrad", grid, lds, ws, Thetabar);
 }
 
 // ---- steady-flight trim (ac_trim.hpp) -----------------------------------------------------------------------------------------

@@ -617,6 +617,92 @@ class SixDOF(ABC):
                    "ac_rollout_wgrad_f32")
         return out
 
+    # ---- reverse mode to the coefficients of the cubic-fit / linear model (include/aircraft_hip.h, ac_*_cgrad_*) ----------
+    _CGRAD_KINDS = {"step": _lib.CGRAD_STEP, "rollout": _lib.CGRAD_ROLLOUT}
+
+    def coef_grad_floats(self):
+        """Length of the coefficient-gradient vector: 210 (poly: coef (6, 34) row-major, then intercept (6,)) or 36 (linear:
+        W (6, 6) row-major)."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_coef_grad_floats(self._handle, C.byref(need)), "ac_coef_grad_floats")
+        return int(need.value)
+
+    def set_coef_grad_grid(self, max_workgroups=0):
+        """Cap the workgroups of the coefficient-gradient kernels (0: the handle's own choice).  The partial sums, and with them
+        the last bits of the result, follow the grid: size the workspace after this call."""
+        lib = self._sync()
+        _lib.check(lib.ac_set_cgrad_grid(self._handle, int(max_workgroups)), "ac_set_cgrad_grid")
+
+    def coef_grad_workspace(self, kind, n, H=0):
+        """Device workspace of the coefficient-gradient call `kind` ("step", "rollout" with n = B).  Allocate it before
+        capturing a graph and pass it as `ws=`."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_cgrad_workspace_floats(self._handle, self._CGRAD_KINDS[kind], int(n), int(H), C.byref(need)),
+                   "ac_cgrad_workspace_floats")
+        return _torch().empty(max(int(need.value), 1), device=self._device_obj(), dtype=_torch().float32)
+
+    def step_coef_grad(self, x, u, dt, lam, ws=None, out=None, need=(True, True, True)):
+        """Gradient of sum(lam * F(x, u, dt)) over the coefficients of the cubic-fit or linear model, and in the same sweep the
+        per-unit (x_bar, u_bar, dt_bar) of step_vjp: -> (theta_bar (coef_grad_floats(),), x_bar, u_bar, dt_bar), device
+        tensors.  need = (x, u, dt): an output that is not needed is not written and comes back as None."""
+        torch = _torch()
+        X, U, L, n = self._wgrad_units(x, u, lam)
+        if ws is None:
+            ws = self.coef_grad_workspace("step", n)
+        lib = self._sync()
+        dts, dtp, keep = self._dt_args(dt, n)
+        if out is None:
+            out = torch.empty((self.coef_grad_floats(),), device=X.device, dtype=torch.float32)
+        Xb = torch.empty_like(X) if need[0] else None
+        Ub = torch.empty((_lib.NUM_CONTROLS, n), device=X.device, dtype=torch.float32) if need[1] else None
+        db = torch.empty((n,), device=X.device, dtype=torch.float32) if need[2] else None
+        ptr = [t.data_ptr() if t is not None else None for t in (Xb, Ub, db)]
+        _lib.check(lib.ac_step_cgrad_f32(self._handle, X.data_ptr(), U.data_ptr(), dts, dtp, n, L.data_ptr(), ptr[0], ptr[1],
+                                         ptr[2], out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "ac_step_cgrad_f32")
+        del keep
+        return out, Xb, (Ub[: self.num_controls] if Ub is not None else None), db
+
+    def rollout_coef_grad(self, X, U, dt, G, ws=None, out=None, need=(True, True, True)):
+        """Gradient of sum(G * X) over the coefficients of the cubic-fit or linear model, X (H+1, 13, B) the trajectory rollout()
+        returned for (x0, U, dt), and in the same sweep the outputs of rollout_vjp:
+        -> (theta_bar, x0_bar (13, B), U_bar (H, num_controls, B), dt_bar (B,)); need = (x0, U, dt) as in step_coef_grad."""
+        torch = _torch()
+        dev = self._device_obj()
+
+        def t3(a, name, rows):
+            t = torch.as_tensor(np.asarray(a, dtype=np.float32) if not isinstance(a, torch.Tensor) else a)
+            if t.dim() != 3 or t.shape[1] not in rows:
+                raise ValueError(f"{name}: expected (., {rows[0]}, B), got {tuple(t.shape)}")
+            return t.to(device=dev, dtype=torch.float32)
+
+        Xt = t3(X, "X", (self.num_states,)).contiguous()
+        Gt = t3(G, "G", (self.num_states,)).contiguous()
+        Hp1, _, B = Xt.shape
+        H = Hp1 - 1
+        Ut = t3(U, "U", (self.num_controls, _lib.NUM_CONTROLS)) if H > 0 else torch.zeros((0, _lib.NUM_CONTROLS, B), device=dev)
+        if Gt.shape != Xt.shape or Ut.shape[0] != H or Ut.shape[2] != B:
+            raise ValueError(f"X {tuple(Xt.shape)}, U {tuple(Ut.shape)} and G {tuple(Gt.shape)} do not describe one rollout")
+        if Ut.shape[1] < _lib.NUM_CONTROLS:
+            Ut = torch.cat([Ut, torch.zeros((H, _lib.NUM_CONTROLS - Ut.shape[1], B), device=dev)], dim=1)
+        Ut = Ut.contiguous()
+        if np.ndim(dt) > 0 or (isinstance(dt, torch.Tensor) and dt.numel() != 1):
+            raise ValueError("rollout_coef_grad: dt must be a scalar (as in rollout)")
+        if ws is None:
+            ws = self.coef_grad_workspace("rollout", B, H)
+        lib = self._sync()
+        if out is None:
+            out = torch.empty((self.coef_grad_floats(),), device=dev, dtype=torch.float32)
+        X0b = torch.empty((self.num_states, B), device=dev, dtype=torch.float32) if need[0] else None
+        Ub = torch.empty((H, _lib.NUM_CONTROLS, B), device=dev, dtype=torch.float32) if need[1] else None
+        db = torch.empty((B,), device=dev, dtype=torch.float32) if need[2] else None
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in (X0b, Ub, db)]
+        _lib.check(lib.ac_rollout_cgrad_f32(self._handle, Xt.data_ptr(), Ut.data_ptr() if H else None, C.c_float(float(dt)), B, H,
+                                            Gt.data_ptr(), ptr[0], ptr[1], ptr[2], out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            self._stream()), "ac_rollout_cgrad_f32")
+        return out, X0b, (Ub[:, : self.num_controls] if Ub is not None else None), db
+
     # ---- getters (reference dynamics/base.py:147-278, aircraft.py:255-330) ------------------------
     def _aero(self, x, u):
         lib = self._sync()

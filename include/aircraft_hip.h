@@ -453,6 +453,33 @@ int ac_step_wgrad_f32(ac_handle* h, const float* X, const float* U, float dt, co
 int ac_rollout_wgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* Wbar,
                          float* ws, size_t ws_floats, void* stream);
 
+/* ---- Reverse mode to the COEFFICIENTS of the cubic-fit and the linear model ----------------------------------
+ * The gradient of  sum over units of Lam . F(x, u, dt; theta)  (step) or  sum over nodes of G_k . X_k  (rollout) over the model's
+ * own parameters, in the order they were installed:
+ *   poly    theta = coef [6][34] then intercept [6] (ac_set_poly): 210 floats
+ *   linear  theta = W [6][6] (ac_set_linear; the last column is the bias): 36 floats
+ * One fused reverse sweep per call (k_step_cgrad: one lane per unit; k_rollout_cgrad: one lane per instance, as
+ * ac_rollout_vjp_f32): it also writes Xbar / Ubar / dtbar (X0bar / Ubar / dtbar) where those pointers are not NULL — the
+ * values of ac_step_vjp_f32 / ac_rollout_vjp_f32 on the fused route — so a backward pass that needs the state, control, dt
+ * and coefficient gradients is one launch.  Thetabar [ac_coef_grad_floats] is overwritten.  Sub-steps: supported up to 30
+ * (above: AC_ERR_UNSUPPORTED); per-unit dt: accepted by the step.  The default model, the quadrotor and the MLP surrogate
+ * (see ac_step_wgrad_f32 for its weights) return AC_ERR_UNSUPPORTED.
+ * Accumulation without atomics, in a fixed order: per-lane accumulators in LDS, one partial per workgroup in the workspace,
+ * the partials added in workgroup order.  The number of workgroups follows from the handle (CU count read by ac_create) and
+ * the problem size alone; ac_set_cgrad_grid caps it (0 = auto; for tests and A/B runs).  The same inputs on the same handle and
+ * grid give the same bits, eager or under graph replay.
+ * ws / ws_floats: caller-owned device scratch of at least ac_cgrad_workspace_floats(h, which, n or B, H) floats (for the grid
+ * in force at the call), else AC_ERR_WORKSPACE.  Asynchronous on `stream`, no allocation, no synchronisation,
+ * hipGraph-capturable. */
+typedef enum ac_cgrad_which { AC_CGRAD_STEP = 0, AC_CGRAD_ROLLOUT = 1 } ac_cgrad_which;
+int ac_coef_grad_floats(const ac_handle* h, size_t* floats);
+int ac_cgrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats);
+int ac_set_cgrad_grid(ac_handle* h, int max_workgroups);
+int ac_step_cgrad_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+                      float* Xbar, float* Ubar, float* dtbar, float* Thetabar, float* ws, size_t ws_floats, void* stream);
+int ac_rollout_cgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
+                         float* Ubar, float* dtbar, float* Thetabar, float* ws, size_t ws_floats, void* stream);
+
 /* ---- steady-flight trim (fixed-wing models) ------------------------------------------------------------------
  * Per instance, find z = (alpha, theta, phi [rad], aileron, elevator [deg], rudder [deg] | beta [rad]) such that the flight
  * given by target (p, V, psi, turn rate psid about NED down, and beta or rudder) is steady:
