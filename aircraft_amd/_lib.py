@@ -21,6 +21,7 @@ HIDDEN_ROUTES = {"auto": 0, "bf16": 1, "f16": 2}      # ac_hidden_route
 VJP_STEP, VJP_ROLLOUT, VJP_DERIVATIVE = 0, 1, 2       # ac_vjp_which
 WGRAD_SEEDS, WGRAD_STEP, WGRAD_ROLLOUT = 0, 1, 2      # ac_wgrad_which
 CGRAD_STEP, CGRAD_ROLLOUT = 0, 1                      # ac_cgrad_which
+AIRFRAME_GRAD_FLOATS = 22                             # AC_AIRFRAME_GRAD_FLOATS: mass, inertia[9], inertia_inv[9], com[3]
 TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac_trim_f32 status per instance
 NUM_STATES = 13
 NUM_CONTROLS = 7
@@ -151,6 +152,10 @@ PROTOTYPES = {
     "ac_set_cgrad_grid": (C.c_int, [_VP, C.c_int]),
     "ac_step_cgrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_rollout_cgrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
+                                       _VP]),
+    "ac_agrad_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_step_agrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_rollout_agrad_f32": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
                                        _VP]),
     "ac_trim_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_trim_f32": (C.c_int, [_VP, C.POINTER(TrimOpts), _VP, _VP, _VP, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,

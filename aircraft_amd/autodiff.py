@@ -26,13 +26,20 @@ any number of RK4 sub-steps, and the backward pass is one fused sweep (ac_step_c
 the state, control, dt and coefficient gradients together:
 
     params = autodiff.CoefficientParameters(ac)  # coef (6, 34) and intercept (6,), or W (6, 6)
+
+With the default, the linear or the cubic-fit model it reaches the airframe's mass properties: one fused
+sweep (ac_step_agrad_f32 / ac_rollout_agrad_f32) yields the gradient over the 22 floats the kernels read, and autograd carries
+it back to the eight physical numbers:
+
+    frame = autodiff.AirframeParameters(ac)      # mass (), inertia (4,) = (Ixx, Iyy, Izz, Ixz), com (3,)
+    X = autodiff.rollout(ac, x0, U, dt, params=frame)          # or params=(CoefficientParameters(ac), frame)
 """
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["step", "rollout", "state_derivative", "MlpParameters", "CoefficientParameters"]
+__all__ = ["step", "rollout", "state_derivative", "MlpParameters", "CoefficientParameters", "AirframeParameters"]
 
 
 class MlpParameters(torch.nn.Module):
@@ -154,17 +161,94 @@ class CoefficientParameters(torch.nn.Module):
             self.sync()
 
 
+class AirframeParameters(torch.nn.Module):
+    """The mass properties of a fixed-wing aircraft as float32 torch Parameters, copied from the aircraft: `mass` (),
+    `inertia` (4,) = (Ixx, Iyy, Izz, Ixz) about the reference point, `com` (3,).  Passed as `params=` to `step` / `rollout`
+    (alone, or as the second entry of a tuple after a CoefficientParameters), a loss back-propagates into their `.grad`.
+
+    The kernels read 22 derived floats (mass, inertia about the centre of mass, its inverse, com) and their gradient kernels
+    differentiate those as independent numbers; `derived()` restates the derivation in torch, so autograd carries the raw
+    gradient back to the eight physical numbers.  S, b, c and rudder_moment_arm are not parameters here."""
+
+    def __init__(self, ac):
+        super().__init__()
+        kind = getattr(ac, "model_kind", None)
+        if kind not in ("default", "linear", "poly") or not all(hasattr(ac, k) for k in ("Ixx", "Iyy", "Izz", "Ixz", "com")):
+            raise ValueError("AirframeParameters: airframe gradients exist for a fixed-wing aircraft with the default, the linear "
+                             f"or the cubic-fit model, not for {'the MLP surrogate' if kind == 'nn' else 'this model'} "
+                             f"({type(ac).__name__}, model {kind!r})")
+        self._ac = ac
+        self.mass = torch.nn.Parameter(torch.tensor(float(ac.mass), dtype=torch.float32))
+        self.inertia = torch.nn.Parameter(torch.tensor([float(ac.Ixx), float(ac.Iyy), float(ac.Izz), float(ac.Ixz)],
+                                                       dtype=torch.float32))
+        self.com = torch.nn.Parameter(torch.tensor([float(c) for c in ac.com], dtype=torch.float32))
+        # the aircraft holds its own float64 numbers, not their float32 rounding, until the first sync(): never "installed"
+        self._installed = None
+
+    def _versions(self):
+        return tuple((id(p), p._version) for p in self.parameters())
+
+    def derived(self):
+        """The 22 floats of ac_params that enter f, in the order of the airframe-gradient vector (AC_AIRFRAME_GRAD_FLOATS):
+        mass, I = I0 + m K(com) row-major, I^-1 row-major, com — float64 (inertia_about_com and its inverse, restated)."""
+        m, (ixx, iyy, izz, ixz), (x, y, z) = self.mass.double(), self.inertia.double(), self.com.double()
+        o = torch.zeros((), dtype=torch.float64, device=m.device)
+        I0 = torch.stack([ixx, o, ixz, o, iyy, o, ixz, o, izz]).reshape(3, 3)
+        K = torch.stack([y * y + z * z, -x * y, -x * z, -y * x, x * x + z * z, -y * z, -z * x, -z * y, x * x + y * y]).reshape(3, 3)
+        I = I0 + m * K
+        return torch.cat([m.reshape(1), I.reshape(9), torch.linalg.inv(I).reshape(9), self.com.double()])
+
+    def sync(self):
+        """Write the current values into the aircraft's attributes (mass, Ixx, Iyy, Izz, Ixz, com); its own _sync() then sends
+        the constants (ac_set_params).  Called by `step` / `rollout` before a forward pass when a parameter changed."""
+        from .dynamics.aircraft import inertia_about_com
+        from .dynamics.base import _capturing
+        import numpy as np
+
+        if _capturing():
+            raise RuntimeError("AirframeParameters.sync(): the constants changed and ac_set_params copies to the device — not "
+                               "possible while a stream is capturing; call params.sync() before the capture")
+        m = float(self.mass.detach())
+        ixx, iyy, izz, ixz = (float(v) for v in self.inertia.detach().cpu())
+        com = self.com.detach().cpu().numpy().astype(np.float64)
+        if not (np.isfinite(m) and m > 0.0):
+            raise ValueError(f"AirframeParameters.sync(): mass must be positive, got {m}")
+        I = inertia_about_com(ixx, iyy, izz, ixz, m, com)
+        if not (np.isfinite(I).all() and np.linalg.eigvalsh(I).min() > 0.0):
+            raise ValueError("AirframeParameters.sync(): the inertia tensor about the centre of mass is not positive definite: "
+                             f"{I.tolist()}")
+        ac = self._ac
+        ac.mass, ac.Ixx, ac.Iyy, ac.Izz, ac.Ixz, ac.com = m, ixx, iyy, izz, ixz, com
+        ac._sync()
+        self._installed = self._versions()
+
+    def sync_if_changed(self):
+        if self._versions() != self._installed:
+            self.sync()
+
+
 def _theta(ac, params):
-    """-> (the flattened parameters (an autograd input), True for coefficient parameters) after making sure the aircraft runs
-    on the current values"""
+    """-> (theta, phi, coef): theta the flattened MLP or coefficient parameters, phi the airframe's derived 22-vector (autograd
+    inputs, or None), coef True where theta belongs to a CoefficientParameters — after making sure the aircraft runs on the
+    current values"""
     if params is None:
-        return None, False
-    if not isinstance(params, (MlpParameters, CoefficientParameters)):
-        raise TypeError(f"params: expected an MlpParameters or a CoefficientParameters, got {type(params).__name__}")
-    if params._ac is not ac:
-        raise ValueError(f"params: this {type(params).__name__} was built from another aircraft")
-    params.sync_if_changed()
-    return params.flat(), isinstance(params, CoefficientParameters)
+        return None, None, False
+    parts = params if isinstance(params, tuple) else (params,)
+    pair = len(parts) == 2 and isinstance(parts[0], CoefficientParameters) and isinstance(parts[1], AirframeParameters)
+    if not pair and (isinstance(params, tuple) or not isinstance(params, (MlpParameters, CoefficientParameters, AirframeParameters))):
+        raise TypeError("params: expected an MlpParameters, a CoefficientParameters, an AirframeParameters or a tuple "
+                        f"(CoefficientParameters, AirframeParameters), got {type(params).__name__}"
+                        + (f" of ({', '.join(type(q).__name__ for q in parts)})" if isinstance(params, tuple) else ""))
+    theta = phi = None
+    for q in parts:
+        if q._ac is not ac:
+            raise ValueError(f"params: this {type(q).__name__} was built from another aircraft")
+        q.sync_if_changed()
+        if isinstance(q, AirframeParameters):
+            phi = q.derived()
+        else:
+            theta = q.flat()
+    return theta, phi, isinstance(parts[0], CoefficientParameters)
 
 
 def _tensor(a, name):
@@ -212,54 +296,70 @@ def _dt_grad(gdt, dt_t):
 
 class _Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, u, dt_t, theta, ac, dt_val, coef):
+    def forward(ctx, x, u, dt_t, theta, phi, ac, dt_val, coef):
         ctx.ac, ctx.dt_val, ctx.coef = ac, dt_val, coef
-        ctx.save_for_backward(x, u, dt_t, theta)
+        ctx.save_for_backward(x, u, dt_t, theta, phi)
         y = ac.state_update(x.detach(), u.detach(), dt_val)
         return y.to(device=x.device, dtype=x.dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        x, u, dt_t, theta = ctx.saved_tensors
-        need_x, need_u, need_dt, need_w = ctx.needs_input_grad[:4]
-        xb = ub = db = wb = None
+        x, u, dt_t, theta, phi = ctx.saved_tensors
+        need_x, need_u, need_dt, need_w, need_a = ctx.needs_input_grad[:5]
+        xb = ub = db = wb = ab = None
         if need_w and ctx.coef:  # ONE fused sweep: the coefficient gradient and whichever of x, u, dt are needed
             wb, xb, ub, db = ctx.ac.step_coef_grad(x.detach(), u.detach(), ctx.dt_val, gy.contiguous(),
                                                    need=(need_x, need_u, need_dt))
             if x.dim() == 1:
                 xb, ub, db = (None if t is None else t[..., 0] for t in (xb, ub, db))
             wb = wb.to(device=theta.device, dtype=theta.dtype)
+            if need_a:  # (a second sweep for the airframe alone: its state outputs stay NULL)
+                ab = ctx.ac.step_airframe_grad(x.detach(), u.detach(), ctx.dt_val, gy.contiguous(), need=(False, False, False))[0]
+        elif need_a:  # ONE fused sweep: the airframe gradient and whichever of x, u, dt are needed
+            ab, xb, ub, db = ctx.ac.step_airframe_grad(x.detach(), u.detach(), ctx.dt_val, gy.contiguous(),
+                                                       need=(need_x, need_u, need_dt))
+            if x.dim() == 1:
+                xb, ub, db = (None if t is None else t[..., 0] for t in (xb, ub, db))
         else:
             if need_x or need_u or need_dt:
                 xb, ub, db = ctx.ac.step_vjp(x.detach(), u.detach(), ctx.dt_val, gy.contiguous())
             if need_w:
                 wb = ctx.ac.step_wgrad(x.detach(), u.detach(), ctx.dt_val, gy.contiguous()).to(device=theta.device, dtype=theta.dtype)
+        if ab is not None:
+            ab = ab.to(device=phi.device, dtype=phi.dtype)
         return (_grad_like(xb, x) if need_x else None, _grad_like(ub, u) if need_u else None,
-                _dt_grad(db, dt_t) if need_dt else None, wb, None, None, None)
+                _dt_grad(db, dt_t) if need_dt else None, wb, ab, None, None, None)
 
 
 class _Rollout(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x0, U, dt_t, theta, ac, dt_val, coef):
+    def forward(ctx, x0, U, dt_t, theta, phi, ac, dt_val, coef):
         ctx.ac, ctx.dt_val, ctx.coef = ac, dt_val, coef
         X = ac.rollout(x0.detach(), U.detach(), dt_val)  # float32 on the handle's device: saved as the kernels read it
-        ctx.save_for_backward(x0, U, X, dt_t, theta)
+        ctx.save_for_backward(x0, U, X, dt_t, theta, phi)
         return X.to(device=x0.device, dtype=x0.dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gX):
-        x0, U, X, dt_t, theta = ctx.saved_tensors
-        need_x, need_u, need_dt, need_w = ctx.needs_input_grad[:4]
+        x0, U, X, dt_t, theta, phi = ctx.saved_tensors
+        need_x, need_u, need_dt, need_w, need_a = ctx.needs_input_grad[:5]
         vec = x0.dim() == 1
         Xs, Us, G = (X, U, gX) if not vec else (X.unsqueeze(-1), U.unsqueeze(-1), gX.unsqueeze(-1))
-        x0b = ub = db = wb = None
+        x0b = ub = db = wb = ab = None
         if need_w and ctx.coef:  # ONE fused sweep (see _Step.backward)
             wb, x0b, ub, db = ctx.ac.rollout_coef_grad(Xs, Us.detach(), ctx.dt_val, G.contiguous(), need=(need_x, need_u, need_dt))
             if vec:
                 x0b, ub = (None if t is None else t[..., 0] for t in (x0b, ub))
             wb = wb.to(device=theta.device, dtype=theta.dtype)
+            if need_a:
+                ab = ctx.ac.rollout_airframe_grad(Xs, Us.detach(), ctx.dt_val, G.contiguous(), need=(False, False, False))[0]
+        elif need_a:
+            ab, x0b, ub, db = ctx.ac.rollout_airframe_grad(Xs, Us.detach(), ctx.dt_val, G.contiguous(),
+                                                           need=(need_x, need_u, need_dt))
+            if vec:
+                x0b, ub = (None if t is None else t[..., 0] for t in (x0b, ub))
         else:
             if need_x or need_u or need_dt:
                 x0b, ub, db = ctx.ac.rollout_vjp(Xs, Us.detach(), ctx.dt_val, G.contiguous())
@@ -267,8 +367,10 @@ class _Rollout(torch.autograd.Function):
                     x0b, ub, db = x0b[..., 0], ub[..., 0], db[0:1]
             if need_w:
                 wb = ctx.ac.rollout_wgrad(Xs, Us.detach(), ctx.dt_val, G.contiguous()).to(device=theta.device, dtype=theta.dtype)
+        if ab is not None:
+            ab = ab.to(device=phi.device, dtype=phi.dtype)
         return (_grad_like(x0b, x0) if need_x else None, _grad_like(ub, U) if need_u else None,
-                _dt_grad(db, dt_t) if need_dt else None, wb, None, None, None)
+                _dt_grad(db, dt_t) if need_dt else None, wb, ab, None, None, None)
 
 
 class _Derivative(torch.autograd.Function):
@@ -292,29 +394,29 @@ class _Derivative(torch.autograd.Function):
 
 def step(ac, x, u, dt, params=None):
     """x+ = F(x, u, dt) (SixDOF.state_update) with a grad_fn.  x (13, n) or (13,), u (num_controls, n), dt a number, a 0-d
-    tensor or a per-unit tensor (n,).  params: an MlpParameters or a CoefficientParameters of `ac` — the loss then reaches the
-    surrogate's weights, or the coefficients of the cubic-fit / linear model, too."""
+    tensor or a per-unit tensor (n,).  params: an MlpParameters, a CoefficientParameters, an AirframeParameters or a tuple
+    (CoefficientParameters, AirframeParameters) of `ac` — the loss then reaches the surrogate's weights, the coefficients of the
+    cubic-fit / linear model, or mass, inertia and centre of mass, too."""
     _tensor(x, "x"); _tensor(u, "u")
     _check_states(ac, x, ac.num_states, "x")
     if u.dim() != x.dim() or u.shape[0] not in (ac.num_controls, 7) or u.shape[1:] != x.shape[1:]:
         raise ValueError(f"u: expected ({ac.num_controls},{' n' if x.dim() == 2 else ''}) matching x, got {tuple(u.shape)}")
     n = x.shape[1] if x.dim() == 2 else 1
     dt_val, dt_t = _dt(dt, n, per_unit_ok=True)
-    theta, coef = _theta(ac, params)
-    return _Step.apply(x, u, dt_t, theta, ac, dt_val, coef)
+    theta, phi, coef = _theta(ac, params)
+    return _Step.apply(x, u, dt_t, theta, phi, ac, dt_val, coef)
 
 
 def rollout(ac, x0, U, dt, params=None):
     """X[k+1] = F(X[k], U[k], dt) (SixDOF.rollout) with a grad_fn.  x0 (13, B) or (13,), U (H, num_controls, B) or
-    (H, num_controls), dt a number or a 0-d tensor -> X (H+1, 13, B).  params: an MlpParameters or a CoefficientParameters of
-    `ac` (see `step`)."""
+    (H, num_controls), dt a number or a 0-d tensor -> X (H+1, 13, B).  params: as in `step`."""
     _tensor(x0, "x0"); _tensor(U, "U")
     _check_states(ac, x0, ac.num_states, "x0")
     if U.dim() != x0.dim() + 1 or U.shape[1] not in (ac.num_controls, 7) or U.shape[2:] != x0.shape[1:]:
         raise ValueError(f"U: expected (H, {ac.num_controls}, B) matching x0, got {tuple(U.shape)}")
     dt_val, dt_t = _dt(dt, 1, per_unit_ok=False)
-    theta, coef = _theta(ac, params)
-    return _Rollout.apply(x0, U, dt_t, theta, ac, dt_val, coef)
+    theta, phi, coef = _theta(ac, params)
+    return _Rollout.apply(x0, U, dt_t, theta, phi, ac, dt_val, coef)
 
 
 def state_derivative(ac, x, u):

@@ -156,6 +156,11 @@ template <int MODEL> struct AdjAnalyticCoeffs : AnalyticCoeffs<MODEL> {
     }
 };
 
+// A provider that declares `static constexpr bool kRecordsAirframe = true` is handed, once per call of f_vjp, the factors of
+// the cotangents of mass, inertia, inertia_inv and com (record_airframe, ac_agrad.hpp).  Every other provider: no code.
+template <class C, class = void> struct RecordsAirframe { static constexpr bool value = false; };
+template <class C> struct RecordsAirframe<C, decltype((void)C::kRecordsAirframe)> { static constexpr bool value = C::kRecordsAirframe; };
+
 // ---- x_dot = f(x, u) and the adjoint of its Jacobians applied to w ---------------------------------------------------------
 // xd: f itself (recomputed here); xb [13] += (df/dx)' w, ub [7] += (df/du)' w.  (p never enters f: xb[0..2] untouched.)
 template <class T, class Coeffs>
@@ -248,6 +253,9 @@ AC_DI void f_vjp(const DevParams& P, Coeffs& coeffs, const T x[13], const T u[7]
         cross3(yb, om, c2);
 #pragma unroll
         for (int j = 0; j < 3; ++j) xb[10 + j] = xb[10 + j] + c1[j] + (I[j] * c2[0] + I[3 + j] * c2[1] + I[6 + j] * c2[2]);
+        // (c2 is the cotangent of I omega, Mb that of M; the quadrotor's airframe stays unrecorded)
+        if constexpr (RecordsAirframe<Coeffs>::value && Coeffs::kModel != AC_MODEL_QUAD)
+            coeffs.record_airframe(P, Fn, w, om, c2, rhs, o.F, Mb);
     }
     // v_dot = Fn / m + g,  Fn = q (F, 0) q^-1
     T Fb[3];

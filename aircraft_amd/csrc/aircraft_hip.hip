@@ -25,6 +25,7 @@
 #include "ac_trim.hpp"
 #include "ac_wgrad.hpp"
 #include "ac_cgrad.hpp"
+#include "ac_agrad.hpp"
 
 using namespace ac;
 
@@ -1776,22 +1777,26 @@ int cgrad_lds_bytes(const ac_handle* h) {
 // Workgroups of a launch over `units` lanes: one per tile of 64 up to the handle's cap — the CU count read at creation times
 // the workgroups whose LDS fits one CU (at most 8), or ac_set_cgrad_grid's value.  Never the runtime's occupancy: the same
 // inputs on the same handle give the same partials.
-int cgrad_grid_of(const ac_handle* h, long units) {
+int grad_grid_of(const ac_handle* h, long units, int lds_bytes) {
     const long tiles = (units + kVjpBlock - 1) / kVjpBlock;
     long cap = h->cgrad_grid;
     if (cap <= 0) {
-        const long per_cu = std::max(1, std::min(8, 160 * 1024 / cgrad_lds_bytes(h)));
+        const long per_cu = std::max(1, std::min(8, 160 * 1024 / lds_bytes));
         cap = (h->num_cus > 0 ? h->num_cus : 256) * per_cu;
     }
     return (int)std::max<long>(1, std::min(tiles, cap));
 }
-int cgrad_finish(ac_handle* h, hipStream_t st, const char* name, int grid, int lds, const float* partial, float* Thetabar) {
+int cgrad_grid_of(const ac_handle* h, long units) { return grad_grid_of(h, units, cgrad_lds_bytes(h)); }
+// after the sweep `name`: the F floats of its `grid` partials added in workgroup order
+int grad_finish(ac_handle* h, hipStream_t st, const char* name, int grid, int lds, const float* partial, int F, float* out) {
     note_launch(h, name, grid, kVjpBlock, lds);
     AC_HIP(hipGetLastError());
-    const int F = cgrad_floats_of(h);
-    hipLaunchKernelGGL(k_wgrad_reduce, (F + kBlock - 1) / kBlock, kBlock, 0, st, partial, grid, F, Thetabar);
+    hipLaunchKernelGGL(k_wgrad_reduce, (F + kBlock - 1) / kBlock, kBlock, 0, st, partial, grid, F, out);
     AC_HIP(hipGetLastError());
     return AC_OK;
+}
+int cgrad_finish(ac_handle* h, hipStream_t st, const char* name, int grid, int lds, const float* partial, float* Thetabar) {
+    return grad_finish(h, st, name, grid, lds, partial, cgrad_floats_of(h), Thetabar);
 }
 }  // namespace
 
@@ -1873,6 +1878,87 @@ int ac_rollout_cgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float
     switch (h->dp.p.model_kind) { AC_CGRAD_ROLL_CASE(AC_MODEL_LINEAR) default: AC_CGRAD_ROLL_CASE(AC_MODEL_POLY) }
 #undef AC_CGRAD_ROLL_CASE
     return cgrad_finish(h, st, "k_rollout_cgrad", grid, lds, ws, Thetabar);
+}
+
+// ---- reverse mode to mass, inertia, inertia_inv and com (ac_agrad.hpp) -----------------------------------------------------------
+namespace {
+// why the airframe gradient cannot run on this handle (nullptr: it can); sets *code
+const char* agrad_refusal(const ac_handle* h, int* code) {
+    *code = AC_ERR_UNSUPPORTED;
+    const int mk = h->dp.p.model_kind;
+    if (mk == AC_MODEL_NN) return "airframe gradients: the MLP surrogate has no fused reverse sweep (default, linear and cubic-fit models only)";
+    if (mk == AC_MODEL_QUAD) return "airframe gradients: the quadrotor's sweep is not recorded (default, linear and cubic-fit models only)";
+    if (model_ready(h) != AC_OK) { *code = AC_ERR_NO_MODEL; return "no coefficients installed: call ac_set_poly / ac_set_linear first"; }
+    if (h->dp.p.substeps > kAgradMaxSubsteps) return "airframe gradients: at most 40 RK4 sub-steps (the limit of the fused reverse sweep)";
+    return nullptr;
+}
+int agrad_lds_bytes(const ac_handle* h) {
+    return cgrad_lane_words(kAgradFloats, h->dp.p.substeps) * kVjpBlock * (int)sizeof(float);
+}
+int agrad_grid_of(const ac_handle* h, long units) { return grad_grid_of(h, units, agrad_lds_bytes(h)); }
+}  // namespace
+
+int ac_agrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats) {
+    if (!h || !floats || n_or_B < 0 || H < 0 || which < AC_CGRAD_STEP || which > AC_CGRAD_ROLLOUT) return AC_ERR_BAD_ARG;
+    g_err[0] = 0;
+    int code;
+    if (const char* why = agrad_refusal(h, &code)) return fail(code, why);
+    *floats = (size_t)agrad_grid_of(h, n_or_B) * (size_t)kAgradFloats;
+    return AC_OK;
+}
+
+int ac_step_agrad_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+                      float* Xbar, float* Ubar, float* dtbar, float* Phibar, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !Phibar || n < 0 || (n > 0 && (!X || !U || !Lam))) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = agrad_refusal(h, &code)) return fail(code, why);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        AC_HIP(hipMemsetAsync(Phibar, 0, (size_t)kAgradFloats * sizeof(float), st));
+        return AC_OK;
+    }
+    const int grid = agrad_grid_of(h, n), lds = agrad_lds_bytes(h);
+    if (!ws || ws_floats < (size_t)grid * (size_t)kAgradFloats)
+        return fail(AC_ERR_WORKSPACE, "airframe-gradient workspace too small: see ac_agrad_workspace_floats");
+#define AC_AGRAD_STEP_CASE(M_)                                                                                          \
+        case M_: {                                                                                                      \
+            const int rc = set_lds_limit(h, k_step_agrad<M_>, lds);                                                     \
+            if (rc != AC_OK) return rc;                                                                                 \
+            hipLaunchKernelGGL(k_step_agrad<M_>, grid, kVjpBlock, lds, st, h->dp, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar, ws); \
+            break;                                                                                                      \
+        }
+    switch (h->dp.p.model_kind) { AC_AGRAD_STEP_CASE(AC_MODEL_LINEAR) AC_AGRAD_STEP_CASE(AC_MODEL_POLY) default: AC_AGRAD_STEP_CASE(AC_MODEL_DEFAULT) }
+#undef AC_AGRAD_STEP_CASE
+    return grad_finish(h, st, "k_step_agrad", grid, lds, ws, kAgradFloats, Phibar);
+}
+
+int ac_rollout_agrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
+                         float* Ubar, float* dtbar, float* Phibar, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !Phibar || B < 0 || H < 0 || (B > 0 && (!Xtraj || !G || (H > 0 && !U)))) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = agrad_refusal(h, &code)) return fail(code, why);
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0 || H == 0) {  // no step, no constant enters; X[0] = x0: the cotangent passes through
+        AC_HIP(hipMemsetAsync(Phibar, 0, (size_t)kAgradFloats * sizeof(float), st));
+        if (B > 0 && X0bar) AC_HIP(hipMemcpyAsync(X0bar, G, (size_t)B * 13 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (B > 0 && dtbar) AC_HIP(hipMemsetAsync(dtbar, 0, (size_t)B * sizeof(float), st));
+        return AC_OK;
+    }
+    const int grid = agrad_grid_of(h, B), lds = agrad_lds_bytes(h);
+    if (!ws || ws_floats < (size_t)grid * (size_t)kAgradFloats)
+        return fail(AC_ERR_WORKSPACE, "airframe-gradient workspace too small: see ac_agrad_workspace_floats");
+#define AC_AGRAD_ROLL_CASE(M_)                                                                                          \
+        case M_: {                                                                                                      \
+            const int rc = set_lds_limit(h, k_rollout_agrad<M_>, lds);                                                  \
+            if (rc != AC_OK) return rc;                                                                                 \
+            hipLaunchKernelGGL(k_rollout_agrad<M_>, grid, kVjpBlock, lds, st, h->dp, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, ws); \
+            break;                                                                                                      \
+        }
+    switch (h->dp.p.model_kind) { AC_AGRAD_ROLL_CASE(AC_MODEL_LINEAR) AC_AGRAD_ROLL_CASE(AC_MODEL_POLY) default: AC_AGRAD_ROLL_CASE(AC_MODEL_DEFAULT) }
+#undef AC_AGRAD_ROLL_CASE
+    return grad_finish(h, st, "k_rollout_agrad", grid, lds, ws, kAgradFloats, Phibar);
 }
 
 // ---- steady-flight trim (ac_trim.hpp) -----------------------------------------------------------------------------------------

@@ -643,31 +643,29 @@ class SixDOF(ABC):
                    "ac_cgrad_workspace_floats")
         return _torch().empty(max(int(need.value), 1), device=self._device_obj(), dtype=_torch().float32)
 
-    def step_coef_grad(self, x, u, dt, lam, ws=None, out=None, need=(True, True, True)):
-        """Gradient of sum(lam * F(x, u, dt)) over the coefficients of the cubic-fit or linear model, and in the same sweep the
-        per-unit (x_bar, u_bar, dt_bar) of step_vjp: -> (theta_bar (coef_grad_floats(),), x_bar, u_bar, dt_bar), device
-        tensors.  need = (x, u, dt): an output that is not needed is not written and comes back as None."""
+    def _step_param_grad(self, call, floats, workspace, x, u, dt, lam, ws, out, need):
+        """One recording reverse sweep over n units (ac_step_cgrad_f32, ac_step_agrad_f32): -> (parameter gradient (floats,),
+        x_bar, u_bar, dt_bar); need = (x, u, dt): an output that is not needed is not written and comes back as None."""
         torch = _torch()
         X, U, L, n = self._wgrad_units(x, u, lam)
         if ws is None:
-            ws = self.coef_grad_workspace("step", n)
+            ws = workspace("step", n)
         lib = self._sync()
         dts, dtp, keep = self._dt_args(dt, n)
         if out is None:
-            out = torch.empty((self.coef_grad_floats(),), device=X.device, dtype=torch.float32)
+            out = torch.empty((floats(),), device=X.device, dtype=torch.float32)
         Xb = torch.empty_like(X) if need[0] else None
         Ub = torch.empty((_lib.NUM_CONTROLS, n), device=X.device, dtype=torch.float32) if need[1] else None
         db = torch.empty((n,), device=X.device, dtype=torch.float32) if need[2] else None
         ptr = [t.data_ptr() if t is not None else None for t in (Xb, Ub, db)]
-        _lib.check(lib.ac_step_cgrad_f32(self._handle, X.data_ptr(), U.data_ptr(), dts, dtp, n, L.data_ptr(), ptr[0], ptr[1],
-                                         ptr[2], out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "ac_step_cgrad_f32")
+        _lib.check(getattr(lib, call)(self._handle, X.data_ptr(), U.data_ptr(), dts, dtp, n, L.data_ptr(), ptr[0], ptr[1], ptr[2],
+                                      out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), call)
         del keep
         return out, Xb, (Ub[: self.num_controls] if Ub is not None else None), db
 
-    def rollout_coef_grad(self, X, U, dt, G, ws=None, out=None, need=(True, True, True)):
-        """Gradient of sum(G * X) over the coefficients of the cubic-fit or linear model, X (H+1, 13, B) the trajectory rollout()
-        returned for (x0, U, dt), and in the same sweep the outputs of rollout_vjp:
-        -> (theta_bar, x0_bar (13, B), U_bar (H, num_controls, B), dt_bar (B,)); need = (x0, U, dt) as in step_coef_grad."""
+    def _rollout_param_grad(self, who, call, floats, workspace, X, U, dt, G, ws, out, need):
+        """The same over a saved rollout (ac_rollout_cgrad_f32, ac_rollout_agrad_f32): -> (parameter gradient, x0_bar (13, B),
+        U_bar (H, num_controls, B), dt_bar (B,))."""
         torch = _torch()
         dev = self._device_obj()
 
@@ -688,20 +686,58 @@ class SixDOF(ABC):
             Ut = torch.cat([Ut, torch.zeros((H, _lib.NUM_CONTROLS - Ut.shape[1], B), device=dev)], dim=1)
         Ut = Ut.contiguous()
         if np.ndim(dt) > 0 or (isinstance(dt, torch.Tensor) and dt.numel() != 1):
-            raise ValueError("rollout_coef_grad: dt must be a scalar (as in rollout)")
+            raise ValueError(f"{who}: dt must be a scalar (as in rollout)")
         if ws is None:
-            ws = self.coef_grad_workspace("rollout", B, H)
+            ws = workspace("rollout", B, H)
         lib = self._sync()
         if out is None:
-            out = torch.empty((self.coef_grad_floats(),), device=dev, dtype=torch.float32)
+            out = torch.empty((floats(),), device=dev, dtype=torch.float32)
         X0b = torch.empty((self.num_states, B), device=dev, dtype=torch.float32) if need[0] else None
         Ub = torch.empty((H, _lib.NUM_CONTROLS, B), device=dev, dtype=torch.float32) if need[1] else None
         db = torch.empty((B,), device=dev, dtype=torch.float32) if need[2] else None
         ptr = [t.data_ptr() if t is not None and t.numel() else None for t in (X0b, Ub, db)]
-        _lib.check(lib.ac_rollout_cgrad_f32(self._handle, Xt.data_ptr(), Ut.data_ptr() if H else None, C.c_float(float(dt)), B, H,
-                                            Gt.data_ptr(), ptr[0], ptr[1], ptr[2], out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            self._stream()), "ac_rollout_cgrad_f32")
+        _lib.check(getattr(lib, call)(self._handle, Xt.data_ptr(), Ut.data_ptr() if H else None, C.c_float(float(dt)), B, H,
+                                      Gt.data_ptr(), ptr[0], ptr[1], ptr[2], out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      self._stream()), call)
         return out, X0b, (Ub[:, : self.num_controls] if Ub is not None else None), db
+
+    def step_coef_grad(self, x, u, dt, lam, ws=None, out=None, need=(True, True, True)):
+        """Gradient of sum(lam * F(x, u, dt)) over the coefficients of the cubic-fit or linear model, and in the same sweep the
+        per-unit (x_bar, u_bar, dt_bar) of step_vjp: -> (theta_bar (coef_grad_floats(),), x_bar, u_bar, dt_bar), device
+        tensors.  need = (x, u, dt): an output that is not needed is not written and comes back as None."""
+        return self._step_param_grad("ac_step_cgrad_f32", self.coef_grad_floats, self.coef_grad_workspace, x, u, dt, lam, ws, out,
+                                     need)
+
+    def rollout_coef_grad(self, X, U, dt, G, ws=None, out=None, need=(True, True, True)):
+        """Gradient of sum(G * X) over the coefficients of the cubic-fit or linear model, X (H+1, 13, B) the trajectory rollout()
+        returned for (x0, U, dt), and in the same sweep the outputs of rollout_vjp:
+        -> (theta_bar, x0_bar (13, B), U_bar (H, num_controls, B), dt_bar (B,)); need = (x0, U, dt) as in step_coef_grad."""
+        return self._rollout_param_grad("rollout_coef_grad", "ac_rollout_cgrad_f32", self.coef_grad_floats,
+                                        self.coef_grad_workspace, X, U, dt, G, ws, out, need)
+
+    # ---- reverse mode to mass, inertia, inertia_inv and com (include/aircraft_hip.h, ac_*_agrad_*; DESIGN.md §4.11) -----------
+    def airframe_grad_workspace(self, kind, n, H=0):
+        """Device workspace of the airframe-gradient call `kind` ("step", "rollout" with n = B).  Allocate it before capturing a
+        graph and pass it as `ws=`."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_agrad_workspace_floats(self._handle, self._CGRAD_KINDS[kind], int(n), int(H), C.byref(need)),
+                   "ac_agrad_workspace_floats")
+        return _torch().empty(max(int(need.value), 1), device=self._device_obj(), dtype=_torch().float32)
+
+    def step_airframe_grad(self, x, u, dt, lam, ws=None, out=None, need=(True, True, True)):
+        """Gradient of sum(lam * F(x, u, dt)) over the 22 airframe floats the kernels read, each as an independent number —
+        mass, inertia (9, row-major), inertia_inv (9), com (3) — and in the same sweep the per-unit outputs of step_vjp:
+        -> (phi_bar (22,), x_bar, u_bar, dt_bar), device tensors; need = (x, u, dt) as in step_coef_grad.  The default, linear
+        and cubic-fit models; autodiff.AirframeParameters carries phi_bar back to mass, (Ixx, Iyy, Izz, Ixz) and com."""
+        return self._step_param_grad("ac_step_agrad_f32", lambda: _lib.AIRFRAME_GRAD_FLOATS, self.airframe_grad_workspace, x, u, dt,
+                                     lam, ws, out, need)
+
+    def rollout_airframe_grad(self, X, U, dt, G, ws=None, out=None, need=(True, True, True)):
+        """Gradient of sum(G * X) over the 22 airframe floats (see step_airframe_grad), X (H+1, 13, B) the trajectory rollout()
+        returned for (x0, U, dt): -> (phi_bar (22,), x0_bar (13, B), U_bar (H, num_controls, B), dt_bar (B,))."""
+        return self._rollout_param_grad("rollout_airframe_grad", "ac_rollout_agrad_f32", lambda: _lib.AIRFRAME_GRAD_FLOATS,
+                                        self.airframe_grad_workspace, X, U, dt, G, ws, out, need)
 
     # ---- getters (reference dynamics/base.py:147-278, aircraft.py:255-330) ------------------------
     def _aero(self, x, u):

@@ -480,6 +480,31 @@ int ac_step_cgrad_f32(ac_handle* h, const float* X, const float* U, float dt, co
 int ac_rollout_cgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
                          float* Ubar, float* dtbar, float* Thetabar, float* ws, size_t ws_floats, void* stream);
 
+/* ---- Reverse mode to the AIRFRAME CONSTANTS: mass, inertia, centre of mass ----------------------------------
+ * The gradient of  sum over units of Lam . F(x, u, dt; phi)  (step) or  sum over nodes of G_k . X_k  (rollout) over the 22
+ * floats of ac_params that enter f, in this order:
+ *   Phibar [0]       mass
+ *   Phibar [1..9]    inertia [9], row-major
+ *   Phibar [10..18]  inertia_inv [9], row-major
+ *   Phibar [19..21]  com [3]
+ * The entries of inertia and inertia_inv are differentiated as INDEPENDENT numbers, exactly as the kernels read them: that
+ * inertia is built from mass and com, that it is symmetric and that inertia_inv is its inverse is the caller's chain rule
+ * (aircraft_amd.autodiff.AirframeParameters.derived()).  com enters through M = Ma + com x F only.  S, b, c and
+ * rudder_moment_arm have no gradient here.
+ * One fused reverse sweep per call (k_step_agrad, k_rollout_agrad), the default, linear and cubic-fit models; like
+ * ac_*_cgrad_f32 it also writes Xbar / Ubar / dtbar (X0bar / Ubar / dtbar) where those pointers are not NULL, accumulates
+ * without atomics in a fixed order and takes its grid from the handle and the problem size (ac_set_cgrad_grid caps it).
+ * Phibar [AC_AIRFRAME_GRAD_FLOATS] is overwritten.  Sub-steps: up to 40, the limit of the fused VJP route (above:
+ * AC_ERR_UNSUPPORTED); per-unit dt: accepted by the step.  The MLP surrogate and the quadrotor return AC_ERR_UNSUPPORTED.
+ * ws / ws_floats: caller-owned device scratch of at least ac_agrad_workspace_floats(h, which, n or B, H) floats (which: an
+ * ac_cgrad_which), else AC_ERR_WORKSPACE.  Asynchronous on `stream`, no allocation, no synchronisation, hipGraph-capturable. */
+#define AC_AIRFRAME_GRAD_FLOATS 22
+int ac_agrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats);
+int ac_step_agrad_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+                      float* Xbar, float* Ubar, float* dtbar, float* Phibar, float* ws, size_t ws_floats, void* stream);
+int ac_rollout_agrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
+                         float* Ubar, float* dtbar, float* Phibar, float* ws, size_t ws_floats, void* stream);
+
 /* ---- steady-flight trim (fixed-wing models) ------------------------------------------------------------------
  * Per instance, find z = (alpha, theta, phi [rad], aileron, elevator [deg], rudder [deg] | beta [rad]) such that the flight
  * given by target (p, V, psi, turn rate psid about NED down, and beta or rudder) is steady:
