@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import golden
+from tests.rollout_matrix import MLP_ROW_IDS, MLP_ROWS, mlp_data
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "host_mlp", "mlp_model_host.cpp")
@@ -371,6 +372,47 @@ def test_valu_image(built):
         want[off:off + m.widths[l + 1]] = m.b[l]
         off += N
     assert off <= m.vimage.size < off + 256 and eq(m.vimage, want)
+
+
+# ---- the rollout-engine matrix ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("row", MLP_ROWS, ids=MLP_ROW_IDS)
+def test_rollout_matrix_rows_reach_the_instance_they_claim(lib, row):
+    """tests/rollout_matrix.py names one net per rollout-engine instance; the host picks the instance from wt, the number of
+    folded layers and (for the cooperative engine's weight ring) plan.n_streamed.  Pinned here, so that a change of the fold
+    or of the LDS rule cannot take an instance — the ring above all — out of tests/test_gpu_rollout_engines.py unnoticed."""
+    md = mlp_data(row)
+    m = Model(lib, md.weights, md.biases, md.act, int(row.use_mfma))
+    assert m.rc == AC_OK, m.err
+    assert (m.wt, m.n, int(m.plan["n_streamed"])) == (row.wt, row.layers, row.n_streamed)
+    assert int(m.plan["n_layers"]) == m.n and m.use_mfma == int(row.use_mfma)
+    # the dispatch of ac_rollout_f32 / ac_rollout_policy_f32, restated
+    nh = m.n - 2
+    if not row.use_mfma:
+        want = ("k_nn_rollout_tiled8", "k_nn_rollout_policy_tiled8") if m.has_vplan else ("k_nn_rollout", None)
+        assert not m.has_vplan or m.vwidth == (32 if row.wt == 2 else 64)
+    elif 1 <= nh <= 3:
+        want = ("k_nn_rollout_reg", "k_nn_rollout_policy_reg")
+    else:
+        want = ("k_nn_rollout_coop", "k_nn_rollout_policy_coop")
+    assert (row.open_kernel, row.policy_kernel) == want
+    if row.n_streamed:  # the hidden x hidden blocks stream, the edge blocks stay
+        assert list(m.plan["streamed"][:row.n_streamed]) == list(range(1, m.n - 1))
+    if row.act is not None and row.act[-1]:
+        assert m.act[-1] == 1  # the tanh on the output layer survives the fold
+
+
+def test_rollout_matrix_covers_every_instance():
+    """3 x 3 register-engine instances, the three cooperative widths with and without hidden x hidden layers, an even and an
+    odd number of streamed layers, the one-layer net, both tiled widths, and the sequential vector-ALU kernel."""
+    reg = {(r.wt, r.layers - 2) for r in MLP_ROWS if r.open_kernel == "k_nn_rollout_reg"}
+    assert reg == {(wt, nh) for wt in (2, 4, 8) for nh in (1, 2, 3)}
+    coop = [r for r in MLP_ROWS if r.open_kernel == "k_nn_rollout_coop"]
+    assert {r.wt for r in coop} == {2, 4, 8} and {r.layers for r in coop} >= {1, 2, 6, 7}
+    assert sorted(r.n_streamed for r in coop if r.n_streamed) == [4, 5]  # the ring runs in these two rows only
+    assert {r.wt for r in MLP_ROWS if r.open_kernel == "k_nn_rollout_tiled8"} == {2, 4}
+    assert [r.wt for r in MLP_ROWS if r.open_kernel == "k_nn_rollout"] == [8]
+    assert any(r.hidden is not None and len(set(r.hidden)) > 1 for r in MLP_ROWS if r.wt == 8)  # ragged widths at width 128
+    assert len(set(MLP_ROW_IDS)) == len(MLP_ROWS)
 
 
 # ---- error paths ------------------------------------------------------------------------------------------------------------
