@@ -63,6 +63,12 @@ class TrimOpts(C.Structure):
     _fields_ = [("lateral", C.c_int), ("tol_v", C.c_float), ("tol_w", C.c_float), ("lo", C.c_float * 6), ("hi", C.c_float * 6)]
 
 
+class MppiOpts(C.Structure):
+    """struct ac_mppi_opts (include/aircraft_hip.h)."""
+    _fields_ = [("sigma", C.c_float * 7), ("u_min", C.c_float * 7), ("u_max", C.c_float * 7), ("lambda_", C.c_float),
+                ("seed", C.c_ulonglong), ("instance_offset", C.c_uint), ("keep_nominal", C.c_int)]
+
+
 class EnvelopePenalty(C.Structure):
     """struct ac_envelope_penalty (include/aircraft_hip.h)."""
     _fields_ = [("lo", C.c_float * 4), ("hi", C.c_float * 4), ("weight", C.c_float)]
@@ -160,6 +166,10 @@ PROTOTYPES = {
     "ac_trim_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_trim_f32": (C.c_int, [_VP, C.POINTER(TrimOpts), _VP, _VP, _VP, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
                               _VP]),
+    "ac_mppi_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_mppi_sample_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP]),
+    "ac_mppi_update_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP,
+                                     C.c_size_t, _VP]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     "ac_device_arch": (C.c_int, [C.c_char_p, C.c_size_t]),

@@ -23,6 +23,7 @@
 #include "ac_select.hpp"
 #include "ac_vjp.hpp"
 #include "ac_trim.hpp"
+#include "ac_mppi.hpp"
 #include "ac_wgrad.hpp"
 #include "ac_cgrad.hpp"
 #include "ac_agrad.hpp"
@@ -2009,6 +2010,54 @@ int ac_trim_f32(ac_handle* h, const ac_trim_opts* o, const float* target, const 
         AC_HIP(hipGetLastError());
     }
     note_launch(h, "k_trim_update", grid, kTrimBlock, 0);
+    return AC_OK;
+}
+
+// ---- MPPI: sampler and softmin update (ac_mppi.hpp, mppi_inst.hip) ---------------------------------------------------------------
+namespace {
+int mppi_check(const ac_handle* h, const ac_mppi_opts* o, int K, long B, long H) {
+    if (!h || !o || K < 1 || B < 1 || H < 1) return AC_ERR_BAD_ARG;
+    if ((long)K > 2147483647L / B) return fail(AC_ERR_BAD_ARG, "mppi: K * B exceeds 2^31 - 1");
+    if (!(o->lambda > 0.f) || !(o->lambda <= 3.4028235e38f)) return fail(AC_ERR_BAD_ARG, "mppi: lambda must be finite and > 0");
+    for (int r = 0; r < 7; ++r) {
+        if (!(o->sigma[r] >= 0.f) || !(o->sigma[r] <= 3.4028235e38f))
+            return fail(AC_ERR_BAD_ARG, "mppi: sigma must be finite and >= 0");
+        if (!(o->u_min[r] <= o->u_max[r])) return fail(AC_ERR_BAD_ARG, "mppi: u_min > u_max (or NaN)");
+    }
+    return AC_OK;
+}
+}  // namespace
+
+int ac_mppi_workspace_floats(const ac_handle* h, int K, long B, long H, size_t* floats) {
+    if (!h || !floats || K < 1 || B < 1 || H < 1 || (long)K > 2147483647L / B) return AC_ERR_BAD_ARG;
+    *floats = (size_t)K * (size_t)B;  // the normalised weights
+    return AC_OK;
+}
+
+int ac_mppi_sample_f32(ac_handle* h, const ac_mppi_opts* o, const unsigned int* it_dev, const float* Unom, const float* X0, int K,
+                       long B, long H, float* Uc, float* X0c, void* stream) {
+    AC_ENTER(h);
+    const int rc = mppi_check(h, o, K, B, H);
+    if (rc != AC_OK) return rc;
+    if (!Unom || !Uc) return AC_ERR_BAD_ARG;
+    if ((X0 == nullptr) != (X0c == nullptr)) return fail(AC_ERR_BAD_ARG, "mppi: X0 and X0c go together");
+    int grid = 0;
+    AC_HIP(mppi_launch_sample(*o, it_dev, Unom, X0, K, B, H, Uc, X0c, (hipStream_t)stream, &grid));
+    note_launch(h, "k_mppi_sample", grid, kMppiBlock, 0);
+    return AC_OK;
+}
+
+int ac_mppi_update_f32(ac_handle* h, const ac_mppi_opts* o, unsigned int* it_dev, const float* J, const float* Uc, const float* Unom,
+                       int K, long B, long H, float* Unew, float* stats, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    const int rc = mppi_check(h, o, K, B, H);
+    if (rc != AC_OK) return rc;
+    if (!J || !Uc || !Unom || !Unew || !stats) return AC_ERR_BAD_ARG;
+    if (!ws || ws_floats < (size_t)K * (size_t)B)
+        return fail(AC_ERR_WORKSPACE, "mppi workspace too small: see ac_mppi_workspace_floats");
+    int grid = 0;
+    AC_HIP(mppi_launch_update(*o, it_dev, J, Uc, Unom, K, B, H, Unew, stats, ws, (hipStream_t)stream, &grid));
+    note_launch(h, "k_mppi_blend", grid, kMppiBlock, 0);
     return AC_OK;
 }
 

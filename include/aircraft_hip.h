@@ -538,8 +538,50 @@ int ac_trim_f32(ac_handle* h, const ac_trim_opts* o,
                 float* X /* [13][n] */, float* U /* [7][n] */, float* Z /* [6][n] */, float* R /* [6][n] */, int* status /* [n] */,
                 float* ws, size_t ws_floats, void* stream);
 
+/* ---- sampling-based MPC: MPPI (every model kind) ---------------------------------------------------------------
+ * One MPPI iteration draws K perturbed control sequences per instance (ac_mppi_sample_f32), rolls them out and costs them with
+ * the calls above (candidate k of instance b is column o = k*B + b, the layout ac_rollout_policy_f32 writes), and blends them by
+ * exp(-cost / lambda) (ac_mppi_update_f32).  Neither call looks at the force model.
+ * Noise: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) with
+ *     key = (seed & 0xffffffff, seed >> 32),  counter = (k, g, t, 2*it + j),  g = instance_offset + b,  t the node, j in {0, 1};
+ * each word pair (xa, xb) gives two normals: u1 = ((xa >> 8) + 1) 2^-24, u2 = (xb >> 8) 2^-24, r = sqrt(-2 ln u1),
+ * na = r cos(2 pi u2), nb = r sin(2 pi u2).  Call j = 0 feeds control rows 0-3 ((x0, x1) -> rows 0, 1; (x2, x3) -> rows 2, 3),
+ * call j = 1 rows 4, 5, 6 (its fourth normal is dropped).  The draw of (seed, it, k, g, t, row) does not depend on B, K, H or on
+ * how a batch is sharded.
+ * it_dev: the iteration counter `it`, one unsigned int in DEVICE memory (NULL: it = 0).  The sampler reads it, the update
+ * increments it as its last action — a captured sample -> ... -> update sequence draws fresh noise at every replay.
+ * ac_mppi_sample_f32:  Uc[t][r][o] = min(max(Unom[t][r][b] + sigma[r] n, u_min[r]), u_max[r]); rows with sigma[r] == 0 get the
+ *   clipped nominal without a draw; keep_nominal: column k = 0 is the clipped nominal in every row.  X0 [13][B] given: X0c [13][K*B]
+ *   is its K-fold tiling, written by the same launch (X0 and X0c both or neither).
+ * ac_mppi_update_f32:  per instance b, F = {k : J[k*B + b] finite}, Jmin = min over F, w_k = exp(-(J_k - Jmin) / lambda) on F (else 0),
+ *   eta = sum w_k:  Unew[t][r][b] = clip(sum_k w_k Uc[t][r][k*B + b] / eta).  stats [4][B]: Jmin, the effective sample size
+ *   eta^2 / sum w_k^2, |F|, the index of the cheapest sample (the lowest k on ties).  F empty: Unew = Unom bit for bit and
+ *   stats = (+inf, 0, 0, -1).  Non-finite costs never win (as in ac_ilqr_accept_f32).  No atomics, every sum in a fixed order: the
+ *   same inputs give the same bits.  Unew may be Unom itself (exact aliasing only).  ws: caller-owned device scratch of at least
+ *   ac_mppi_workspace_floats floats (the normalised weights), else AC_ERR_WORKSPACE.
+ * AC_ERR_BAD_ARG: K, B or H < 1, K*B > 2^31 - 1, lambda not finite or <= 0, a negative or non-finite sigma, u_min > u_max, a NULL
+ * required pointer, X0 / X0c given one without the other.  Like every compute call: asynchronous on `stream`, no allocation, no
+ * synchronisation, hipGraph-capturable. */
+typedef struct ac_mppi_opts {
+    float sigma[7];               /* std of the control noise per row (units of the row); 0 = row not sampled */
+    float u_min[7], u_max[7];     /* control box */
+    float lambda;                 /* temperature, > 0 */
+    unsigned long long seed;
+    unsigned int instance_offset; /* global index of local instance 0 (sharded batches) */
+    int keep_nominal;             /* 1: sample k = 0 is the unperturbed nominal */
+} ac_mppi_opts;
+int ac_mppi_workspace_floats(const ac_handle* h, int K, long B, long H, size_t* floats);
+int ac_mppi_sample_f32(ac_handle* h, const ac_mppi_opts* o, const unsigned int* it_dev,
+                       const float* Unom /* [H][7][B] */, const float* X0 /* [13][B] or NULL */,
+                       int K, long B, long H, float* Uc /* [H][7][K*B] */,
+                       float* X0c /* [13][K*B] or NULL */, void* stream);
+int ac_mppi_update_f32(ac_handle* h, const ac_mppi_opts* o, unsigned int* it_dev,
+                       const float* J /* [K*B] */, const float* Uc, const float* Unom,
+                       int K, long B, long H, float* Unew /* [H][7][B] */, float* stats /* [4][B] */,
+                       float* ws, size_t ws_floats, void* stream);
+
 /* Diagnostics */
-const char* ac_last_error(void);     /* thread-local text of the last failing HIP call */
+const char* ac_last_error(void);    /* thread-local text of the last failing HIP call */
 const char* ac_version(void);
 int ac_device_arch(char* buf, size_t len);  /* gcnArchName of the current device */
 /* Device pointer and size (floats) of the handle's second-order workspace (tests poison it with NaNs to prove that every
