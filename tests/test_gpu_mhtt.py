@@ -174,6 +174,9 @@ def test_node_cost_backward_and_cost_match_numpy(gpu):
     Kr, kr, dVr = io.backward(mh.cost, f64(X), U, f64(A), f64(Bm), node=node)
     assert rel_fro(f64(K), Kr) < 2e-3 and rel_fro(f64(kff), kr) < 2e-3 and rel_fro(f64(dV), dVr) < 2e-3
     assert (f64(dV)[0] <= 0).all()
+    # ... and every (node, instance) on its own, within 8 x what fp32 arithmetic costs on these inputs (tests/riccati_ref.py)
+    from tests.riccati_ref import backward_f32, check_riccati
+    check_riccati("mhtt_node_backward", f64(K), f64(kff), f64(dV), (Kr, kr, dVr), backward_f32(mh.cost, f64(X), U, f64(A), f64(Bm), node=node))
     # the model: tracking curvature on position, reference = track point at the frozen progress
     S = f64(ws["S"])
     assert np.allclose(node[0][:-1, :3], 2 * mh.weights.w_tracking) and not node[0][:, 3:].any()
