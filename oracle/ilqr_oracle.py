@@ -176,6 +176,40 @@ def goal_cost(orc, g, goal, X, U, lam=None):
     return J
 
 
+GOAL_TERMS = ("goal", "rate", "height", "speed", "vx", "vyz", "al")
+
+
+def goal_cost_terms(orc, g, goal, X, U, lam=None):
+    """goal_cost term by term: ({name: (Bc,) weighted term}, {name: (Bc,) S_abs}), S_abs = the sum of the absolute values of
+    the term's summands (per axis, per node, per control row; the two squares of the augmented-Lagrangian term).  The terms
+    add up to goal_cost."""
+    H, _, Bc = U.shape
+    Bn = goal.shape[1]
+    gl = np.tile(goal, (1, Bc // Bn))
+    t, a = {}, {}
+    t["goal"] = g.w_goal * ((X[H, 0] - gl[0]) ** 2 + (X[H, 1] - gl[1]) ** 2)
+    du = U[1:] - U[:-1]
+    t["rate"] = g.w_rate * l0_smooth(du[:, _rate_rows(g)], g.eps_rate).sum(axis=(0, 1))
+    t["height"] = g.w_height * (X[H, 2] - X[0, 2]) ** 2
+    speed = np.zeros(Bc)
+    for k in range(H):
+        vr = orc.aero(X[k], np.zeros((7, Bc)))[:3]
+        speed += (vr * vr).sum(axis=0)
+    t["speed"] = -g.w_speed * speed / H
+    t["vx"] = g.w_vx * X[H, 3]
+    t["vyz"] = g.w_vyz * (X[H, 4] ** 2 + X[H, 5] ** 2)
+    for k in t:
+        a[k] = np.abs(t[k])     # sums of terms of one sign (vx: a single summand)
+    t["al"] = np.zeros(Bc); a["al"] = np.zeros(Bc)
+    if g.w_al > 0:
+        s = (np.zeros(Bn) if lam is None else np.asarray(lam, float)) / (2 * g.w_al)
+        s = np.tile(s, Bc // Bn)
+        v = np.maximum(0.0, X[H, 3] - g.vx_max + s)
+        t["al"] = g.w_al * (v ** 2 - s ** 2)
+        a["al"] = g.w_al * (v ** 2 + s ** 2)
+    return t, a
+
+
 def goal_model(orc, g, goal, X, U, lam=None):
     """The quadratic model of ac_goal_model_f32 around (X, U): node_q, node_xref, node_glin (H+1,13,B), uglin (H,7,B) and
     the rate curvature on the (u,u) diagonal (H,7,B)."""

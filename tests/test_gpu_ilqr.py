@@ -555,6 +555,22 @@ def test_goal_acquisition_kernels_match_numpy(gpu):
     got2 = il.trajectory_cost(X2, U2).cpu().numpy()
     want2 = np.concatenate([want, io.goal_cost(orc, gl, goal, Xh, 0.5 * U, lam)])
     assert np.abs(got2 - want2).max() <= 2e-5 * np.abs(want2).max()
+    # ... and term by term, one weight at a time, every instance within 8 x what fp32 arithmetic costs on these inputs
+    # (tests/cost_terms_ref.py; e32 of these inputs 3e-8 .. 1.7e-7 per term)
+    from tests import cost_terms_ref as cr
+    assert ac.epsilon == cr.EPSILON
+    terms, sabs = io.goal_cost_terms(orc, gl, goal, Xh, U, lam)
+    f32t = cr.goal_terms_np(np.float32, gl, goal, Xh, U, lam)
+    fields = ("w_goal", "w_rate", "w_height", "w_speed", "w_vx", "w_vyz", "w_al")
+    keep = {k: getattr(il.loss, k) for k in fields}
+    got_t = {}
+    for t, field in zip(io.GOAL_TERMS, fields):
+        for k in fields:
+            setattr(il.loss, k, keep[k] if k == field else 0.0)
+        got_t[t] = il.trajectory_cost(X, Ud).cpu().numpy().astype(np.float64)
+    for k, v in keep.items():
+        setattr(il.loss, k, v)
+    cr.check_terms("goal_terms[glider]", got_t, terms, sabs, f32t)
     ws = il._workspace(B, gpu)
     Hz = ws["Hz"].zero_()
     ug = il._goal_model(X, Ud, Hz)
@@ -569,6 +585,12 @@ def test_goal_acquisition_kernels_match_numpy(gpu):
     assert np.abs(diag - uhw).max() <= 2e-5 * np.abs(uhw).max()
     Hh[:, np.arange(13, 20), np.arange(13, 20)] = 0.0
     assert not Hh.any()                    # nothing but the (u,u) diagonal is touched
+    # ... and per (node, instance, row group) within 8 x e32.  Not the attitude rows of the speed gradient: they are
+    # 2 epsilon sum_i d v_rel_i / d q_j ~ 4e-7, what is left when terms of ~6000 cancel, and their fp32 restatement is 0.38 of
+    # that on these inputs; they stay on the whole-tensor line above.
+    f32m = cr.goal_model_np(np.float32, gl, goal, Xh, U, lam)
+    cr.check_groups("goal_model[glider]", {"nq": (f64(g["nq"]), nq, f32m[0]), "nx": (f64(g["nx"]), nx, f32m[1]), "ng": (f64(g["ng"]), ng, f32m[2]),
+                                           "uglin": (f64(ug), ugw, f32m[3]), "uhess": (diag, uhw, f32m[4])}, skip={("ng", "q")})
     # backward pass with the control gradient
     F, A, Bm, _ = il.linearise(X, Ud, want_c=False)
     node = (g["nq"], g["nx"], g["ng"])

@@ -143,6 +143,21 @@ def test_mhtt_loss_matches_restatement(gpu):
                              w_low_velocity=0.0, w_control=0.0)
     _, _, te = mh.progress(X, dev(s0, gpu), mode=1, want_terms=True)
     assert np.allclose(f64(mh.loss(X, dev(U, gpu), S)), f64(te).sum(axis=0), rtol=1e-5)
+    # ... and term by term, one weight at a time, every instance within 8 x what fp32 arithmetic costs on these inputs
+    # (tests/cost_terms_ref.py).  Not the tracking term: with track coordinates of 300 m beside errors of a few metres its fp32
+    # restatement is 2.5e-6 from float64 on these gliders, beyond the 1.25e-6 a case may have; it is pinned on the tracks of
+    # tests/test_gpu_cost_terms.py.  The backward and low-velocity terms are exactly zero here, and must come out so.
+    from tests import cost_terms_ref as cr
+    terms, sabs = to.mhtt_loss_terms(tro, mh.track_length, f64(X), U, f64(S))
+    f32t = cr.mhtt_terms_np(np.float32, cr.TrackNP(arc_points(), np.float32), f64(X), U, f64(S))
+    got = {}
+    for label, w in cr.weights_one_hot():
+        if label in ("w_tracking", "all"):
+            continue
+        mh.weights = MHTTWeights(**w)
+        got[label] = f64(mh.loss(X, dev(U, gpu), S))
+    assert not terms["w_backward"].any() and not terms["w_low_velocity"].any()
+    cr.check_terms("mhtt_terms[glider]", got, terms, sabs, f32t)
 
 
 def test_initialise_matches_reference_shape(gpu):
@@ -183,6 +198,13 @@ def test_node_cost_backward_and_cost_match_numpy(gpu):
     want_ref = np.stack([mh.track.eval(S[k]) for k in range(12)])
     assert np.abs(node[1][:12, :3] - want_ref).max() < 1e-3
     assert (node[2][:12, 3] < 0).all()  # rewards velocity along the track (+x here)
+    # ... and every (node, instance, row group) against the float64 model, within 8 x e32 (tests/cost_terms_ref.py; e32 of these
+    # inputs: nq 1.6e-7, nx 4.8e-8, ng 1.9e-7)
+    import track_oracle as to
+    from tests import cost_terms_ref as cr
+    want_model = to.mhtt_model(tro, mh.track_length, f64(X), s0, mh.dt, 1)
+    f32m = cr.progress_np(np.float32, cr.TrackNP(arc_points(), np.float32), f64(X), s0, mh.dt, 1)[3:]
+    cr.check_groups("mhtt_model[glider]", {n: (node[i], want_model[i], f32m[i]) for i, n in enumerate(("nq", "nx", "ng"))})
     # cost of the quadratic model through the ABI, also on a line-search-wide batch (column a*B + b -> b)
     import ctypes as C
     import torch
