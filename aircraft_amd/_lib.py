@@ -133,6 +133,13 @@ PROTOTYPES = {
     "ac_goal_multiplier_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP]),
     "ac_ilqr_backward_goal_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP,
                                             _VP, _VP]),
+    "ac_ilqr_backward_rate_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
+                                            _VP, _VP, _VP, _VP]),
+    "ac_rollout_policy_rate_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _FP, C.c_int, C.c_float, C.c_long, C.c_long,
+                                             _VP, _VP, _VP]),
+    "ac_goal_model_rate_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ac_ilqr_rate_model_f32": (C.c_int, [_VP, _FP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP]),
+    "ac_ilqr_rate_cost_f32": (C.c_int, [_VP, _FP, _VP, C.c_long, _VP, C.c_long, C.c_long, _VP, _VP]),
     "ac_set_track": (C.c_int, [_VP, C.c_int, _FP, C.c_float]),
     "ac_track_eval_f32": (C.c_int, [_VP, _VP, C.c_long, _VP, _VP, _VP]),
     "ac_track_progress_f32": (C.c_int, [_VP, _VP, _VP, _VP, C.c_float, C.c_long, C.c_long, C.c_int, _VP, _VP, _VP, _VP,

@@ -9,6 +9,10 @@ main/control/control.py:35-70: goal term on the final position, actuation penalt
 One iteration = linearise (ac_shoot_sens_f32) -> backward Riccati pass (ac_ilqr_backward_f32) -> closed-loop rollouts for
 every line-search step alpha in ONE launch (ac_rollout_policy_f32) -> cost (ac_ilqr_cost_f32) -> per-instance argmin.
 Everything stays on the device; torch supplies the buffers only (the acceptance is a HIP kernel too: ac_ilqr_accept_f32).
+
+A control-RATE cost (`ILQR(rate_weight=)`, `GoalAcquisition(rate="exact")`) is modelled exactly: the Riccati pass carries the
+previous control as seven more states (ac_ilqr_backward_rate_f32, csrc/ac_ilqr_rate.hpp) and the closed loop feeds the control
+it applied at the previous node back through the gains Kp (ac_rollout_policy_rate_f32).
 """
 from __future__ import annotations
 
@@ -84,8 +88,11 @@ class ILQR(MultipleShooting):
     def __init__(self, *, system, dt: float = 0.01, num_nodes: int, cost: QuadraticCost, opts: Optional[dict] = None,
                  alphas: Sequence[float] = (1.0, 0.5, 0.25, 0.1, 0.03), hessian: str = "gauss-newton",
                  envelope_weight: float = 0.0, envelope_bounds=None, envelope: str = "penalty",
-                 time: str = "fixed", dt_bounds=(0.005, 0.02), w_time: float = 0.0, r_time: float = 0.0):
-        """hessian: 'gauss-newton' (first-order dynamics in the backward pass: iLQR) or 'exact' (adds the second-order
+                 time: str = "fixed", dt_bounds=(0.005, 0.02), w_time: float = 0.0, r_time: float = 0.0, rate_weight=None):
+        """rate_weight (a scalar or 7 values, >= 0): adds the actuator-slew cost  1/2 sum_k sum_i w_i (u_k,i - u_{k-1},i)^2  —
+        plus the k = 0 term against `solve(u_prev=)` — to the objective (`trajectory_cost`), modelled exactly in the backward
+        pass; the time row of time='variable' is excluded.
+        hessian: 'gauss-newton' (first-order dynamics in the backward pass: iLQR) or 'exact' (adds the second-order
         terms  sum_i lambda_i d2F_i/dz dz  of every node — what IPOPT gets from `nlp_hess_l`).
         envelope_weight > 0: the flight envelope of AircraftControl.state_constraint (control/aircraft.py:44-59:
         20^2 <= |v_rel|^2 <= 100^2, |beta| <= 10 deg, |alpha| <= 20 deg, z < 0) as a soft constraint — the squared violation
@@ -120,6 +127,15 @@ class ILQR(MultipleShooting):
         self.hessian_mode = hessian
         self.envelope_weight = float(envelope_weight)
         self.envelope_bounds = envelope_bounds
+        self.rate_weight = None
+        if rate_weight is not None:
+            w = [float(rate_weight)] * 7 if not hasattr(rate_weight, "__len__") else [float(v) for v in rate_weight]
+            assert len(w) == 7 and all(0.0 <= v < float("inf") for v in w), "rate_weight: a scalar or 7 finite values >= 0"
+            if self.time_row > 0:
+                w[self.time_row] = 0.0
+            self.rate_weight = w
+        self._u_prev = None        # (7, B) control applied before the window (solve(u_prev=)), or None
+        self._rate_exact = self.rate_weight is not None   # the backward pass carries u_{k-1} (GoalAcquisition(rate="exact") too)
         self._ws = None
 
     # ---- device workspace (allocated once per (B, H)) ------------------------------------------------
@@ -134,6 +150,8 @@ class ILQR(MultipleShooting):
                             improved=torch.empty((B,), device=dev, dtype=torch.bool))
             if self.time_row > 0:
                 self._ws.update(dt=f(H, B), c=f(H, 13, B))
+            if self._rate_exact:
+                self._ws.update(Kp=f(H, 7, 7, B), rate_g=f(H, 7, B), rate_h=f(H, 7, B))
             if self.hessian_mode == "exact":
                 self._ws.update(Lam=f(H, 13, B), Hz=f(H, 21, 21, B))
                 self.system._sync()
@@ -213,6 +231,29 @@ class ILQR(MultipleShooting):
             out = torch.empty((B,), device=X.device, dtype=torch.float32)
         _lib.check(lib.ac_ilqr_cost_f32(self.system._handle, self._cstruct(), X.data_ptr(), U.data_ptr(), B, H,
                                         out.data_ptr(), self.system._stream()), "ac_ilqr_cost_f32")
+        if self.rate_weight is not None:  # (a candidate batch reads instance o % Bn's previous control)
+            up = self._u_prev
+            _lib.check(lib.ac_ilqr_rate_cost_f32(self.system._handle, self._rate_arr(), up.data_ptr() if up is not None else None,
+                                                 up.shape[1] if up is not None else B, U.data_ptr(), B, H, out.data_ptr(),
+                                                 self.system._stream()), "ac_ilqr_rate_cost_f32")
+        return out
+
+    def _rate_arr(self):
+        return (C.c_float * 7)(*self.rate_weight)
+
+    def rate_model(self, U, out=None):
+        """The model of the quadratic rate cost for the backward pass: (rate_g, rate_h), each (N, 7, B) — gradient and
+        curvature with respect to the difference u_k - u_{k-1}; row 0 is the term against `u_prev` (zeros without one)."""
+        torch = _torch()
+        lib = self.system._sync()
+        H, B = U.shape[0], U.shape[2]
+        if out is None:
+            out = (torch.empty((H, 7, B), device=U.device), torch.empty((H, 7, B), device=U.device))
+        up = self._u_prev
+        assert up is None or tuple(up.shape) == (7, B), "u_prev: (7, B)"
+        _lib.check(lib.ac_ilqr_rate_model_f32(self.system._handle, self._rate_arr(), U.data_ptr(),
+                                              up.data_ptr() if up is not None else None, B, H, out[0].data_ptr(),
+                                              out[1].data_ptr(), self.system._stream()), "ac_ilqr_rate_model_f32")
         return out
 
     def _node_cost(self, X, U):
@@ -239,15 +280,29 @@ class ILQR(MultipleShooting):
 
     _goal_model = None  # GoalAcquisition sets it (see iterate)
 
-    def backward(self, X, U, A, Bm, out=None, Hz=None, node="auto", uglin=None):
+    def backward(self, X, U, A, Bm, out=None, Hz=None, node="auto", uglin=None, rate=None):
         """Riccati pass -> K (N, 7, 13, B), kff (N, 7, B), dV (2, B).  Hz (N, 21, 21, B): optional second-order
         dynamics blocks from `hessian()` (exact-Hessian / Newton step).  uglin (N, 7, B): optional per-node control
-        gradient (needs node arrays and Hz: ac_ilqr_backward_goal_f32)."""
+        gradient (needs node arrays and Hz: ac_ilqr_backward_goal_f32).
+        rate = (rate_g, rate_h), each (N, 7, B): the control-rate term per difference u_k - u_{k-1}, carried exactly
+        (ac_ilqr_backward_rate_f32) -> K, kff, dV, Kp (N, 7, 7, B); `out` then takes the four."""
         torch = _torch()
         lib = self.system._sync()
         H, B = U.shape[0], U.shape[2]
         if isinstance(node, str):
             node = self._node_cost(X, U)
+        if rate is not None:
+            assert uglin is None, "the rate gradient arrives in `rate`"
+            if out is None:
+                out = (torch.empty((H, 7, 13, B), device=X.device), torch.empty((H, 7, B), device=X.device),
+                       torch.empty((2, B), device=X.device), torch.empty((H, 7, 7, B), device=X.device))
+            K, kff, dV, Kp = out
+            _lib.check(lib.ac_ilqr_backward_rate_f32(self.system._handle, self._cstruct(), *self._ptrs(node),
+                                                     C.c_void_p(Hz.data_ptr() if Hz is not None else 0), rate[0].data_ptr(),
+                                                     rate[1].data_ptr(), X.data_ptr(), U.data_ptr(), A.data_ptr(),
+                                                     Bm.data_ptr(), B, H, K.data_ptr(), Kp.data_ptr(), kff.data_ptr(),
+                                                     dV.data_ptr(), self.system._stream()), "ac_ilqr_backward_rate_f32")
+            return K, kff, dV, Kp
         if out is None:
             out = (torch.empty((H, 7, 13, B), device=X.device), torch.empty((H, 7, B), device=X.device),
                    torch.empty((2, B), device=X.device))
@@ -267,8 +322,9 @@ class ILQR(MultipleShooting):
                    "ac_ilqr_backward_newton_f32")
         return K, kff, dV
 
-    def forward(self, x0, Xnom, U, K, kff, alphas=None, out=None):
-        """Closed-loop rollouts for every alpha: Xc (H+1, 13, n_alpha*B), Uc (H, 7, n_alpha*B); column a*B + b."""
+    def forward(self, x0, Xnom, U, K, kff, alphas=None, out=None, Kp=None):
+        """Closed-loop rollouts for every alpha: Xc (H+1, 13, n_alpha*B), Uc (H, 7, n_alpha*B); column a*B + b.
+        Kp (N, 7, 7, B): the gains on the previous control of `backward(rate=)` (ac_rollout_policy_rate_f32)."""
         torch = _torch()
         lib = self.system._sync()
         alphas = self.alphas if alphas is None else [float(a) for a in alphas]
@@ -278,6 +334,12 @@ class ILQR(MultipleShooting):
             out = (torch.empty((H + 1, 13, na * B), device=U.device), torch.empty((H, 7, na * B), device=U.device))
         Xc, Uc = out
         arr = (C.c_float * na)(*alphas)
+        if Kp is not None:
+            _lib.check(lib.ac_rollout_policy_rate_f32(self.system._handle, self._cstruct(), x0.data_ptr(), Xnom.data_ptr(),
+                                                      U.data_ptr(), K.data_ptr(), Kp.data_ptr(), kff.data_ptr(), arr, na,
+                                                      C.c_float(self.dt), B, H, Xc.data_ptr(), Uc.data_ptr(),
+                                                      self.system._stream()), "ac_rollout_policy_rate_f32")
+            return Xc, Uc
         _lib.check(lib.ac_rollout_policy_f32(self.system._handle, self._cstruct(), x0.data_ptr(), Xnom.data_ptr(),
                                              U.data_ptr(), K.data_ptr(), kff.data_ptr(), arr, na, C.c_float(self.dt),
                                              B, H, Xc.data_ptr(), Uc.data_ptr(), self.system._stream()),
@@ -301,10 +363,18 @@ class ILQR(MultipleShooting):
         Hz = None
         env = self.envelope_weight > 0
         goal = self._goal_model is not None  # GoalAcquisition: node arrays + control gradient + (u, u) curvature
-        if self.hessian_mode != "exact" and (env or goal):
+        exact_rate = self._rate_exact       # the rate term per difference, u_{k-1} carried through the backward pass
+        if self.hessian_mode != "exact" and (env or (goal and not exact_rate)):
             Hz = ws["Hz"].zero_()
         # (first: it WRITES the node arrays the envelope below adds to; adds the rate curvature to Hz, returns the control gradient)
-        uglin = self._goal_model(X, U, Hz) if goal else None
+        uglin = self._goal_model(X, U, Hz) if (goal and not exact_rate) else None
+        rate = None
+        if exact_rate:
+            rate = (ws["rate_g"], ws["rate_h"])
+            if goal:
+                self._goal_model_rate(X, U, rate)  # the node arrays too
+            else:
+                self.rate_model(U, out=rate)
         if env:
             if node is None:  # the constant cost as per-node arrays, so that the penalty gradient has a place to go
                 ws["env_glin"].zero_()
@@ -315,8 +385,12 @@ class ILQR(MultipleShooting):
             Hz = self.hessian(X, U, ws["Lam"], out=ws["Hz"])
         if env:
             self._envelope_model(X, Hz=Hz)
-        self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"]), Hz=Hz, node=node, uglin=uglin)
-        self.forward(x0, X, U, ws["K"], ws["kff"], out=(ws["Xc"], ws["Uc"]))
+        if rate is not None:
+            self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"], ws["Kp"]), Hz=Hz, node=node, rate=rate)
+            self.forward(x0, X, U, ws["K"], ws["kff"], out=(ws["Xc"], ws["Uc"]), Kp=ws["Kp"])
+        else:
+            self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"]), Hz=Hz, node=node, uglin=uglin)
+            self.forward(x0, X, U, ws["K"], ws["kff"], out=(ws["Xc"], ws["Uc"]))
         self.trajectory_cost(ws["Xc"], ws["Uc"], out=ws["Jc"])
         self.trajectory_cost(X, U, out=ws["J0"])
         if env:
@@ -338,13 +412,20 @@ class ILQR(MultipleShooting):
                                           self.system._stream()), "ac_ilqr_accept_f32")
         return Ja, imp
 
-    def solve(self, x0, U0, iters: int = 10, save_to: Optional[str] = None, save_instance: int = 0, al_every: int = 0):
+    def solve(self, x0, U0, iters: int = 10, save_to: Optional[str] = None, save_instance: int = 0, al_every: int = 0,
+              u_prev=None):
         """Rollout from x0 with U0, then `iters` iLQR iterations.  Returns (X, U, cost history (iters+1, B)).
+        u_prev (7, B), with `rate_weight`: the control applied before the window; the rate cost then has a k = 0 term.
         `save_to` writes instance `save_instance` after every iteration in the reference's trajectory format
         (iteration_0 = the initial rollout), the role of the IPOPT callback in control/base.py:60-86.
         al_every > 0 (envelope = 'al'): a multiplier update after every al_every-th sweep."""
         torch = _torch()
         U = U0.clone()
+        if u_prev is not None:
+            assert self.rate_weight is not None, "u_prev needs ILQR(rate_weight=)"
+            assert tuple(u_prev.shape) == (7, U0.shape[2]), "u_prev: (7, B)"
+            u_prev = u_prev.to(device=U0.device, dtype=torch.float32).contiguous()
+        self._u_prev = u_prev
         if self.time_row > 0:
             U[:, self.time_row, :] = self.dt  # every node starts at the nominal step (the rollout below uses it)
         X = self.rollout(x0, U)
@@ -375,16 +456,24 @@ class GoalAcquisition(ILQR):
     search and the history (ac_goal_cost_f32); the backward pass sees its convex quadratic model (ac_goal_model_f32:
     csrc/ac_goal.hpp states what is modelled how); the terminal inequality is an augmented-Lagrangian term with one
     multiplier per instance, updated by `update_goal_multiplier()` (`solve(al_every=)`).  time='variable' adds the
-    reference's time term 10000 T through w_time (opts['time'] = 'progress' in the reference's driver, control.py:182)."""
+    reference's time term 10000 T through w_time (opts['time'] = 'progress' in the reference's driver, control.py:182).
+    rate: how the backward pass models the control-rate term — 'frozen' (neighbours u_{k-1}, u_{k+1} held at the iterate, the
+    diagonal curvature only) or 'exact' (ac_goal_model_rate_f32: the term per difference, u_{k-1} carried through the pass).
+    The exact loss is the same either way."""
 
     def __init__(self, *, system, goal, dt: float = 0.01, num_nodes: int = 400, vel_param: float = 1.0, w_goal: float = 1000.0,
                  w_rate: float = 100.0, eps_rate: float = 1e-2, w_height: float = 1.0, w_speed: float = 0.01,
                  w_final_velocity: float = 1000.0, vx_max: float = -2.0, w_al: float = 10.0, r: float = 0.0, reg: float = 1e-2,
-                 time: str = "fixed", w_time: float = 10000.0, **kw):
+                 time: str = "fixed", w_time: float = 10000.0, rate: str = "frozen", **kw):
+        assert rate in ("frozen", "exact")
+        assert not (rate == "exact" and kw.get("rate_weight") is not None), "rate='exact' and rate_weight do not combine"
         cost = QuadraticCost(q=[0.0] * 13, qf=[0.0] * 13, r=[float(r)] * 7, reg=float(reg))  # every state term lives in the node arrays
         super().__init__(system=system, dt=dt, num_nodes=num_nodes, cost=cost, time=time, w_time=w_time if time == "variable" else 0.0,
                          **kw)
         assert self.hessian_mode == "gauss-newton"
+        self.rate_mode = rate
+        if rate == "exact":
+            self._rate_exact = True
         self.goal = goal
         self.loss = _lib.GoalLoss()
         ls = self.loss
@@ -422,6 +511,17 @@ class GoalAcquisition(ILQR):
                                          g["ng"].data_ptr(), g["ug"].data_ptr(), Hz.data_ptr(), self.system._stream()),
                    "ac_goal_model_f32")
         return g["ug"]
+
+    def _goal_model_rate(self, X, U, rate):
+        """The node arrays (as _goal_model) and the l0 term per difference u_k - u_{k-1} into rate = (rate_g, rate_h)."""
+        lib = self.system._sync()
+        H, B = U.shape[0], U.shape[2]
+        g = self._goal_ws(B, U.device)
+        _lib.check(lib.ac_goal_model_rate_f32(self.system._handle, C.byref(self.loss), g["goal"].data_ptr(), g["lam"].data_ptr(),
+                                              X.data_ptr(), U.data_ptr(), B, H, g["nq"].data_ptr(), g["nx"].data_ptr(),
+                                              g["ng"].data_ptr(), rate[0].data_ptr(), rate[1].data_ptr(),
+                                              self.system._stream()), "ac_goal_model_rate_f32")
+        return rate
 
     def trajectory_cost(self, X, U, out=None):
         """The exact loss of every column of (X, U) (a candidate batch reads instance b % B's goal and multiplier)."""

@@ -17,8 +17,10 @@
 //     the linear terms and the gradient of the (concave) speed reward as gradients, the control-rate term by its exact
 //     gradient with respect to u_k — neighbours u_{k-1}, u_{k+1} held at the iterate — and the Gauss-Newton curvature of
 //     both differences u_k takes part in, (l0')^2 / (2 l0) -> 2 / eps, on the diagonal of Q_uu.  (The cross terms between
-//     consecutive controls are left to the line search; an exact treatment carries u_{k-1} as seven more states through
-//     the Riccati pass.)
+//     consecutive controls are left to the line search.)  This is GoalAcquisition(rate="frozen"), the default;
+//   * or, with rate="exact", the same model with the control-rate term handed over per DIFFERENCE d_k = u_k - u_{k-1}
+//     (k_goal_model<0, true>: g = w_rate l0'(d_k), h = w_rate (l0')^2 / (2 l0), row 0 zero, nothing added to Hz or uglin) to
+//     the Riccati pass that carries u_{k-1} as seven more states (ac_ilqr_rate.hpp): the cross terms are then modelled exactly.
 // The reference's control matrix has N + 1 columns (N differences); the sweep's has N (N - 1 differences).
 #pragma once
 #include "ac_ilqr.hpp"
@@ -90,7 +92,10 @@ __global__ __launch_bounds__(kBlock) void k_goal_cost(const DevParams P, const G
 // The quadratic model around the iterate, in the form the backward pass consumes: node_q / node_xref / node_glin
 // [H+1][13][B] (WRITTEN, every entry), node_uglin [H][7][B] (written), and the rate curvature ADDED to the diagonal of the
 // (u, u) block of Hz [H][21][21][B].  One lane per (node, instance).
-template <int INST = 0>
+// RATE (the exact treatment, ac_ilqr_rate.hpp): the same node arrays, and in place of node_uglin / Hz the rate model per
+// difference d_k = u_k - u_{k-1}: node_uglin is rate_g [H][7][B] = w_rate l0'(d_k), Hz is rate_h [H][7][B] =
+// w_rate (l0')^2 / (2 l0) (both WRITTEN, every entry; row 0 and the time row are zero).
+template <int INST = 0, bool RATE = false>
 __global__ __launch_bounds__(kBlock) void k_goal_model(const DevParams P, const GoalLoss G, const float* __restrict__ goal,
                                                        const float* __restrict__ lam, const float* __restrict__ X,
                                                        const float* __restrict__ U, long B, long H,
@@ -117,26 +122,37 @@ __global__ __launch_bounds__(kBlock) void k_goal_model(const DevParams P, const 
         const float w = -(G.w_speed / (float)H);
 #pragma unroll
         for (int j = 0; j < 7; ++j) gl[3 + j] = w * vv.d[j];
-        // control-rate term: gradient with respect to u_k, Gauss-Newton curvature of the two differences u_k takes part in
-        float* hz = Hz + k * 441 * B + b;
+        if constexpr (RATE) {
 #pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            float g = 0.f, h = 0.f;
-            if (!(i == G.time_row && G.time_row > 0)) {
-                const float u = U[(k * 7 + i) * B + b];
-                if (k > 0) {
-                    float g1, h1;
-                    l0_model(u - U[((k - 1) * 7 + i) * B + b], G.eps_rate, g1, h1);
-                    g += g1; h += h1;
-                }
-                if (k + 1 < H) {
-                    float g1, h1;
-                    l0_model(U[((k + 1) * 7 + i) * B + b] - u, G.eps_rate, g1, h1);
-                    g -= g1; h += h1;
-                }
+            for (int i = 0; i < 7; ++i) {
+                float g = 0.f, h = 0.f;
+                if (!(i == G.time_row && G.time_row > 0) && k > 0)
+                    l0_model(U[(k * 7 + i) * B + b] - U[((k - 1) * 7 + i) * B + b], G.eps_rate, g, h);
+                node_uglin[(k * 7 + i) * B + b] = G.w_rate * g;
+                Hz[(k * 7 + i) * B + b] = G.w_rate * h;
             }
-            node_uglin[(k * 7 + i) * B + b] = G.w_rate * g;
-            if (Hz && h != 0.f) hz[(long)((13 + i) * 21 + 13 + i) * B] += G.w_rate * h;
+        } else {
+            // control-rate term: gradient with respect to u_k, Gauss-Newton curvature of the two differences u_k takes part in
+            float* hz = Hz + k * 441 * B + b;
+#pragma unroll
+            for (int i = 0; i < 7; ++i) {
+                float g = 0.f, h = 0.f;
+                if (!(i == G.time_row && G.time_row > 0)) {
+                    const float u = U[(k * 7 + i) * B + b];
+                    if (k > 0) {
+                        float g1, h1;
+                        l0_model(u - U[((k - 1) * 7 + i) * B + b], G.eps_rate, g1, h1);
+                        g += g1; h += h1;
+                    }
+                    if (k + 1 < H) {
+                        float g1, h1;
+                        l0_model(U[((k + 1) * 7 + i) * B + b] - u, G.eps_rate, g1, h1);
+                        g -= g1; h += h1;
+                    }
+                }
+                node_uglin[(k * 7 + i) * B + b] = G.w_rate * g;
+                if (Hz && h != 0.f) hz[(long)((13 + i) * 21 + 13 + i) * B] += G.w_rate * h;
+            }
         }
     } else {
         q[0] = q[1] = 2.0f * G.w_goal; xr[0] = goal[b]; xr[1] = goal[B + b];

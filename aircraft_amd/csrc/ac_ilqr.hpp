@@ -448,12 +448,15 @@ __global__ __launch_bounds__(kBlock) void k_ilqr_cost(const IlqrCost C, const No
 
 // ---- feedback policy evaluated inside the rollout kernels ---------------------------------------------
 // Output instance o = a * B + b (a = line-search index): u = clip(U_k[b] + alpha_a kff_k[b] + K_k[b] (x - Xnom_k[b])).
+// With Kp (the exact control-rate pass, ac_ilqr_rate.hpp) the law gains  + Kp_k[b] (u_applied_{k-1} - U_{k-1}[b])  for k > 0:
+// both `control` overloads read the control the lane applied at the previous node from `u` on entry.
 struct Policy {
     const float* __restrict__ Xnom;  // [H+1][13][B]
     const float* __restrict__ U;     // [H][7][B]
     const float* __restrict__ K;     // [H][7][13][B]
     const float* __restrict__ kff;   // [H][7][B]
     long B;                          // nominal batch
+    const float* __restrict__ Kp = nullptr;  // [H][7][7][B] or NULL: gains on the previous control
     AlphaSet alphas;
     float u_min[7], u_max[7];
     // Time as a decision variable (the reference's `dt_k` per node, control/base.py:276, 339-385: dt_k = 1 / progress_k^2
@@ -474,11 +477,19 @@ struct Policy {
         float dx[13];
 #pragma unroll
         for (int i = 0; i < 13; ++i) dx[i] = x[i] - Xnom[(k * 13 + i) * B + b];
+        const bool fb = Kp != nullptr && k > 0;
+        float dp[7];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) dp[i] = fb ? u[i] - U[((k - 1) * 7 + i) * B + b] : 0.f;
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
             float s = fmaf(alpha, kff[(k * 7 + i) * B + b], U[(k * 7 + i) * B + b]);
 #pragma unroll
             for (int m = 0; m < 13; ++m) s = fmaf(K[((k * 7 + i) * 13 + m) * B + b], dx[m], s);
+            if (fb) {
+#pragma unroll
+                for (int m = 0; m < 7; ++m) s = fmaf(Kp[((k * 7 + i) * 7 + m) * B + b], dp[m], s);
+            }
             u[i] = fminf(fmaxf(s, u_min[i]), u_max[i]);
         }
     }
@@ -486,8 +497,10 @@ struct Policy {
     // The same control law for kernels where the four lane groups g = 0..3 of a wave hold the same instance (MLP
     // rollouts): group g takes the columns m = g, g+4, g+8, g+12 of K_k, so a lane loads a quarter of the gains, and
     // the partial products are summed across the groups with two cross-lane adds.  load() can be issued a node ahead.
+    // With Kp, group g also takes the columns m = g, g + 4 (< 7) of Kp_k and the rows of U_{k-1} that go with them.
     struct Quarter {
         float kq[7][4], xn[4], ub[7];
+        float kpq[7][2], up[2];
     };
     AC_DI void load(long k, long o, int g, Quarter& q) const {
         const long b = o % B;
@@ -503,8 +516,26 @@ struct Policy {
         }
 #pragma unroll
         for (int i = 0; i < 7; ++i) q.ub[i] = fmaf(alpha, kff[(k * 7 + i) * B + b], U[(k * 7 + i) * B + b]);
+        if (Kp != nullptr) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int m = g + 4 * c;
+                const bool on = m < 7 && k > 0;
+                const int mm = m < 7 ? m : 6;
+                q.up[c] = on ? U[((k - 1) * 7 + mm) * B + b] : 0.f;
+#pragma unroll
+                for (int i = 0; i < 7; ++i) q.kpq[i][c] = on ? Kp[((k * 7 + i) * 7 + mm) * B + b] : 0.f;
+            }
+        }
     }
     AC_DI void control(const Quarter& q, int g, const float x[13], float u[7]) const {
+        float dp[2] = {0.f, 0.f};
+        if (Kp != nullptr) {  // u[g], u[g + 4] (applied at the previous node; zero at node 0) without dynamic register indexing
+            const float a0 = g == 0 ? u[0] : (g == 1 ? u[1] : (g == 2 ? u[2] : u[3]));
+            const float a1 = g == 0 ? u[4] : (g == 1 ? u[5] : (g == 2 ? u[6] : 0.f));
+            dp[0] = a0 - q.up[0];
+            dp[1] = a1 - q.up[1];
+        }
         float dx[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -520,6 +551,7 @@ struct Policy {
             float s = 0.f;
 #pragma unroll
             for (int c = 0; c < 4; ++c) s = fmaf(q.kq[i][c], dx[c], s);
+            if (Kp != nullptr) s = fmaf(q.kpq[i][1], dp[1], fmaf(q.kpq[i][0], dp[0], s));
             s += __shfl_xor(s, 16, 64);
             s += __shfl_xor(s, 32, 64);
             u[i] = fminf(fmaxf(q.ub[i] + s, u_min[i]), u_max[i]);

@@ -424,7 +424,7 @@ AC_DI void rollout_policy_body(const DevParams& P, const MlpPlan& plan, const fl
     const long raw = (long)blockIdx.x * 16 + col;
     const bool live = raw < Bout;
     const long o = live ? raw : Bout - 1;
-    float x[13], u[7];
+    float x[13], u[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (Policy::control reads the previous node's control when pol.Kp is set)
     load_rows<13>(X0, pol.B, o % pol.B, x);
     const bool writer = live && g == 0 && wave == 0;
     double xa[13];

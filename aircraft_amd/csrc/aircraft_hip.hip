@@ -15,6 +15,7 @@
 #include "ac_nn_decl.hpp"
 #include "ac_ilqr.hpp"
 #include "ac_goal.hpp"
+#include "ac_ilqr_rate.hpp"
 #include "ac_track.hpp"
 #include "ac_hess.hpp"
 #include "ac_hess_adj.hpp"
@@ -1266,6 +1267,75 @@ int ac_ilqr_backward_goal_f32(ac_handle* h, const ac_ilqr_cost* cost, const floa
     return AC_OK;
 }
 
+// ---- the control-rate term modelled exactly: u_{k-1} carried through the Riccati pass (ac_ilqr_rate.hpp) -------------------
+int ac_ilqr_backward_rate_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
+                              const float* node_glin, const float* Hz, const float* rate_g, const float* rate_h, const float* X,
+                              const float* U, const float* A, const float* Bm, long B, long H, float* K, float* Kp, float* kff,
+                              float* dV, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !cost || !rate_g || !rate_h || !X || !U || !A || !Bm || !K || !Kp || !kff || !dV || B < 0 || H < 1)
+        return AC_ERR_BAD_ARG;
+    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
+    const NodeCost nc{node_q, node_xref, node_glin, B};
+    AC_HIP(ilqr_rate_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, rate_g, rate_h, B, H, K, Kp, kff, dV,
+                                     (hipStream_t)stream));
+    note_launch(h, "k_ilqr_backward_rate", (int)B, 64, 0);
+    return AC_OK;
+}
+
+int ac_goal_model_rate_f32(ac_handle* h, const ac_goal_loss* loss, const float* goal, const float* lam, const float* X,
+                           const float* U, long B, long H, float* node_q, float* node_xref, float* node_glin, float* rate_g,
+                           float* rate_h, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !loss || !goal || !X || !U || !node_q || !node_xref || !node_glin || !rate_g || !rate_h || B < 0 || H < 1)
+        return AC_ERR_BAD_ARG;
+    int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    const long n = (H + 1) * B;
+    const int grid = (int)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL((k_goal_model<0, true>), grid, kBlock, 0, (hipStream_t)stream, h->dp, to_dev_goal(loss), goal, lam, X, U, B,
+                       H, node_q, node_xref, node_glin, rate_g, rate_h);
+    note_launch(h, "k_goal_model_rate", grid, kBlock, 0);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+
+static bool rate_weights(const float* w, RateWeights* out) {
+    for (int i = 0; i < 7; ++i) {
+        if (!(w[i] >= 0.f) || !(w[i] <= 3.4028235e38f)) return false;
+        out->w[i] = w[i];
+    }
+    return true;
+}
+
+int ac_ilqr_rate_model_f32(ac_handle* h, const float* rate_weight, const float* U, const float* u_prev, long B, long H,
+                           float* rate_g, float* rate_h, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !rate_weight || !U || !rate_g || !rate_h || B < 0 || H < 1) return AC_ERR_BAD_ARG;
+    RateWeights W;
+    if (!rate_weights(rate_weight, &W)) return fail(AC_ERR_BAD_ARG, "ac_ilqr_rate_model_f32: rate weights must be finite and >= 0");
+    int grid = 0;
+    AC_HIP(ilqr_rate_launch_model(W, U, u_prev, B, H, rate_g, rate_h, (hipStream_t)stream, &grid));
+    note_launch(h, "k_ilqr_rate_model", grid, kBlock, 0);
+    return AC_OK;
+}
+
+int ac_ilqr_rate_cost_f32(ac_handle* h, const float* rate_weight, const float* u_prev, long Bn, const float* U, long B, long H,
+                          float* cost_inout, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !rate_weight || !U || !cost_inout || B < 0 || H < 1 || Bn < 1 || B % Bn != 0) return AC_ERR_BAD_ARG;
+    RateWeights W;
+    if (!rate_weights(rate_weight, &W)) return fail(AC_ERR_BAD_ARG, "ac_ilqr_rate_cost_f32: rate weights must be finite and >= 0");
+    int grid = 0;
+    AC_HIP(ilqr_rate_launch_cost(W, U, u_prev, Bn, B, H, cost_inout, (hipStream_t)stream, &grid));
+    note_launch(h, "k_ilqr_rate_cost", grid, kBlock, 0);
+    return AC_OK;
+}
+
 int ac_ilqr_cost_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* X, const float* U, long B, long H,
                      float* out, void* stream) {
     return ac_ilqr_cost_node_f32(h, cost, nullptr, nullptr, nullptr, B, X, U, B, H, out, stream);
@@ -1370,9 +1440,10 @@ int ac_mhtt_loss_f32(ac_handle* h, const ac_mhtt_weights* weights, const float* 
     return AC_OK;
 }
 
-int ac_rollout_policy_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X0, const float* Xnom, const float* U,
-                          const float* K, const float* kff, const float* alphas, int n_alpha, float dt, long B, long H,
-                          float* Xout, float* Uout, void* stream) {
+// the two closed-loop entries; Kp == nullptr: the law without the previous-control term (ac_rollout_policy_f32)
+static int rollout_policy(ac_handle* h, const ac_ilqr_cost* limits, const float* X0, const float* Xnom, const float* U,
+                          const float* K, const float* Kp, const float* kff, const float* alphas, int n_alpha, float dt, long B,
+                          long H, float* Xout, float* Uout, void* stream) {
     AC_ENTER(h);
     if (h && B == 0) return AC_OK;
     if (!h || !limits || !X0 || !Xnom || !U || !K || !kff || !alphas || !Xout || !Uout || B < 0 || H < 1) return AC_ERR_BAD_ARG;
@@ -1381,7 +1452,7 @@ int ac_rollout_policy_f32(ac_handle* h, const ac_ilqr_cost* limits, const float*
     if (rc != AC_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     Policy pol;
-    pol.Xnom = Xnom; pol.U = U; pol.K = K; pol.kff = kff; pol.B = B;
+    pol.Xnom = Xnom; pol.U = U; pol.K = K; pol.kff = kff; pol.B = B; pol.Kp = Kp;
     pol.alphas.n = n_alpha;
     for (int i = 0; i < 8; ++i) pol.alphas.a[i] = i < n_alpha ? alphas[i] : 0.f;
     memcpy(pol.u_min, limits->u_min, sizeof(pol.u_min));
@@ -1429,6 +1500,19 @@ int ac_rollout_policy_f32(ac_handle* h, const ac_ilqr_cost* limits, const float*
     note_launch(h, "k_rollout_policy", grid, 64, 0);
     AC_HIP(hipGetLastError());
     return AC_OK;
+}
+
+int ac_rollout_policy_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X0, const float* Xnom, const float* U,
+                          const float* K, const float* kff, const float* alphas, int n_alpha, float dt, long B, long H,
+                          float* Xout, float* Uout, void* stream) {
+    return rollout_policy(h, limits, X0, Xnom, U, K, nullptr, kff, alphas, n_alpha, dt, B, H, Xout, Uout, stream);
+}
+
+int ac_rollout_policy_rate_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X0, const float* Xnom, const float* U,
+                               const float* K, const float* Kp, const float* kff, const float* alphas, int n_alpha, float dt,
+                               long B, long H, float* Xout, float* Uout, void* stream) {
+    if (h && B != 0 && !Kp) { AC_ENTER(h); return AC_ERR_BAD_ARG; }
+    return rollout_policy(h, limits, X0, Xnom, U, K, Kp, kff, alphas, n_alpha, dt, B, H, Xout, Uout, stream);
 }
 
 int ac_hess_workspace(const ac_handle* h, float** ptr, size_t* floats) {

@@ -348,6 +348,35 @@ int ac_ilqr_backward_goal_f32(ac_handle* h, const ac_ilqr_cost* cost, const floa
                               const float* U, const float* A, const float* Bm, long B, long H, float* K, float* kff,
                               float* dV, void* stream);
 
+/* The control-RATE term  sum_k rho_k(u_k - u_{k-1})  modelled exactly: the Riccati pass carries p_k = u_{k-1} as seven more
+ * states (csrc/ac_ilqr_rate.hpp states the recursion).  rate_g, rate_h [H][7][B]: gradient and non-negative diagonal
+ * curvature of rho_k with respect to the difference d_k = u_k - u_{k-1}; row 0 is the term against the control applied before
+ * the window (all zeros: none).
+ *   ac_ilqr_backward_rate_f32   ac_ilqr_backward_newton_f32 (node arrays and Hz optional, as there) with the rate model;
+ *                               also returns Kp [H][7][7][B], the gains on the previous control
+ *   ac_rollout_policy_rate_f32  ac_rollout_policy_f32 with the law
+ *                               u_k = clip(U_k + alpha kff_k + K_k (x - Xnom_k) + Kp_k (u_applied_{k-1} - U_{k-1})),  k > 0
+ *   ac_goal_model_rate_f32      ac_goal_model_f32's node arrays, and the l0 term per difference: rate_g = w_rate l0'(d_k),
+ *                               rate_h = w_rate l0'^2 / (2 l0) (row 0 and the time row zero); nothing goes to Hz or uglin
+ *   ac_ilqr_rate_model_f32      the quadratic rate cost  1/2 sum_k sum_i w_i (u_k,i - u_{k-1},i)^2  (rate_weight: HOST float[7],
+ *                               finite, >= 0; u_prev [7][B] or NULL = no k = 0 term): rate_g = w d, rate_h = w
+ *   ac_ilqr_rate_cost_f32       cost_inout[o] += that cost of column o of a candidate batch U [H][7][B] (B % Bn == 0); column o
+ *                               reads the previous control of instance o % Bn (u_prev [7][Bn] or NULL) */
+int ac_ilqr_backward_rate_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
+                              const float* node_glin, const float* Hz, const float* rate_g, const float* rate_h, const float* X,
+                              const float* U, const float* A, const float* Bm, long B, long H, float* K, float* Kp, float* kff,
+                              float* dV, void* stream);
+int ac_rollout_policy_rate_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X0, const float* Xnom, const float* U,
+                               const float* K, const float* Kp, const float* kff, const float* alphas, int n_alpha, float dt,
+                               long B, long H, float* Xout, float* Uout, void* stream);
+int ac_goal_model_rate_f32(ac_handle* h, const ac_goal_loss* loss, const float* goal, const float* lam, const float* X,
+                           const float* U, long B, long H, float* node_q, float* node_xref, float* node_glin, float* rate_g,
+                           float* rate_h, void* stream);
+int ac_ilqr_rate_model_f32(ac_handle* h, const float* rate_weight, const float* U, const float* u_prev, long B, long H,
+                           float* rate_g, float* rate_h, void* stream);
+int ac_ilqr_rate_cost_f32(ac_handle* h, const float* rate_weight, const float* u_prev, long Bn, const float* U, long B, long H,
+                          float* cost_inout, void* stream);
+
 /* Exact-Hessian (Newton / SQP) variant of the sweep, for the force models ac_shoot_hess_f32 supports:
  *   ac_ilqr_costate_f32        Lam [H][13][B]: multipliers of the defect rows at the current iterate,
  *                              Lam[H-1] = grad l_N(x_N), Lam[k-1] = grad l_k(x_k) + A_k' Lam[k]
