@@ -387,6 +387,16 @@ __global__ __launch_bounds__(kBlock, kSensWavesPerSimd) void k_deriv_sens(const 
 // ---- envelope rows of AircraftControl.state_constraint (control/aircraft.py:44-59) and their state Jacobian ---------
 //   rows[0] = v_rel . v_rel (20^2 .. 100^2)   rows[1] = beta (+-10 deg)   rows[2] = alpha (+-20 deg)   rows[3] = z (< 0)
 // One lane per unit; the rows depend on (v, q) only: Dual<7>.  rows [4][n]; Jx [4][13][n] (may be NULL).
+// d|v_rel|^2 / dq.  r = q^-1 v q keeps |v| for every q (q^-1 is the true inverse), so r . dr/dq = 0 and only the epsilon offset of
+// v_rel = r + eps reaches the attitude columns: 2 eps sum_i dr_i/dq_j (~3e-4).  The product rule 2 v_rel . dv_rel/dq leaves that
+// as the rest of terms of ~2 V^2 that cancel: ~1e-3 of rounding in fp32, more than the value.  Directions 3..6 of the Dual<7>
+// seeding of k_envelope / k_envelope_model are the quaternion's.
+AC_DI void speed_row_attitude_columns(const DevParams& P, const AeroPre<Dual<7>>& a, Dual<7>& vv) {
+    const float e2 = 2.0f * P.p.epsilon;
+#pragma unroll
+    for (int j = 3; j < 7; ++j) vv.d[j] = e2 * ((a.vr[0].d[j] + a.vr[1].d[j]) + a.vr[2].d[j]);
+}
+
 template <int INST = 0>  // a template only so that the header may be included by several translation units
 __global__ __launch_bounds__(kBlock) void k_envelope(const DevParams P, const float* __restrict__ X, long n, long blk,
                                                      float* __restrict__ rows, float* __restrict__ Jx) {
@@ -404,7 +414,8 @@ __global__ __launch_bounds__(kBlock) void k_envelope(const DevParams P, const fl
     }
     AeroPre<T> a;
     aero_pre(P, x, a);
-    const T row[3] = {a.vr[0] * a.vr[0] + a.vr[1] * a.vr[1] + a.vr[2] * a.vr[2], a.beta, a.alpha};
+    T row[3] = {a.vr[0] * a.vr[0] + a.vr[1] * a.vr[1] + a.vr[2] * a.vr[2], a.beta, a.alpha};
+    speed_row_attitude_columns(P, a, row[0]);
     float* ro = rows + ua.off(4);
 #pragma unroll
     for (int r = 0; r < 3; ++r) ro[(long)r * blk] = row[r].v;
@@ -542,7 +553,8 @@ __global__ __launch_bounds__(kBlock) void k_envelope_model(const DevParams P, co
     for (int r = 0; r < 13; ++r) { x[r] = T(xv[r]); if (r >= 3 && r < 10) x[r].d[r - 3] = 1.f; }
     AeroPre<T> a;
     aero_pre(P, x, a);
-    const T row[3] = {a.vr[0] * a.vr[0] + a.vr[1] * a.vr[1] + a.vr[2] * a.vr[2], a.beta, a.alpha};
+    T row[3] = {a.vr[0] * a.vr[0] + a.vr[1] * a.vr[1] + a.vr[2] * a.vr[2], a.beta, a.alpha};
+    speed_row_attitude_columns(P, a, row[0]);
     float viol[4], active[4], grad[4][13], lh[4], ll[4];
     load_multipliers(lam, k, b, B, lh, ll);
 #pragma unroll

@@ -128,6 +128,51 @@ def envelope_al(orc, X, lo, hi, w, lam=None):
     return cost, grad, curv, sv, rows_all
 
 
+ENVELOPE_KINDS = ("up", "dn", "sh", "sl")     # the summands w up^2, w dn^2, -w sh^2, -w sl^2 of L_A
+
+
+def envelope_al_terms(orc, X, lo, hi, w, lam=None, rows_jx=None):
+    """envelope_al row by row and side by side.  Returns a dict:
+      summands (Hn, 4, 4, B)   [node, kind, row, instance]: w up^2, w dn^2, -w sh^2, -w sl^2 (ENVELOPE_KINDS),
+                               up = max(0, g - hi + sh), dn = max(0, lo - g + sl), sh = lam_hi / 2w, sl = lam_lo / 2w
+      terms, sabs (4, 4, B)    their sum and the sum of their absolute values over the nodes
+      grad (Hn, 4, 13, B)      2 w (up - dn) grad g_r, per row
+      curv (Hn, 4, 13, 13, B)  2 w (sides active) grad g_r grad g_r', per row (Gauss-Newton)
+      up, dn (Hn, 4, B)        the shifted one-sided violations before the max (their sign is the active set)
+      rows (Hn, 4, B), Jx (Hn, 4, 13, B)
+    The terms add up to envelope_al's cost, the rows of grad / curv to its gradient / curvature.  rows_jx: (rows, Jx) of an
+    earlier call on the same X (they do not depend on the bounds), to spare the oracle calls."""
+    Hn, _, B = X.shape
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    lam = np.zeros((Hn, 8, B)) if lam is None else np.asarray(lam, dtype=np.float64)
+    if rows_jx is None:
+        rows = np.zeros((Hn, 4, B)); Jx = np.zeros((Hn, 4, 13, B))
+        for k in range(Hn):
+            rows[k], Jx[k] = orc.envelope(X[k])
+    else:
+        rows, Jx = rows_jx
+    sh, sl = lam[:, :4] / (2 * w), lam[:, 4:] / (2 * w)
+    up = rows - hi[None, :, None] + sh
+    dn = lo[None, :, None] - rows + sl
+    vh, vl = np.maximum(0.0, up), np.maximum(0.0, dn)
+    summands = np.stack([w * vh ** 2, w * vl ** 2, -w * sh ** 2, -w * sl ** 2], axis=1)
+    active = (vh > 0).astype(float) + (vl > 0).astype(float)
+    grad = 2 * w * (vh - vl)[:, :, None, :] * Jx
+    curv = 2 * w * active[:, :, None, None, :] * Jx[:, :, :, None, :] * Jx[:, :, None, :, :]
+    return dict(summands=summands, terms=summands.sum(axis=0), sabs=np.abs(summands).sum(axis=0), grad=grad, curv=curv,
+                up=up, dn=dn, rows=rows, Jx=Jx)
+
+
+def envelope_excess(rows, lo, hi):
+    """The measure k_envelope_multipliers reports: per instance the largest unshifted bound excess over nodes and rows, each
+    row relative to its span hi - lo where that is a finite positive float32 number (else taken as it is); never below 0."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    span = hi - lo
+    sc = np.where((span > 0) & (span < 1e30), 1.0 / np.where(span > 0, span, 1.0), 1.0)
+    exc = np.maximum(rows - hi[None, :, None], lo[None, :, None] - rows) * sc[None, :, None]
+    return np.maximum(exc.max(axis=(0, 1)), 0.0)
+
+
 def envelope_al_update(rows, lo, hi, w, lam):
     """lam_hi <- max(0, lam_hi + 2w (g - hi)), lam_lo <- max(0, lam_lo + 2w (lo - g)); rows (Hn, 4, B) -> new lam (Hn, 8, B)"""
     up = rows - hi[None, :, None]

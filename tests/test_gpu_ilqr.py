@@ -279,6 +279,12 @@ def test_envelope_penalty_kernels_match_numpy(gpu):
     Hh = Hz.cpu().numpy()
     assert np.abs(Hh[:, :13, :13] - pw[:12]).max() <= 1e-4 * max(np.abs(pw).max(), 1.0)
     assert not Hh[:, 13:].any() and not Hh[:, :, 13:].any()
+    # ... and row by row (tests/envelope_ref.py): the curvature of every row meets the e32 condition on these inputs; the cost
+    # and the gradient do not (violations of a few ulp of the row: DESIGN.md section 5) and keep the lines above
+    from tests import envelope_ref as er
+    er.check_solver_rows("envelope_penalty_rows", lambda b: ILQR(system=ac, dt=0.01, num_nodes=12, cost=cost, alphas=(1.0, 0.5),
+                                                                 envelope_weight=3.0, envelope_bounds=b),
+                         X, None, lo, hi, 3.0, rows=(0, 1, 2, 3), quantities=("curv",))
 
 
 def test_envelope_al_kernels_match_numpy(gpu):
@@ -338,6 +344,12 @@ def test_envelope_al_kernels_match_numpy(gpu):
     ILQR(system=ac, dt=0.01, num_nodes=H, cost=cost, alphas=(1.0, 0.5), envelope_weight=w,
          envelope_bounds=il.envelope_bounds).envelope_cost(X, Jp)
     assert torch.equal(Ja, Jp)
+    # ... and row by row (tests/envelope_ref.py): with these multipliers the beta, alpha and height rows meet the e32 condition on
+    # cost, gradient and curvature; the speed row meets it on the curvature only
+    from tests import envelope_ref as er
+    make = lambda b: ILQR(system=ac, dt=0.01, num_nodes=H, cost=cost, alphas=(1.0, 0.5), envelope_weight=w, envelope="al", envelope_bounds=b)  # noqa: E731
+    er.check_solver_rows("envelope_al_rows", make, X, lam0, lo, hi, w, rows=(1, 2, 3), quantities=("cost", "grad", "curv"))
+    er.check_solver_rows("envelope_al_rows", make, X, lam0, lo, hi, w, rows=(0,), quantities=("curv",))
 
 
 def test_envelope_multipliers_enforce_what_the_penalty_leaves_violated(gpu):
