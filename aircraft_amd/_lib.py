@@ -135,6 +135,10 @@ PROTOTYPES = {
                                             _VP, _VP]),
     "ac_ilqr_backward_rate_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
                                             _VP, _VP, _VP, _VP]),
+    "ac_ilqr_backward_box_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP,
+                                           _VP, _VP, _VP, _VP]),
+    "ac_ilqr_backward_rate_box_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long,
+                                                _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ac_rollout_policy_rate_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _FP, C.c_int, C.c_float, C.c_long, C.c_long,
                                              _VP, _VP, _VP]),
     "ac_goal_model_rate_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -13,6 +13,10 @@ Everything stays on the device; torch supplies the buffers only (the acceptance 
 A control-RATE cost (`ILQR(rate_weight=)`, `GoalAcquisition(rate="exact")`) is modelled exactly: the Riccati pass carries the
 previous control as seven more states (ac_ilqr_backward_rate_f32, csrc/ac_ilqr_rate.hpp) and the closed loop feeds the control
 it applied at the previous node back through the gains Kp (ac_rollout_policy_rate_f32).
+
+The control box enters the backward pass with `ILQR(box="qp")` (control-limited DDP: a 7-variable QP per node,
+ac_ilqr_backward_box_f32 / ac_ilqr_backward_rate_box_f32, csrc/ac_boxqp.hpp); the default `box="clip"` leaves it to the clip of the
+closed-loop rollout.
 """
 from __future__ import annotations
 
@@ -88,8 +92,12 @@ class ILQR(MultipleShooting):
     def __init__(self, *, system, dt: float = 0.01, num_nodes: int, cost: QuadraticCost, opts: Optional[dict] = None,
                  alphas: Sequence[float] = (1.0, 0.5, 0.25, 0.1, 0.03), hessian: str = "gauss-newton",
                  envelope_weight: float = 0.0, envelope_bounds=None, envelope: str = "penalty",
-                 time: str = "fixed", dt_bounds=(0.005, 0.02), w_time: float = 0.0, r_time: float = 0.0, rate_weight=None):
-        """rate_weight (a scalar or 7 values, >= 0): adds the actuator-slew cost  1/2 sum_k sum_i w_i (u_k,i - u_{k-1},i)^2  —
+                 time: str = "fixed", dt_bounds=(0.005, 0.02), w_time: float = 0.0, r_time: float = 0.0, rate_weight=None,
+                 box: str = "clip"):
+        """box: 'clip' (the backward pass is unconstrained, the closed-loop rollout clips into [u_min, u_max]) or 'qp' (the box
+        in the backward pass too: per node  min 1/2 d'Quu d + Qu'd,  u_min - U_k <= d <= u_max - U_k;  kff is its solution, the
+        gains of clamped controls are zero; `last_active` / `qp_stat` report the active set and the QP's iteration counts).
+        rate_weight (a scalar or 7 values, >= 0): adds the actuator-slew cost  1/2 sum_k sum_i w_i (u_k,i - u_{k-1},i)^2  —
         plus the k = 0 term against `solve(u_prev=)` — to the objective (`trajectory_cost`), modelled exactly in the backward
         pass; the time row of time='variable' is excluded.
         hessian: 'gauss-newton' (first-order dynamics in the backward pass: iLQR) or 'exact' (adds the second-order
@@ -110,6 +118,8 @@ class ILQR(MultipleShooting):
         # force model ignores carries dt_k, boxed by dt_bounds, costed by w_time * dt_k (+ 1/2 r_time dt_k^2); the column of B
         # for it is c = dF/d(dt) from the sensitivity kernels.
         assert time in ("fixed", "variable")
+        assert box in ("clip", "qp"), "box: 'clip' or 'qp'"
+        self.box = box
         self.time_row = 0
         if time == "variable":
             assert hessian == "gauss-newton", "the exact-Hessian sweep keeps the fixed step"
@@ -152,6 +162,9 @@ class ILQR(MultipleShooting):
                 self._ws.update(dt=f(H, B), c=f(H, 13, B))
             if self._rate_exact:
                 self._ws.update(Kp=f(H, 7, 7, B), rate_g=f(H, 7, B), rate_h=f(H, 7, B))
+            if self.box == "qp":
+                self._ws.update(act=torch.zeros((H, 7, B), device=dev, dtype=torch.int8),
+                                stat=torch.zeros((2, B), device=dev, dtype=torch.int32))
             if self.hessian_mode == "exact":
                 self._ws.update(Lam=f(H, 13, B), Hz=f(H, 21, 21, B))
                 self.system._sync()
@@ -280,12 +293,62 @@ class ILQR(MultipleShooting):
 
     _goal_model = None  # GoalAcquisition sets it (see iterate)
 
-    def backward(self, X, U, A, Bm, out=None, Hz=None, node="auto", uglin=None, rate=None):
+    @property
+    def last_active(self):
+        """box='qp': the active set of the last backward pass, (N, 7, B) int8 — 0 free, -1 / +1 clamped at the lower / upper
+        bound, 2 pinned (u_min == u_max); None before the first iteration or with box='clip'."""
+        return self._ws.get("act") if self._ws is not None else None
+
+    @property
+    def qp_stat(self):
+        """box='qp': (2, B) int32 of the last backward pass — the largest Newton-iteration count over the instance's nodes, and
+        the number of nodes whose QP ended at an iteration cap."""
+        return self._ws.get("stat") if self._ws is not None else None
+
+    def _backward_box(self, X, U, A, Bm, out, Hz, node, uglin, rate):
+        torch = _torch()
+        lib = self.system._sync()
+        H, B = U.shape[0], U.shape[2]
+        n = 4 if rate is not None else 3
+        if out is None:
+            out = (torch.empty((H, 7, 13, B), device=X.device), torch.empty((H, 7, B), device=X.device),
+                   torch.empty((2, B), device=X.device))
+            if rate is not None:
+                out += (torch.empty((H, 7, 7, B), device=X.device),)
+        out = tuple(out)
+        if len(out) == n:
+            out += (torch.empty((H, 7, B), device=X.device, dtype=torch.int8),
+                    torch.empty((2, B), device=X.device, dtype=torch.int32))
+        assert len(out) == n + 2, "out: the outputs of the unboxed pass, then act (N, 7, B) int8 and stat (2, B) int32"
+        act, stat = out[n], out[n + 1]
+        assert act.dtype == torch.int8 and stat.dtype == torch.int32 and act.is_contiguous() and stat.is_contiguous()
+        hz = C.c_void_p(Hz.data_ptr() if Hz is not None else 0)
+        if rate is not None:
+            K, kff, dV, Kp = out[:4]
+            _lib.check(lib.ac_ilqr_backward_rate_box_f32(self.system._handle, self._cstruct(), *self._ptrs(node), hz,
+                                                         rate[0].data_ptr(), rate[1].data_ptr(), X.data_ptr(), U.data_ptr(),
+                                                         A.data_ptr(), Bm.data_ptr(), B, H, K.data_ptr(), Kp.data_ptr(),
+                                                         kff.data_ptr(), dV.data_ptr(), act.data_ptr(), stat.data_ptr(),
+                                                         self.system._stream()), "ac_ilqr_backward_rate_box_f32")
+            return out
+        K, kff, dV = out[:3]
+        if uglin is not None:
+            assert node is not None and Hz is not None
+        _lib.check(lib.ac_ilqr_backward_box_f32(self.system._handle, self._cstruct(), *self._ptrs(node),
+                                                C.c_void_p(uglin.data_ptr() if uglin is not None else 0), hz, X.data_ptr(),
+                                                U.data_ptr(), A.data_ptr(), Bm.data_ptr(), B, H, K.data_ptr(), kff.data_ptr(),
+                                                dV.data_ptr(), act.data_ptr(), stat.data_ptr(), self.system._stream()),
+                   "ac_ilqr_backward_box_f32")
+        return out
+
+    def backward(self, X, U, A, Bm, out=None, Hz=None, node="auto", uglin=None, rate=None, box=False):
         """Riccati pass -> K (N, 7, 13, B), kff (N, 7, B), dV (2, B).  Hz (N, 21, 21, B): optional second-order
         dynamics blocks from `hessian()` (exact-Hessian / Newton step).  uglin (N, 7, B): optional per-node control
         gradient (needs node arrays and Hz: ac_ilqr_backward_goal_f32).
         rate = (rate_g, rate_h), each (N, 7, B): the control-rate term per difference u_k - u_{k-1}, carried exactly
-        (ac_ilqr_backward_rate_f32) -> K, kff, dV, Kp (N, 7, 7, B); `out` then takes the four."""
+        (ac_ilqr_backward_rate_f32) -> K, kff, dV, Kp (N, 7, 7, B); `out` then takes the four.
+        box=True: the control box as a QP per node (ac_ilqr_backward_box_f32 / ac_ilqr_backward_rate_box_f32); the result — and
+        `out` — then carries act (N, 7, B) int8 and stat (2, B) int32 after the outputs above."""
         torch = _torch()
         lib = self.system._sync()
         H, B = U.shape[0], U.shape[2]
@@ -293,6 +356,9 @@ class ILQR(MultipleShooting):
             node = self._node_cost(X, U)
         if rate is not None:
             assert uglin is None, "the rate gradient arrives in `rate`"
+        if box:
+            return self._backward_box(X, U, A, Bm, out, Hz, node, uglin, rate)
+        if rate is not None:
             if out is None:
                 out = (torch.empty((H, 7, 13, B), device=X.device), torch.empty((H, 7, B), device=X.device),
                        torch.empty((2, B), device=X.device), torch.empty((H, 7, 7, B), device=X.device))
@@ -385,11 +451,15 @@ class ILQR(MultipleShooting):
             Hz = self.hessian(X, U, ws["Lam"], out=ws["Hz"])
         if env:
             self._envelope_model(X, Hz=Hz)
+        qp = self.box == "qp"
+        extra = (ws["act"], ws["stat"]) if qp else ()
         if rate is not None:
-            self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"], ws["Kp"]), Hz=Hz, node=node, rate=rate)
+            self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"], ws["Kp"]) + extra, Hz=Hz, node=node, rate=rate,
+                          box=qp)
             self.forward(x0, X, U, ws["K"], ws["kff"], out=(ws["Xc"], ws["Uc"]), Kp=ws["Kp"])
         else:
-            self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"]), Hz=Hz, node=node, uglin=uglin)
+            self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"]) + extra, Hz=Hz, node=node, uglin=uglin,
+                          box=qp)
             self.forward(x0, X, U, ws["K"], ws["kff"], out=(ws["Xc"], ws["Uc"]))
         self.trajectory_cost(ws["Xc"], ws["Uc"], out=ws["Jc"])
         self.trajectory_cost(X, U, out=ws["J0"])

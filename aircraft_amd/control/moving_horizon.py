@@ -203,7 +203,8 @@ class MHTT(ILQR):
         assert opts.get("time", "fixed") == "fixed", "can only run mhtt with fixed time"  # moving_horizon.py:35
         self.weights = weights or MHTTWeights()
         cost = QuadraticCost(r=[2.0 * self.weights.w_control] * 7, reg=reg)  # w_control * |u|^2 = 1/2 u' (2 w) u
-        super().__init__(system=system, dt=dt, num_nodes=num_nodes, cost=cost, opts=opts, alphas=alphas, hessian=hessian)
+        super().__init__(system=system, dt=dt, num_nodes=num_nodes, cost=cost, opts=opts, alphas=alphas, hessian=hessian,
+                         box=kwargs.get("box", "clip"))
         self.track = track
         self.track_length = track.length()
         assert self.track_length > 1e-6  # moving_horizon.py:155

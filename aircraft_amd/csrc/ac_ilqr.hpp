@@ -7,11 +7,14 @@
 //   cost      J = sum_k 1/2 (x_k - x_ref)' Q (x_k - x_ref) + 1/2 u_k' R u_k  +  1/2 (x_N - x_goal)' Qf (x_N - x_goal)
 //   backward  Q-function expansion with the kernel-computed A_k = dF/dx, B_k = dF/du (no second-order dynamics terms),
 //             Levenberg regularisation mu on Q_uu, gains  K_k = -Quu^-1 Qux,  k_k = -Quu^-1 Qu
+//             with BOX (control-limited DDP): k_k = argmin 1/2 d'Quu d + Qu'd over u_min - u_k <= d <= u_max - u_k (ac_boxqp.hpp),
+//             rows of K_k at clamped controls zero, the others from the free block of Quu
 //   forward   closed-loop rollout  u = clip(u_k + alpha k_k + K_k (x - x_k)),  several alpha per instance in one launch
 //
 // Layouts: X [H+1][13][B], U [H][7][B], A [H][13][13][B], Bm [H][13][7][B], K [H][7][13][B], kff [H][7][B].
 #pragma once
 #include "ac_kernels_analytic.hpp"
+#include "ac_boxqp.hpp"
 
 namespace ac {
 
@@ -78,6 +81,40 @@ template <bool NODE, bool NEWTON> struct IlqrRing {
     static_assert(kInstr * (kDepth - 1) <= 63, "vmcnt is a 6-bit counter");
 };
 
+// Outputs of the box-constrained pass (BOX, control-limited DDP: the control box enters the backward pass as a QP per node,
+// ac_boxqp.hpp) — an empty struct for the unconstrained kernels.
+template <bool BOX> struct IlqrBoxOut {};
+template <> struct IlqrBoxOut<true> {
+    signed char* __restrict__ act;  // [H][7][B] or NULL: 0 free, -1 / +1 clamped at the lower / upper bound, 2 pinned (u_min >= u_max)
+    int* __restrict__ stat;         // [2][B] or NULL: largest Newton-iteration count over the nodes, nodes whose QP hit a cap
+};
+
+// Per node of a BOX kernel: delta* of  min 1/2 d'Quu d + Qu'd,  u_min - U_k <= d <= u_max - U_k  becomes kff, and Quu is replaced
+// by its free block (unit rows and columns at the clamped controls) for the factorisation that gives the gains.
+struct IlqrBoxNode {
+    unsigned clamped = 0u;
+    int iters = 0, capped = 0;
+    AC_DI bool on(int i) const { return (clamped >> i) & 1u; }
+    AC_DI void solve(const IlqrCost& C, const float* u_k, const float (&Qs)[7][7], const float (&qu)[7], float (&Qf)[7][7],
+                     float (&kf)[7], signed char* act, long stride) {
+        float lo[7], hi[7];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) { lo[i] = C.u_min[i] - u_k[i]; hi[i] = C.u_max[i] - u_k[i]; }
+        BoxQp r;
+        boxqp7(Qs, qu, lo, hi, r);
+        clamped = r.clamped;
+        iters = iters > r.iters ? iters : r.iters;
+        capped += r.capped;
+        boxqp_mask(Qs, clamped, Qf);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) kf[i] = r.x[i];
+        if (act != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 7; ++i) act[i * stride] = (signed char)r.act(i);
+        }
+    }
+};
+
 AC_DI void ilqr_glds(const float* g, float* lds_dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                      (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
@@ -85,12 +122,13 @@ AC_DI void ilqr_glds(const float* g, float* lds_dst) {
 // wave-level hand-off through LDS (single-wave workgroup): LDS traffic retired, no reordering across this point
 AC_DI void ilqr_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 
-template <bool NODE, bool NEWTON>  // per-node cost arrays or the constant cost; second-order dynamics blocks or none
+// per-node cost arrays or the constant cost; second-order dynamics blocks or none; the control box as a QP per node or not at all
+template <bool NODE, bool NEWTON, bool BOX = false>
 __global__ __launch_bounds__(64) void k_ilqr_backward(const IlqrCost C, const NodeCost N, const float* __restrict__ X,
                                                       const float* __restrict__ U, const float* __restrict__ A,
                                                       const float* __restrict__ Bm, const float* __restrict__ Hz, long B, long H,
                                                       float* __restrict__ K, float* __restrict__ kff,
-                                                      float* __restrict__ dV) {
+                                                      float* __restrict__ dV, const IlqrBoxOut<BOX> box = {}) {
     typedef IlqrRing<NODE, NEWTON> R;
     __shared__ float smem[kIlqrWork + R::kDepth * R::kNodeFloats];  // ONE array: work area, then the node ring
     float* S = smem;
@@ -150,6 +188,7 @@ __global__ __launch_bounds__(64) void k_ilqr_backward(const IlqrCost C, const No
         for (int i = rb; i < 13; i += 4) sV[i * 13 + j] = (i == j) ? qterm : 0.f;
     }
     float dv1 = 0.f, dv2 = 0.f;
+    IlqrBoxNode bx;  // (BOX only)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     for (int d = 0; d < R::kDepth; ++d)
         if (H - 1 - d >= 0) issue(H - 1 - d, d);
@@ -258,10 +297,18 @@ __global__ __launch_bounds__(64) void k_ilqr_backward(const IlqrCost C, const No
         for (int i = 0; i < 7; ++i)
 #pragma unroll
             for (int m = 0; m <= i; ++m) { Qs[i][m] = 0.5f * (sQuu[i * 7 + m] + sQuu[m * 7 + i]); Qs[m][i] = Qs[i][m]; }
+        float Qf[7][7], kfb[7];  // BOX: the free block of Quu (unit rows / columns at the clamped controls) and delta*
+        if constexpr (BOX) {
+            float qub[7], uk[7];
+#pragma unroll
+            for (int i = 0; i < 7; ++i) { qub[i] = squ[i]; uk[i] = nd[273 + i]; }
+            bx.solve(C, uk, Qs, qub, Qf, kfb, (threadIdx.x == 0 && box.act != nullptr) ? box.act + (k * 7) * B + b : nullptr, B);
+        }
+        const float (&Qc)[7][7] = BOX ? Qf : Qs;  // what is factorised
         float L[7][7], rinv[7];
 #pragma unroll
         for (int m = 0; m < 7; ++m) {
-            float d = Qs[m][m];
+            float d = Qc[m][m];
 #pragma unroll
             for (int p = 0; p < m; ++p) d = fmaf(-L[m][p], L[m][p], d);
             d = fmaxf(d, 1e-12f);
@@ -270,7 +317,7 @@ __global__ __launch_bounds__(64) void k_ilqr_backward(const IlqrCost C, const No
             L[m][m] = d * rinv[m];
 #pragma unroll
             for (int i = m + 1; i < 7; ++i) {
-                float s = Qs[i][m];
+                float s = Qc[i][m];
 #pragma unroll
                 for (int p = 0; p < m; ++p) s = fmaf(-L[i][p], L[m][p], s);
                 L[i][m] = s * rinv[m];
@@ -295,16 +342,29 @@ __global__ __launch_bounds__(64) void k_ilqr_backward(const IlqrCost C, const No
         float kf[7], quv[7];
 #pragma unroll
         for (int i = 0; i < 7; ++i) { quv[i] = squ[i]; kf[i] = quv[i]; }
-        solve(kf);
+        if constexpr (BOX) {  // kff = delta*: exactly the bound minus U_k on a clamped row
 #pragma unroll
-        for (int i = 0; i < 7; ++i) kf[i] = -kf[i];
+            for (int i = 0; i < 7; ++i) kf[i] = kfb[i];
+        } else {
+            solve(kf);
+#pragma unroll
+            for (int i = 0; i < 7; ++i) kf[i] = -kf[i];
+        }
         float kcol[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (j < 13) {
 #pragma unroll
             for (int i = 0; i < 7; ++i) kcol[i] = sQux[i * 13 + j];
+            if constexpr (BOX) {
+#pragma unroll
+                for (int i = 0; i < 7; ++i) kcol[i] = bx.on(i) ? 0.f : kcol[i];
+            }
             solve(kcol);
 #pragma unroll
             for (int i = 0; i < 7; ++i) kcol[i] = -kcol[i];
+            if constexpr (BOX) {  // rows of K at clamped controls: +0.0f, not the -0.0f of the line above
+#pragma unroll
+                for (int i = 0; i < 7; ++i) kcol[i] = bx.on(i) ? 0.f : kcol[i];
+            }
             if (rb == 0) {
 #pragma unroll
                 for (int i = 0; i < 7; ++i) { sK[i * 13 + j] = kcol[i]; K[((k * 7 + i) * 13 + j) * B + b] = kcol[i]; }
@@ -378,6 +438,9 @@ __global__ __launch_bounds__(64) void k_ilqr_backward(const IlqrCost C, const No
         if (k - R::kDepth >= 0) issue(k - R::kDepth, slot);  // every read of this slot has retired (lgkmcnt(0) above)
     }
     if (threadIdx.x == 0) { dV[b] = dv1; dV[B + b] = dv2; }
+    if constexpr (BOX) {
+        if (threadIdx.x == 0 && box.stat != nullptr) { box.stat[b] = bx.iters; box.stat[B + b] = bx.capped; }
+    }
 }
 
 // ---- costate sweep ------------------------------------------------------------------------------------

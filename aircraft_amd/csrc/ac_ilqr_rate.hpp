@@ -34,13 +34,14 @@ template <bool NODE, bool NEWTON> struct IlqrRateRing {
     static_assert(kRate + 14 <= kNodeFloats, "node image");
 };
 
-template <bool NODE, bool NEWTON>
+template <bool NODE, bool NEWTON, bool BOX = false>  // BOX: the control box as a QP per node (IlqrBoxNode, ac_ilqr.hpp)
 __global__ __launch_bounds__(64) void k_ilqr_backward_rate(const IlqrCost C, const NodeCost N, const float* __restrict__ X,
                                                            const float* __restrict__ U, const float* __restrict__ A,
                                                            const float* __restrict__ Bm, const float* __restrict__ Hz,
                                                            const float* __restrict__ rate_g, const float* __restrict__ rate_h,
                                                            long B, long H, float* __restrict__ K, float* __restrict__ Kp,
-                                                           float* __restrict__ kff, float* __restrict__ dV) {
+                                                           float* __restrict__ kff, float* __restrict__ dV,
+                                                           const IlqrBoxOut<BOX> box = {}) {
     typedef IlqrRateRing<NODE, NEWTON> R;
     __shared__ float smem[kIlqrRateWork + R::kDepth * R::kNodeFloats];  // ONE array: work area, then the node ring
     float* S = smem;
@@ -107,6 +108,7 @@ __global__ __launch_bounds__(64) void k_ilqr_backward_rate(const IlqrCost C, con
         for (int i = rb; i < 7; i += 4) sVpp[i * 7 + j] = 0.f;
     }
     float dv1 = 0.f, dv2 = 0.f;
+    IlqrBoxNode bx;  // (BOX only)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     for (int d = 0; d < R::kDepth; ++d)
         if (H - 1 - d >= 0) issue(H - 1 - d, d);
@@ -218,10 +220,18 @@ __global__ __launch_bounds__(64) void k_ilqr_backward_rate(const IlqrCost C, con
         for (int i = 0; i < 7; ++i)
 #pragma unroll
             for (int m = 0; m <= i; ++m) { Qs[i][m] = 0.5f * (sQuu[i * 7 + m] + sQuu[m * 7 + i]); Qs[m][i] = Qs[i][m]; }
+        float Qf[7][7], kfb[7];  // BOX: the free block of Quu (unit rows / columns at the clamped controls) and delta*
+        if constexpr (BOX) {
+            float qub[7], uk[7];
+#pragma unroll
+            for (int i = 0; i < 7; ++i) { qub[i] = squ[i]; uk[i] = nd[273 + i]; }
+            bx.solve(C, uk, Qs, qub, Qf, kfb, (threadIdx.x == 0 && box.act != nullptr) ? box.act + (k * 7) * B + b : nullptr, B);
+        }
+        const float (&Qc)[7][7] = BOX ? Qf : Qs;  // what is factorised
         float L[7][7], rinv[7];
 #pragma unroll
         for (int m = 0; m < 7; ++m) {
-            float d = Qs[m][m];
+            float d = Qc[m][m];
 #pragma unroll
             for (int p = 0; p < m; ++p) d = fmaf(-L[m][p], L[m][p], d);
             d = fmaxf(d, 1e-12f);
@@ -230,7 +240,7 @@ __global__ __launch_bounds__(64) void k_ilqr_backward_rate(const IlqrCost C, con
             L[m][m] = d * rinv[m];
 #pragma unroll
             for (int i = m + 1; i < 7; ++i) {
-                float s = Qs[i][m];
+                float s = Qc[i][m];
 #pragma unroll
                 for (int p = 0; p < m; ++p) s = fmaf(-L[i][p], L[m][p], s);
                 L[i][m] = s * rinv[m];
@@ -255,16 +265,29 @@ __global__ __launch_bounds__(64) void k_ilqr_backward_rate(const IlqrCost C, con
         float kf[7], quv[7];
 #pragma unroll
         for (int i = 0; i < 7; ++i) { quv[i] = squ[i]; kf[i] = quv[i]; }
-        solve(kf);
+        if constexpr (BOX) {  // kff = delta*: exactly the bound minus U_k on a clamped row
 #pragma unroll
-        for (int i = 0; i < 7; ++i) kf[i] = -kf[i];
+            for (int i = 0; i < 7; ++i) kf[i] = kfb[i];
+        } else {
+            solve(kf);
+#pragma unroll
+            for (int i = 0; i < 7; ++i) kf[i] = -kf[i];
+        }
         float kcol[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (j < 13) {
 #pragma unroll
             for (int i = 0; i < 7; ++i) kcol[i] = sQux[i * 13 + j];
+            if constexpr (BOX) {
+#pragma unroll
+                for (int i = 0; i < 7; ++i) kcol[i] = bx.on(i) ? 0.f : kcol[i];
+            }
             solve(kcol);
 #pragma unroll
             for (int i = 0; i < 7; ++i) kcol[i] = -kcol[i];
+            if constexpr (BOX) {  // rows of K at clamped controls: +0.0f, not the -0.0f of the line above
+#pragma unroll
+                for (int i = 0; i < 7; ++i) kcol[i] = bx.on(i) ? 0.f : kcol[i];
+            }
             if (rb == 0) {
 #pragma unroll
                 for (int i = 0; i < 7; ++i) { sK[i * 13 + j] = kcol[i]; K[((k * 7 + i) * 13 + j) * B + b] = kcol[i]; }
@@ -274,9 +297,17 @@ __global__ __launch_bounds__(64) void k_ilqr_backward_rate(const IlqrCost C, con
         if (j < 7) {
 #pragma unroll
             for (int i = 0; i < 7; ++i) kpcol[i] = (i == j) ? -hj : 0.f;
+            if constexpr (BOX) {
+#pragma unroll
+                for (int i = 0; i < 7; ++i) kpcol[i] = bx.on(i) ? 0.f : kpcol[i];
+            }
             solve(kpcol);
 #pragma unroll
             for (int i = 0; i < 7; ++i) kpcol[i] = -kpcol[i];
+            if constexpr (BOX) {  // the same rows of Kp
+#pragma unroll
+                for (int i = 0; i < 7; ++i) kpcol[i] = bx.on(i) ? 0.f : kpcol[i];
+            }
             if (rb == 0) {
 #pragma unroll
                 for (int i = 0; i < 7; ++i) { sKp[i * 7 + j] = kpcol[i]; Kp[((k * 7 + i) * 7 + j) * B + b] = kpcol[i]; }
@@ -404,6 +435,9 @@ __global__ __launch_bounds__(64) void k_ilqr_backward_rate(const IlqrCost C, con
         if (k - R::kDepth >= 0) issue(k - R::kDepth, slot);  // every read of this slot has retired (lgkmcnt(0) above)
     }
     if (threadIdx.x == 0) { dV[b] = dv1; dV[B + b] = dv2; }
+    if constexpr (BOX) {
+        if (threadIdx.x == 0 && box.stat != nullptr) { box.stat[b] = bx.iters; box.stat[B + b] = bx.capped; }
+    }
 }
 
 // ---- quadratic rate cost  1/2 sum_k sum_i w_i (u_{k,i} - u_{k-1,i})^2,  u_{-1} = u_prev [7][Bn] (NULL: no k = 0 term) ----
@@ -424,6 +458,11 @@ __global__ __launch_bounds__(kBlock) void k_ilqr_rate_cost(const RateWeights W, 
 hipError_t ilqr_rate_launch_backward(const IlqrCost& C, const NodeCost& N, const float* X, const float* U, const float* A,
                                      const float* Bm, const float* Hz, const float* rate_g, const float* rate_h, long B, long H,
                                      float* K, float* Kp, float* kff, float* dV, hipStream_t st);
+// the eight BOX kernels (ilqr_box_inst.hip): k_ilqr_backward<NODE, NEWTON, true> (uglin travels in N) and
+// k_ilqr_backward_rate<NODE, NEWTON, true> when rate_g != NULL (Kp then too)
+hipError_t ilqr_box_launch_backward(const IlqrCost& C, const NodeCost& N, const float* X, const float* U, const float* A,
+                                    const float* Bm, const float* Hz, const float* rate_g, const float* rate_h, long B, long H,
+                                    float* K, float* Kp, float* kff, float* dV, signed char* act, int* stat, hipStream_t st);
 hipError_t ilqr_rate_launch_model(const RateWeights& W, const float* U, const float* u_prev, long B, long H, float* rate_g,
                                   float* rate_h, hipStream_t st, int* grid);
 hipError_t ilqr_rate_launch_cost(const RateWeights& W, const float* U, const float* u_prev, long Bn, long B, long H, float* cost,

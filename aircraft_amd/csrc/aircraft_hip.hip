@@ -1284,6 +1284,50 @@ int ac_ilqr_backward_rate_f32(ac_handle* h, const ac_ilqr_cost* cost, const floa
     return AC_OK;
 }
 
+// ---- the control box in the backward pass: a 7-variable QP per node (ac_boxqp.hpp; the eight kernels of ilqr_box_inst.hip) -------
+static bool box_ok(const ac_ilqr_cost* c) {
+    for (int i = 0; i < 7; ++i) {
+        const float lo = c->u_min[i], hi = c->u_max[i];
+        if (!(fabsf(lo) <= 3.4028235e38f) || !(fabsf(hi) <= 3.4028235e38f) || lo > hi) return false;
+    }
+    return true;
+}
+
+int ac_ilqr_backward_box_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
+                             const float* node_glin, const float* node_uglin, const float* Hz, const float* X, const float* U,
+                             const float* A, const float* Bm, long B, long H, float* K, float* kff, float* dV, signed char* act,
+                             int* stat, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !cost || !X || !U || !A || !Bm || !K || !kff || !dV || B < 0 || H < 1) return AC_ERR_BAD_ARG;
+    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
+    if (node_uglin && !(node_q && Hz)) return AC_ERR_BAD_ARG;
+    if (!box_ok(cost)) return AC_ERR_BAD_ARG;
+    NodeCost nc{node_q, node_xref, node_glin, B};
+    nc.uglin = node_uglin;
+    AC_HIP(ilqr_box_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, nullptr, nullptr, B, H, K, nullptr, kff, dV, act, stat,
+                                    (hipStream_t)stream));
+    note_launch(h, "k_ilqr_backward_box", (int)B, 64, 0);
+    return AC_OK;
+}
+
+int ac_ilqr_backward_rate_box_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
+                                  const float* node_glin, const float* Hz, const float* rate_g, const float* rate_h,
+                                  const float* X, const float* U, const float* A, const float* Bm, long B, long H, float* K,
+                                  float* Kp, float* kff, float* dV, signed char* act, int* stat, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !cost || !rate_g || !rate_h || !X || !U || !A || !Bm || !K || !Kp || !kff || !dV || B < 0 || H < 1)
+        return AC_ERR_BAD_ARG;
+    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
+    if (!box_ok(cost)) return AC_ERR_BAD_ARG;
+    const NodeCost nc{node_q, node_xref, node_glin, B};
+    AC_HIP(ilqr_box_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, rate_g, rate_h, B, H, K, Kp, kff, dV, act, stat,
+                                    (hipStream_t)stream));
+    note_launch(h, "k_ilqr_backward_rate_box", (int)B, 64, 0);
+    return AC_OK;
+}
+
 int ac_goal_model_rate_f32(ac_handle* h, const ac_goal_loss* loss, const float* goal, const float* lam, const float* X,
                            const float* U, long B, long H, float* node_q, float* node_xref, float* node_glin, float* rate_g,
                            float* rate_h, void* stream) {

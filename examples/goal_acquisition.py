@@ -7,13 +7,15 @@ polynomial coefficient model every reference driver uses (:166), the driver's ce
 velocity constraint v_x(N) < -2 — solved here for B random restarts at once (perturbed initial controls) by the iLQR sweep
 on the exact loss, where the reference hands ONE instance to IPOPT.  Prints the loss history (mean / best over the batch).
 
-    python examples/goal_acquisition.py [--batch 64] [--iters 12] [--time variable] [--rate exact]
+    python examples/goal_acquisition.py [--batch 64] [--iters 12] [--time variable] [--rate exact] [--box qp]
 
 --rate: how the backward pass models the control-rate term — frozen neighbours (the default) or exactly, with u_{k-1} carried
 through the Riccati pass.  The loss that is printed is the exact one either way.
 --reg: the Levenberg term on Q_uu; default 1 with --rate frozen, 100 with --rate exact.  The frozen model's 4e4 on the diagonal
 of Q_uu damps every step by itself; the exact model has no curvature along smooth control changes, and with reg = 1 its steps
 are too long for the line search on most restarts (profiles/goal_acquisition_rate_*.txt).
+--box: where the control box acts — clip (the default: in the closed-loop rollout only) or qp (in the backward pass too: a QP per
+node, control-limited DDP).
 """
 import argparse
 import os
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--time", choices=("fixed", "variable"), default="fixed")
     ap.add_argument("--rate", choices=("frozen", "exact"), default="frozen")
     ap.add_argument("--reg", type=float, default=None)
+    ap.add_argument("--box", choices=("clip", "qp"), default="clip")
     args = ap.parse_args()
     reg = args.reg if args.reg is not None else (100.0 if args.rate == "exact" else 1.0)
     import torch
@@ -51,15 +54,19 @@ def main():
     U0 = np.zeros((H, 7, B), dtype=np.float32)
     U0[:, :3] = rng.normal(0, 0.3, (1, 3, B))                      # random restarts: a constant offset on the three surfaces
     il = GoalAcquisition(system=ac, goal=(150.0, 0.0), dt=0.01, num_nodes=H, vel_param=1.0, time=args.time,
-                         alphas=(1.0, 0.5, 0.25, 0.1, 0.03), reg=reg, rate=args.rate)
+                         alphas=(1.0, 0.5, 0.25, 0.1, 0.03), reg=reg, rate=args.rate, box=args.box)
     X, U, hist = il.solve(x0, torch.from_numpy(U0).to(dev), iters=args.iters, al_every=4)
     h = hist.cpu().numpy()
     for i, row in enumerate(h):
-        print(f"[rate={args.rate} reg={reg:g}] sweep {i:2d}  loss mean {row.mean():14.1f}  best {row.min():14.1f}")
+        print(f"[rate={args.rate} reg={reg:g} box={args.box}] sweep {i:2d}  loss mean {row.mean():14.1f}  best {row.min():14.1f}")
     xN = X[-1].cpu().numpy()
     b = int(h[-1].argmin())
     print(f"best instance {b}: final p = ({xN[0, b]:.1f}, {xN[1, b]:.1f}, {xN[2, b]:.1f}) m, v = ({xN[3, b]:.1f}, {xN[4, b]:.1f}, {xN[5, b]:.1f}) m/s, "
           f"goal (150, 0); v_x(N) < -2 violated by {float(il.update_goal_multiplier(X)[b]):.2f} m/s")
+    if args.box == "qp":
+        act, stat = il.last_active.cpu().numpy(), il.qp_stat.cpu().numpy()
+        print(f"last backward pass: {((act == 1) | (act == -1))[:, :3].mean():.1%} of the surface entries clamped, "
+              f"most QP iterations {int(stat[0].max())}, nodes at a cap {int(stat[1].sum())}")
 
 
 if __name__ == "__main__":

@@ -377,6 +377,29 @@ int ac_ilqr_rate_model_f32(ac_handle* h, const float* rate_weight, const float* 
 int ac_ilqr_rate_cost_f32(ac_handle* h, const float* rate_weight, const float* u_prev, long Bn, const float* U, long B, long H,
                           float* cost_inout, void* stream);
 
+/* The control box IN the backward pass (control-limited DDP; Tassa, Mansard, Todorov, ICRA 2014).  The passes above solve the
+ * unconstrained  kff = -Quu^-1 Qu, K = -Quu^-1 Qux  and leave the box to the clip of the closed-loop rollout.  These two solve,
+ * per node,
+ *     min_d  1/2 d'Quu d + Qu'd     subject to   u_min - U_k <= d <= u_max - U_k        (fp32, projected Newton: csrc/ac_boxqp.hpp)
+ * and return  kff_k = d*,  rows of K_k (and Kp_k) at clamped controls exactly 0.0f, the other rows from the free block of Quu;
+ * V and dV follow from the general formulas with these gains.  A row with u_min >= u_max is pinned: always clamped.  With a
+ * feasible U, U + alpha kff is inside the box for every alpha in [0, 1].
+ *   ac_ilqr_backward_box_f32       ac_ilqr_backward_newton_f32 / _goal_f32: node arrays and Hz optional, node_uglin optional and
+ *                                  only with node arrays and Hz
+ *   ac_ilqr_backward_rate_box_f32  ac_ilqr_backward_rate_f32
+ * act  [H][7][B] int8 or NULL: 0 free, -1 clamped at the lower bound, +1 at the upper bound, 2 pinned.
+ * stat [2][B] int32 or NULL: the largest Newton-iteration count over the instance's nodes; the number of nodes whose QP ended at
+ *      a cap (16 iterations, 12 halvings) — the last iterate is kept there, feasible and no worse than the start.
+ * AC_ERR_BAD_ARG for u_min[i] > u_max[i] or a non-finite bound.  Asynchronous on the stream, no allocation, capturable. */
+int ac_ilqr_backward_box_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
+                             const float* node_glin, const float* node_uglin, const float* Hz, const float* X, const float* U,
+                             const float* A, const float* Bm, long B, long H, float* K, float* kff, float* dV, signed char* act,
+                             int* stat, void* stream);
+int ac_ilqr_backward_rate_box_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
+                                  const float* node_glin, const float* Hz, const float* rate_g, const float* rate_h,
+                                  const float* X, const float* U, const float* A, const float* Bm, long B, long H, float* K,
+                                  float* Kp, float* kff, float* dV, signed char* act, int* stat, void* stream);
+
 /* Exact-Hessian (Newton / SQP) variant of the sweep, for the force models ac_shoot_hess_f32 supports:
  *   ac_ilqr_costate_f32        Lam [H][13][B]: multipliers of the defect rows at the current iterate,
  *                              Lam[H-1] = grad l_N(x_N), Lam[k-1] = grad l_k(x_k) + A_k' Lam[k]
