@@ -139,6 +139,13 @@ PROTOTYPES = {
                                            _VP, _VP, _VP, _VP]),
     "ac_ilqr_backward_rate_box_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long,
                                                 _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ac_ilqr_backward_shoot_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP,
+                                             _VP, _VP, _VP, C.c_int, _VP, _VP, _VP]),
+    "ac_shoot_direction_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP,
+                                         _VP]),
+    "ac_shoot_merit_weight_f32": (C.c_int, [_VP, _VP, C.c_float, C.c_long, C.c_long, _VP, _VP]),
+    "ac_shoot_candidates_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _FP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP]),
+    "ac_shoot_merit_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP]),
     "ac_rollout_policy_rate_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _FP, C.c_int, C.c_float, C.c_long, C.c_long,
                                              _VP, _VP, _VP]),
     "ac_goal_model_rate_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP]),

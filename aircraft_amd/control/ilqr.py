@@ -17,6 +17,12 @@ it applied at the previous node back through the gains Kp (ac_rollout_policy_rat
 The control box enters the backward pass with `ILQR(box="qp")` (control-limited DDP: a 7-variable QP per node,
 ac_ilqr_backward_box_f32 / ac_ilqr_backward_rate_box_f32, csrc/ac_boxqp.hpp); the default `box="clip"` leaves it to the clip of the
 closed-loop rollout.
+
+`ILQR(shooting="multiple")` is Gauss-Newton multiple shooting (Giftthaler et al. 2018): the states of the iterate are decision
+variables, the gaps d_k = F(x_k, u_k) - x_{k+1} enter the Riccati pass (ac_ilqr_backward_shoot_f32), one forward sweep gives the
+direction (dX, dU) and the multipliers of the defect rows (ac_shoot_direction_f32), every line-search candidate X + alpha dX,
+clip(U + alpha dU) is evaluated as independent nodes in ONE step launch (ac_shoot_defect_f32), and the acceptance runs on the exact
+L1 merit  J + mu_b sum |defect|  (ac_shoot_merit_f32).  The default `shooting="single"` is the sweep described above, unchanged.
 """
 from __future__ import annotations
 
@@ -93,8 +99,12 @@ class ILQR(MultipleShooting):
                  alphas: Sequence[float] = (1.0, 0.5, 0.25, 0.1, 0.03), hessian: str = "gauss-newton",
                  envelope_weight: float = 0.0, envelope_bounds=None, envelope: str = "penalty",
                  time: str = "fixed", dt_bounds=(0.005, 0.02), w_time: float = 0.0, r_time: float = 0.0, rate_weight=None,
-                 box: str = "clip"):
-        """box: 'clip' (the backward pass is unconstrained, the closed-loop rollout clips into [u_min, u_max]) or 'qp' (the box
+                 box: str = "clip", shooting: str = "single", defect_weight: float = 1.0, merit_factor: float = 2.0):
+        """shooting: 'single' (the iterate is a rollout; line search by closed-loop rollouts) or 'multiple' (the states are decision
+        variables too: `solve(X0=)` takes a state guess, the defects x_{k+1} - F(x_k, u_k) are closed by the iteration; the line
+        search runs on the merit  J + mu_b sum |defect|  with  mu_b <- max(mu_b, merit_factor max |lambda|), mu_b = defect_weight
+        at the start of every solve; `last_multipliers`, `last_defect`, `merit_weight`, `defect_history`).
+        box: 'clip' (the backward pass is unconstrained, the closed-loop rollout clips into [u_min, u_max]) or 'qp' (the box
         in the backward pass too: per node  min 1/2 d'Quu d + Qu'd,  u_min - U_k <= d <= u_max - U_k;  kff is its solution, the
         gains of clamped controls are zero; `last_active` / `qp_stat` report the active set and the QP's iteration counts).
         rate_weight (a scalar or 7 values, >= 0): adds the actuator-slew cost  1/2 sum_k sum_i w_i (u_k,i - u_{k-1},i)^2  —
@@ -120,6 +130,15 @@ class ILQR(MultipleShooting):
         assert time in ("fixed", "variable")
         assert box in ("clip", "qp"), "box: 'clip' or 'qp'"
         self.box = box
+        assert shooting in ("single", "multiple"), "shooting: 'single' or 'multiple'"
+        self.shooting = shooting
+        self.defect_weight, self.merit_factor = float(defect_weight), float(merit_factor)
+        assert 0.0 < self.defect_weight < float("inf") and 0.0 <= self.merit_factor < float("inf"), "defect_weight > 0, merit_factor >= 0"
+        if shooting == "multiple":  # (each of these is a follow-up)
+            assert rate_weight is None, "shooting='multiple' does not take rate_weight yet (the rate kernels have no defect switch)"
+            assert time == "fixed", "shooting='multiple' keeps the fixed step (time='variable' is not supported yet)"
+            assert hessian == "gauss-newton", "shooting='multiple' is Gauss-Newton (hessian='exact' is not supported yet)"
+        self.defect_history = None
         self.time_row = 0
         if time == "variable":
             assert hessian == "gauss-newton", "the exact-Hessian sweep keeps the fixed step"
@@ -165,6 +184,10 @@ class ILQR(MultipleShooting):
             if self.box == "qp":
                 self._ws.update(act=torch.zeros((H, 7, B), device=dev, dtype=torch.int8),
                                 stat=torch.zeros((2, B), device=dev, dtype=torch.int32))
+            if self.shooting == "multiple":
+                self._ws.update(Vx=f(H, 13, B), Vxx=f(H, 13, 13, B), dX=f(H + 1, 13, B), dU=f(H, 7, B), Lam=f(H, 13, B),
+                                Rc=f(H, 13, na * B), phic=f(na * B), phi0=f(B), dinfc=f(na * B), dinf0=f(B),
+                                mu=torch.full((B,), self.defect_weight, device=dev, dtype=torch.float32))
             if self.hessian_mode == "exact":
                 self._ws.update(Lam=f(H, 13, B), Hz=f(H, 21, 21, B))
                 self.system._sync()
@@ -341,19 +364,147 @@ class ILQR(MultipleShooting):
                    "ac_ilqr_backward_box_f32")
         return out
 
-    def backward(self, X, U, A, Bm, out=None, Hz=None, node="auto", uglin=None, rate=None, box=False):
+    # ---- multiple shooting ---------------------------------------------------------------------------------------------------
+    @property
+    def last_multipliers(self):
+        """shooting='multiple': the multipliers of the defect rows of the last iteration's QP, (N, 13, B); None before it.
+        They are those of the sweep `iterate` runs, lam_k = V_x^{k+1} + V_xx^{k+1} dx_{k+1} with the control step CLIPPED into the
+        box: where no clip binds they are the multipliers of the equality-constrained QP exactly, where one binds they belong to the
+        clipped direction, not to the QP's solution."""
+        return self._ws.get("Lam") if self._shoot_done() else None
+
+    @property
+    def last_defect(self):
+        """shooting='multiple': (B,) the largest |x_{k+1} - F(x_k, u_k)| of the iterate the last iteration STARTED from (the end
+        of `solve` measures the final iterate); None before the first iteration."""
+        return self._ws.get("dinf0") if self._shoot_done() else None
+
+    @property
+    def merit_weight(self):
+        """shooting='multiple': (B,) the weight mu_b of the L1 defect term in the merit function.  Every `solve` starts it at
+        `defect_weight` and it never decreases within one; `GoalAcquisition.solve(al_every=)` is a sequence of solves (one per
+        block of sweeps between multiplier updates: the objective changes there), so it starts again with every block."""
+        return self._ws.get("mu") if (self._ws is not None and self.shooting == "multiple") else None
+
+    def _shoot_done(self):
+        """an iteration of this mode has filled the workspace (the buffers are uninitialised before)"""
+        return self._ws is not None and self.shooting == "multiple" and self._ws.get("shoot_done", False)
+
+    def _backward_shoot(self, X, U, A, Bm, F, out, Hz, node, uglin, box):
+        torch = _torch()
+        lib = self.system._sync()
+        H, B = U.shape[0], U.shape[2]
+        if out is None:
+            out = (torch.empty((H, 7, 13, B), device=X.device), torch.empty((H, 7, B), device=X.device),
+                   torch.empty((2, B), device=X.device), torch.empty((H, 13, B), device=X.device),
+                   torch.empty((H, 13, 13, B), device=X.device))
+        out = tuple(out)
+        if box and len(out) == 5:
+            out += (torch.empty((H, 7, B), device=X.device, dtype=torch.int8), torch.empty((2, B), device=X.device, dtype=torch.int32))
+        assert len(out) == (7 if box else 5), "out: K, kff, dV, Vx (N, 13, B), Vxx (N, 13, 13, B), then act and stat with box=True"
+        K, kff, dV, Vx, Vxx = out[:5]
+        assert (Vx is None) == (Vxx is None), "Vx and Vxx go together"
+        act, stat = (out[5], out[6]) if box else (None, None)
+        if box:
+            assert act.dtype == torch.int8 and stat.dtype == torch.int32 and act.is_contiguous() and stat.is_contiguous()
+        if uglin is not None:
+            assert node is not None and Hz is not None
+        vp = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
+        _lib.check(lib.ac_ilqr_backward_shoot_f32(self.system._handle, self._cstruct(), *self._ptrs(node), vp(uglin), vp(Hz),
+                                                  X.data_ptr(), U.data_ptr(), A.data_ptr(), Bm.data_ptr(), F.data_ptr(), B, H,
+                                                  K.data_ptr(), kff.data_ptr(), dV.data_ptr(), vp(Vx), vp(Vxx), 1 if box else 0,
+                                                  vp(act), vp(stat), self.system._stream()), "ac_ilqr_backward_shoot_f32")
+        return out
+
+    def direction(self, X, F, A, Bm, K, kff, Vx=None, Vxx=None, out=None, U=None):
+        """shooting='multiple': the forward sweep  dx_0 = 0, du_k = kff_k + K_k dx_k, dx_{k+1} = A_k dx_k + B_k du_k + F_k - x_{k+1}
+        -> dX (N+1, 13, B), dU (N, 7, B), Lam (N, 13, B) = Vx[k] + Vxx[k] dx_{k+1} (None without Vx / Vxx): the solution of the
+        equality-constrained QP of the iteration and the multipliers of its defect rows (ac_shoot_direction_f32).
+        U (N, 7, B): clip the control step as it is formed, du_k = clip(U_k + kff_k + K_k dx_k, u_min, u_max) - U_k, dX following
+        the clipped step — what `iterate` does, so that the candidates stay consistent where the box binds."""
+        torch = _torch()
+        lib = self.system._sync()
+        H, B = kff.shape[0], kff.shape[2]
+        assert (Vx is None) == (Vxx is None), "Vx and Vxx go together"
+        if out is None:
+            out = (torch.empty((H + 1, 13, B), device=X.device), torch.empty((H, 7, B), device=X.device),
+                   torch.empty((H, 13, B), device=X.device) if Vx is not None else None)
+        dX, dU, Lam = out
+        vp = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
+        _lib.check(lib.ac_shoot_direction_f32(self.system._handle, self._cstruct() if U is not None else None, X.data_ptr(), vp(U),
+                                              F.data_ptr(), A.data_ptr(), Bm.data_ptr(),
+                                              K.data_ptr(), kff.data_ptr(), vp(Vx), vp(Vxx), B, H, dX.data_ptr(), dU.data_ptr(),
+                                              vp(Lam if Vx is not None else None), self.system._stream()), "ac_shoot_direction_f32")
+        return dX, dU, (Lam if Vx is not None else None)
+
+    def _merit(self, J, mu, phi, dinf, R=None, F=None, X=None):
+        lib = self.system._sync()
+        src = R if R is not None else F
+        H, Bc = src.shape[0], src.shape[2]
+        vp = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
+        _lib.check(lib.ac_shoot_merit_f32(self.system._handle, J.data_ptr(), mu.data_ptr(), mu.shape[0], vp(R), vp(F), vp(X), Bc, H,
+                                          phi.data_ptr(), dinf.data_ptr(), self.system._stream()), "ac_shoot_merit_f32")
+        return phi, dinf
+
+    def _shoot_search(self, X, U, ws, env):
+        """Direction, merit weight, the candidates of every alpha as independent nodes, their merit, the acceptance."""
+        lib = self.system._sync()
+        H, B = U.shape[0], U.shape[2]
+        na = len(self.alphas)
+        self.direction(X, ws["F"], ws["A"], ws["Bm"], ws["K"], ws["kff"], ws["Vx"], ws["Vxx"], out=(ws["dX"], ws["dU"], ws["Lam"]),
+                       U=U)
+        _lib.check(lib.ac_shoot_merit_weight_f32(self.system._handle, ws["Lam"].data_ptr(), C.c_float(self.merit_factor), B, H,
+                                                 ws["mu"].data_ptr(), self.system._stream()), "ac_shoot_merit_weight_f32")
+        arr = (C.c_float * na)(*self.alphas)
+        _lib.check(lib.ac_shoot_candidates_f32(self.system._handle, self._cstruct(), X.data_ptr(), U.data_ptr(), ws["dX"].data_ptr(),
+                                               ws["dU"].data_ptr(), arr, na, B, H, ws["Xc"].data_ptr(), ws["Uc"].data_ptr(),
+                                               self.system._stream()), "ac_shoot_candidates_f32")
+        _lib.check(lib.ac_shoot_defect_f32(self.system._handle, ws["Xc"].data_ptr(), ws["Uc"].data_ptr(), C.c_float(self.dt),
+                                           C.c_void_p(0), na * B, H, ws["Rc"].data_ptr(), self.system._stream()),
+                   "ac_shoot_defect_f32")
+        self.trajectory_cost(ws["Xc"], ws["Uc"], out=ws["Jc"])
+        self.trajectory_cost(X, U, out=ws["J0"])
+        if env:
+            self.envelope_cost(ws["Xc"], ws["Jc"])
+            self.envelope_cost(X, ws["J0"])
+        self._merit(ws["Jc"], ws["mu"], ws["phic"], ws["dinfc"], R=ws["Rc"])
+        self._merit(ws["J0"], ws["mu"], ws["phi0"], ws["dinf0"], F=ws["F"], X=X)   # the iterate's own F: no second step evaluation
+        ws["shoot_done"] = True
+        return self.accept(ws["phic"], ws["phi0"], ws["Xc"], ws["Uc"], X, U)
+
+    def measure(self, X, U):
+        """shooting='multiple': (cost J (B,), largest |defect| (B,)) of an iterate — one step launch; fresh tensors."""
+        torch = _torch()
+        B = U.shape[2]
+        ws = self._workspace(B, U.device)
+        R = self.defects(X, U)
+        J = self.trajectory_cost(X, U).clone()
+        if self.envelope_weight > 0:
+            self.envelope_cost(X, J)
+        phi, dinf = torch.empty_like(J), torch.empty_like(J)
+        self._merit(J, ws["mu"], phi, dinf, R=R)
+        return J, dinf
+
+    def backward(self, X, U, A, Bm, out=None, Hz=None, node="auto", uglin=None, rate=None, box=False, shoot=None):
         """Riccati pass -> K (N, 7, 13, B), kff (N, 7, B), dV (2, B).  Hz (N, 21, 21, B): optional second-order
         dynamics blocks from `hessian()` (exact-Hessian / Newton step).  uglin (N, 7, B): optional per-node control
         gradient (needs node arrays and Hz: ac_ilqr_backward_goal_f32).
         rate = (rate_g, rate_h), each (N, 7, B): the control-rate term per difference u_k - u_{k-1}, carried exactly
         (ac_ilqr_backward_rate_f32) -> K, kff, dV, Kp (N, 7, 7, B); `out` then takes the four.
         box=True: the control box as a QP per node (ac_ilqr_backward_box_f32 / ac_ilqr_backward_rate_box_f32); the result — and
-        `out` — then carries act (N, 7, B) int8 and stat (2, B) int32 after the outputs above."""
+        `out` — then carries act (N, 7, B) int8 and stat (2, B) int32 after the outputs above.
+        shoot = F (N, 13, B), the step results F(x_k, u_k) of `linearise`: the pass over a multiple-shooting iterate, whose node k
+        reads V'_x + V'_xx (F_k - x_{k+1}) in place of V'_x (ac_ilqr_backward_shoot_f32) -> K, kff, dV, Vx (N, 13, B),
+        Vxx (N, 13, 13, B) — the value expansion node k starts from, what `direction` needs for the multipliers — then act, stat
+        with box=True; in `out`, Vx and Vxx may both be None."""
         torch = _torch()
         lib = self.system._sync()
         H, B = U.shape[0], U.shape[2]
         if isinstance(node, str):
             node = self._node_cost(X, U)
+        if shoot is not None:
+            assert rate is None, "the rate kernels have no defect switch"
+            return self._backward_shoot(X, U, A, Bm, shoot, out, Hz, node, uglin, box)
         if rate is not None:
             assert uglin is None, "the rate gradient arrives in `rate`"
         if box:
@@ -413,7 +564,9 @@ class ILQR(MultipleShooting):
         return Xc, Uc
 
     def iterate(self, x0, X, U):
-        """One iLQR iteration in place on (X, U).  Returns (cost (B,), improved (B,) bool)."""
+        """One iLQR iteration in place on (X, U).  Returns (cost (B,), improved (B,) bool).
+        shooting='multiple': X need not be the rollout of U; the first result is the accepted MERIT J + mu sum |defect|
+        (the cost and the defect of the iterate the iteration started from are left in the workspace: `last_defect`)."""
         torch = _torch()
         B = U.shape[2]
         ws = self._workspace(B, U.device)
@@ -453,6 +606,11 @@ class ILQR(MultipleShooting):
             self._envelope_model(X, Hz=Hz)
         qp = self.box == "qp"
         extra = (ws["act"], ws["stat"]) if qp else ()
+        if self.shooting == "multiple":
+            assert rate is None, "shooting='multiple' does not combine with rate='exact' yet"
+            self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"], ws["Vx"], ws["Vxx"]) + extra, Hz=Hz, node=node,
+                          uglin=uglin, box=qp, shoot=ws["F"])
+            return self._shoot_search(X, U, ws, env)
         if rate is not None:
             self.backward(X, U, ws["A"], ws["Bm"], out=(ws["K"], ws["kff"], ws["dV"], ws["Kp"]) + extra, Hz=Hz, node=node, rate=rate,
                           box=qp)
@@ -482,9 +640,37 @@ class ILQR(MultipleShooting):
                                           self.system._stream()), "ac_ilqr_accept_f32")
         return Ja, imp
 
+    def _solve_shoot(self, x0, U, X0, iters, save_to, save_instance, al_every):
+        torch = _torch()
+        H, B = U.shape[0], U.shape[2]
+        if X0 is None:
+            X = self.rollout(x0, U)
+        else:
+            assert tuple(X0.shape) == (H + 1, 13, B), "X0: (N + 1, 13, B)"
+            X = X0.to(device=U.device, dtype=torch.float32).clone().contiguous()
+            X[0].copy_(x0)
+        ws = self._workspace(B, U.device)
+        ws["mu"].fill_(self.defect_weight)
+        hist, dhist = [], []
+        if save_to:
+            self.save_progress(save_to, 0, X, U, save_instance, mode="w")
+        for it in range(iters):
+            self.iterate(x0, X, U)   # (J and the defect of the iterate it started from are by-products of its line search)
+            hist.append(ws["J0"].clone()); dhist.append(ws["dinf0"].clone())
+            if al_every and self.envelope_mode == "al" and (it + 1) % al_every == 0 and it + 1 < iters:
+                self.update_multipliers(X)
+            if save_to:
+                self.save_progress(save_to, it + 1, X, U, save_instance)
+        J, dinf = self.measure(X, U)
+        hist.append(J); dhist.append(dinf)
+        self.defect_history = torch.stack(dhist)
+        return X, U, torch.stack(hist)
+
     def solve(self, x0, U0, iters: int = 10, save_to: Optional[str] = None, save_instance: int = 0, al_every: int = 0,
-              u_prev=None):
+              u_prev=None, X0=None):
         """Rollout from x0 with U0, then `iters` iLQR iterations.  Returns (X, U, cost history (iters+1, B)).
+        shooting='multiple': X0 (N+1, 13, B) is the state guess (its row block 0 is overwritten with x0; None: the rollout, whose
+        gaps are rounding only); the history holds the COST J of every iterate, `defect_history` (iters+1, B) its largest |defect|.
         u_prev (7, B), with `rate_weight`: the control applied before the window; the rate cost then has a k = 0 term.
         `save_to` writes instance `save_instance` after every iteration in the reference's trajectory format
         (iteration_0 = the initial rollout), the role of the IPOPT callback in control/base.py:60-86.
@@ -496,6 +682,9 @@ class ILQR(MultipleShooting):
             assert tuple(u_prev.shape) == (7, U0.shape[2]), "u_prev: (7, B)"
             u_prev = u_prev.to(device=U0.device, dtype=torch.float32).contiguous()
         self._u_prev = u_prev
+        assert X0 is None or self.shooting == "multiple", "a state guess X0 needs ILQR(shooting='multiple')"
+        if self.shooting == "multiple":
+            return self._solve_shoot(x0, U, X0, iters, save_to, save_instance, al_every)
         if self.time_row > 0:
             U[:, self.time_row, :] = self.dt  # every node starts at the nominal step (the rollout below uses it)
         X = self.rollout(x0, U)
@@ -541,6 +730,7 @@ class GoalAcquisition(ILQR):
         super().__init__(system=system, dt=dt, num_nodes=num_nodes, cost=cost, time=time, w_time=w_time if time == "variable" else 0.0,
                          **kw)
         assert self.hessian_mode == "gauss-newton"
+        assert not (rate == "exact" and self.shooting == "multiple"), "shooting='multiple' does not combine with rate='exact' yet"
         self.rate_mode = rate
         if rate == "exact":
             self._rate_exact = True
@@ -622,10 +812,16 @@ class GoalAcquisition(ILQR):
         # multiplier updates between blocks of sweeps (the objective changes with them: monotone within a block)
         X, U, hist = super().solve(x0, U0, iters=min(al_every, iters), **kw)
         hists, done = [hist], min(al_every, iters)
+        dhs = [self.defect_history]
         while done < iters:
             self.update_goal_multiplier(X)
             n = min(al_every, iters - done)
+            if self.shooting == "multiple":
+                kw = dict(kw, X0=X)   # the iterate's states are decision variables: the next block starts from them
             X, U, h = super().solve(x0, U, iters=n, **kw)
             hists.append(h)
+            dhs.append(self.defect_history)
             done += n
+        if self.shooting == "multiple":
+            self.defect_history = torch.cat(dhs)
         return X, U, torch.cat(hists)

@@ -73,10 +73,11 @@ struct AlphaSet {
 //  * one wave = one workgroup, so LDS hand-offs need only lgkmcnt(0), never a cross-wave barrier.
 constexpr int kIlqrWork = 736;  // LDS floats of the per-instance work area (layout below)
 
-template <bool NODE, bool NEWTON> struct IlqrRing {
+template <bool NODE, bool NEWTON, bool SHOOT = false> struct IlqrRing {
     static constexpr bool kUglin = NODE && NEWTON;               // the control-gradient row (NodeCost::uglin) travels in the ring
-    static constexpr int kInstr = 6 + (NEWTON ? 7 : 0) + (kUglin ? 1 : 0);  // LDS-DMA wave-instructions per node
-    static constexpr int kNodeFloats = NEWTON ? 768 : 320;      // A 0..168, B 169..259, x 260, u 273, q 280, xref 293, glin 306, Hz 320..760, uglin 761..767
+    static constexpr int kInstr = 6 + (NEWTON ? 7 : 0) + (kUglin ? 1 : 0) + (SHOOT ? 1 : 0);  // LDS-DMA wave-instructions per node
+    static constexpr int kShoot = NEWTON ? 768 : 320;            // SHOOT: F_k at kShoot..+12, x_{k+1} at kShoot+13..+25
+    static constexpr int kNodeFloats = kShoot + (SHOOT ? 26 : 0);  // A 0..168, B 169..259, x 260, u 273, q 280, xref 293, glin 306, Hz 320..760, uglin 761..767
     static constexpr int kDepth = NEWTON ? 5 : 8;                // nodes in flight (kInstr * (kDepth - 1) <= 63)
     static_assert(kInstr * (kDepth - 1) <= 63, "vmcnt is a 6-bit counter");
 };
@@ -87,6 +88,18 @@ template <bool BOX> struct IlqrBoxOut {};
 template <> struct IlqrBoxOut<true> {
     signed char* __restrict__ act;  // [H][7][B] or NULL: 0 free, -1 / +1 clamped at the lower / upper bound, 2 pinned (u_min >= u_max)
     int* __restrict__ stat;         // [2][B] or NULL: largest Newton-iteration count over the nodes, nodes whose QP hit a cap
+};
+
+// Multiple shooting (SHOOT): the iterate's states are decision variables, node k has the gap  d_k = F_k - x_{k+1}  and the
+// linearised dynamics read  dx_{k+1} = A_k dx_k + B_k du_k + d_k.  The only change to the recursion: node k reads
+// v = V'_x + V'_xx d_k  wherever it read V'_x (in Q_x and Q_u).  F_k and x_{k+1} travel in the ring (ONE more LDS-DMA
+// wave-instruction per node).  Optionally the value expansion each node STARTS from is written out for the direction sweep
+// (k_shoot_direction: lam_k = V_x^{k+1} + V_xx^{k+1} dx_{k+1}) — an empty struct for the single-shooting kernels.
+template <bool SHOOT> struct IlqrShootIn {};
+template <> struct IlqrShootIn<true> {
+    const float* __restrict__ F;  // [H][13][B]: F(x_k, u_k)
+    float* __restrict__ Vx;       // [H][13][B] or NULL: Vx[k] = V_x^{k+1}
+    float* __restrict__ Vxx;      // [H][13][13][B] or NULL (both or neither): Vxx[k] = V_xx^{k+1}
 };
 
 // Per node of a BOX kernel: delta* of  min 1/2 d'Quu d + Qu'd,  u_min - U_k <= d <= u_max - U_k  becomes kff, and Quu is replaced
@@ -122,325 +135,33 @@ AC_DI void ilqr_glds(const float* g, float* lds_dst) {
 // wave-level hand-off through LDS (single-wave workgroup): LDS traffic retired, no reordering across this point
 AC_DI void ilqr_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 
-// per-node cost arrays or the constant cost; second-order dynamics blocks or none; the control box as a QP per node or not at all
+// per-node cost arrays or the constant cost; second-order dynamics blocks or none; the control box as a QP per node or not at all.
+// The body is ac_ilqr_backward_body.hpp, shared with k_ilqr_backward_shoot below (its SHOOT switch is AC_ILQR_SHOOT).
+// A textual include under a second kernel name, not a fourth template parameter and not a body function: the mangled names of
+// these kernels are pinned (tests/test_host_box.py looks for `Lb1EEEv`), a further parameter changes them, and a body inlined from
+// a function gives the existing kernels another schedule (the __restrict__ kernel arguments reach it as scoped alias information).
 template <bool NODE, bool NEWTON, bool BOX = false>
 __global__ __launch_bounds__(64) void k_ilqr_backward(const IlqrCost C, const NodeCost N, const float* __restrict__ X,
                                                       const float* __restrict__ U, const float* __restrict__ A,
                                                       const float* __restrict__ Bm, const float* __restrict__ Hz, long B, long H,
                                                       float* __restrict__ K, float* __restrict__ kff,
                                                       float* __restrict__ dV, const IlqrBoxOut<BOX> box = {}) {
-    typedef IlqrRing<NODE, NEWTON> R;
-    __shared__ float smem[kIlqrWork + R::kDepth * R::kNodeFloats];  // ONE array: work area, then the node ring
-    float* S = smem;
-    float* ring = smem + kIlqrWork;
-    const int t = threadIdx.x, rb = t >> 4, j = t & 15;
-    const long b = blockIdx.x;  // grid = B
-    float* sV = S;            // [13][13]
-    float* sVA = S + 169;     // [13][13]
-    float* sVB = S + 338;     // [13][7]
-    float* sQux = S + 429;    // [7][13]
-    float* sQuu = S + 520;    // [7][7]
-    float* sK = S + 569;      // [7][13]
-    float* svx = S + 660;     // [13]
-    float* sqx = S + 673;     // [13]
-    float* squ = S + 686;     // [7]
+#define AC_ILQR_SHOOT 0
+#include "ac_ilqr_backward_body.hpp"
+#undef AC_ILQR_SHOOT
+}
 
-    // gather node k into ring slot `slot` (wave-uniform); element e of an array lives B floats after element e-1
-    auto issue = [&](long k, int slot) {
-        float* dst = ring + slot * R::kNodeFloats;
-        const float* a = A + (k * 169) * B + b;
-        ilqr_glds(a + (long)t * B, dst);
-        ilqr_glds(a + (long)(t + 64) * B, dst + 64);
-        if (t < 169 - 128) ilqr_glds(a + (long)(t + 128) * B, dst + 128);
-        const float* bm = Bm + (k * 91) * B + b;
-        ilqr_glds(bm + (long)t * B, dst + 169);
-        if (t < 91 - 64) ilqr_glds(bm + (long)(t + 64) * B, dst + 169 + 64);
-        {   // lanes 0-12 x_k, 13-19 u_k, 20-32 q_k, 33-45 xref_k, 46-58 glin_k
-            const float* src = X + (k * 13 + t) * B + b;
-            if (t >= 13) src = U + (k * 7 + (t - 13)) * B + b;
-            if constexpr (NODE) {
-                if (t >= 20) src = N.q + (k * 13 + (t - 20)) * B + b;
-                if (t >= 33) src = N.xref + (k * 13 + (t - 33)) * B + b;
-                if (t >= 46) src = N.glin + (k * 13 + (t - 46)) * B + b;
-            }
-            if (t < (NODE ? 59 : 20)) ilqr_glds(src, dst + 260);
-        }
-        if constexpr (NEWTON) {
-            const float* hz = Hz + (k * 441) * B + b;
-#pragma unroll
-            for (int c = 0; c < 7; ++c)
-                if (c * 64 + t < 441) ilqr_glds(hz + (long)(c * 64 + t) * B, dst + 320 + c * 64);
-        }
-        if constexpr (R::kUglin) {  // (always issued, so that the vmcnt bookkeeping is static; without the array: u_k again, unused)
-            const float* ug = N.uglin ? N.uglin + (k * 7) * B + b : U + (k * 7) * B + b;
-            if (t < 7) ilqr_glds(ug + (long)t * B, dst + 761);
-        }
-    };
-    const float ug_on = (R::kUglin && N.uglin) ? 1.f : 0.f;
-
-    // terminal condition (ordinary loads, before any LDS-DMA is in flight)
-    float qterm = 0.f;
-    if (j < 13) {
-        const float xn = X[(H * 13 + j) * B + b];
-        float xr, gl;
-        N.template row<NODE>(C, H, true, j, b, qterm, xr, gl);
-        if (rb == 0) svx[j] = fmaf(qterm, xn - xr, gl);
-        for (int i = rb; i < 13; i += 4) sV[i * 13 + j] = (i == j) ? qterm : 0.f;
-    }
-    float dv1 = 0.f, dv2 = 0.f;
-    IlqrBoxNode bx;  // (BOX only)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    for (int d = 0; d < R::kDepth; ++d)
-        if (H - 1 - d >= 0) issue(H - 1 - d, d);
-    ilqr_sync();
-
-    for (long it = 0; it < H; ++it) {
-        const long k = H - 1 - it;
-        const int slot = (int)(it % R::kDepth);
-        // node k's gather has landed once at most (kDepth - 1) younger ones are outstanding; in the tail fewer were issued
-        if (it + R::kDepth - 1 < H) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(R::kInstr * (R::kDepth - 1)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        const float* nd = ring + slot * R::kNodeFloats;
-        const float* sA = nd;         // [13][13]
-        const float* sB = nd + 169;   // [13][7]
-        // stage gradients
-        float qjj = 0.f;  // diagonal entry j of the stage Hessian
-        if (j < 13) {
-            float xr = C.x_ref[j], gl = 0.f;
-            qjj = C.q[j];
-            if constexpr (NODE) { qjj = nd[280 + j]; xr = nd[293 + j]; gl = nd[306 + j]; }
-            if (rb == 0) sqx[j] = fmaf(qjj, nd[260 + j] - xr, gl);
-        }
-        if (j < 7 && rb == 0) {
-            float g = fmaf(C.r[j], nd[273 + j], C.u_lin[j]);
-            if constexpr (R::kUglin) g = fmaf(ug_on, nd[761 + j], g);
-            squ[j] = g;
-        }
-        ilqr_sync();
-        // This lane's columns of A_k and B_k stay in registers for the node (read once from the ring slot).
-        float acol[13], bcol[13];
-#pragma unroll
-        for (int m = 0; m < 13; ++m) {
-            acol[m] = (j < 13) ? sA[m * 13 + j] : 0.f;
-            bcol[m] = (j < 7) ? sB[m * 7 + j] : 0.f;
-        }
-        // VA = V A, VB = V B: one read of row i of V serves both products
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            const int i = rb + 4 * n;
-            if (i < 13) {
-                float sa = 0.f, sb = 0.f;
-#pragma unroll
-                for (int m = 0; m < 13; ++m) {
-                    const float v = sV[i * 13 + m];
-                    sa = fmaf(v, acol[m], sa);
-                    sb = fmaf(v, bcol[m], sb);
-                }
-                if (j < 13) sVA[i * 13 + j] = sa;
-                if (j < 7) sVB[i * 7 + j] = sb;
-            }
-        }
-        ilqr_sync();
-        // Qx, Qu (per column, every row group), Qxx rows of column j (registers), Qux, Quu
-        float qxx[4] = {0.f, 0.f, 0.f, 0.f};
-        float qx = 0.f, qu = 0.f;
-        const float* hz = nd + 320;  // [21][21] (NEWTON only)
-        {
-            float vacol[13], vbcol[13], vxs[13];  // column j of VA / VB, and V_x
-#pragma unroll
-            for (int m = 0; m < 13; ++m) {
-                vacol[m] = (j < 13) ? sVA[m * 13 + j] : 0.f;
-                vbcol[m] = (j < 7) ? sVB[m * 7 + j] : 0.f;
-                vxs[m] = svx[m];
-            }
-            qx = (j < 13) ? sqx[j] : 0.f;
-            qu = (j < 7) ? squ[j] : 0.f;
-#pragma unroll
-            for (int m = 0; m < 13; ++m) { qx = fmaf(acol[m], vxs[m], qx); qu = fmaf(bcol[m], vxs[m], qu); }
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                const int i = rb + 4 * n;
-                if (i < 13 && j < 13) {
-                    float s = (i == j) ? qjj : 0.f;
-                    if constexpr (NEWTON) s += hz[i * 21 + j];
-#pragma unroll
-                    for (int m = 0; m < 13; ++m) s = fmaf(sA[m * 13 + i], vacol[m], s);
-                    qxx[n] = s;
-                }
-            }
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const int i = rb + 4 * n;
-                if (i < 7) {  // column i of B_k serves row i of Qux and of Quu
-                    float sx = NEWTON ? ((j < 13) ? hz[(13 + i) * 21 + j] : 0.f) : 0.f;
-                    float su = (i == j) ? C.r[j < 7 ? j : 0] + C.reg : 0.f;
-                    if constexpr (NEWTON) su += (j < 7) ? hz[(13 + i) * 21 + 13 + j] : 0.f;
-#pragma unroll
-                    for (int m = 0; m < 13; ++m) {
-                        const float bi = sB[m * 7 + i];
-                        sx = fmaf(bi, vacol[m], sx);
-                        su = fmaf(bi, vbcol[m], su);
-                    }
-                    if (j < 13) sQux[i * 13 + j] = sx;
-                    if (j < 7) sQuu[i * 7 + j] = su;
-                }
-            }
-        }
-        ilqr_sync();  // Qux, Quu complete; sqx / squ / svx fully read
-        if (j < 7 && rb == 0) squ[j] = qu;  // now holds Qu
-        ilqr_sync();
-        // Cholesky Quu = L L' (every lane, in registers; reciprocal diagonal via rsq, no divisions), then
-        // K(:, j) = -Quu^-1 Qux(:, j), kff = -Quu^-1 Qu
-        float Qs[7][7];  // symmetrised Quu
-#pragma unroll
-        for (int i = 0; i < 7; ++i)
-#pragma unroll
-            for (int m = 0; m <= i; ++m) { Qs[i][m] = 0.5f * (sQuu[i * 7 + m] + sQuu[m * 7 + i]); Qs[m][i] = Qs[i][m]; }
-        float Qf[7][7], kfb[7];  // BOX: the free block of Quu (unit rows / columns at the clamped controls) and delta*
-        if constexpr (BOX) {
-            float qub[7], uk[7];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) { qub[i] = squ[i]; uk[i] = nd[273 + i]; }
-            bx.solve(C, uk, Qs, qub, Qf, kfb, (threadIdx.x == 0 && box.act != nullptr) ? box.act + (k * 7) * B + b : nullptr, B);
-        }
-        const float (&Qc)[7][7] = BOX ? Qf : Qs;  // what is factorised
-        float L[7][7], rinv[7];
-#pragma unroll
-        for (int m = 0; m < 7; ++m) {
-            float d = Qc[m][m];
-#pragma unroll
-            for (int p = 0; p < m; ++p) d = fmaf(-L[m][p], L[m][p], d);
-            d = fmaxf(d, 1e-12f);
-            rinv[m] = __builtin_amdgcn_rsqf(d);
-            rinv[m] = rinv[m] * fmaf(-0.5f * d * rinv[m], rinv[m], 1.5f);  // one Newton step: full fp32 accuracy
-            L[m][m] = d * rinv[m];
-#pragma unroll
-            for (int i = m + 1; i < 7; ++i) {
-                float s = Qc[i][m];
-#pragma unroll
-                for (int p = 0; p < m; ++p) s = fmaf(-L[i][p], L[m][p], s);
-                L[i][m] = s * rinv[m];
-            }
-        }
-        auto solve = [&](float rhs[7]) {  // in place: rhs <- Quu^-1 rhs
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                float s = rhs[i];
-#pragma unroll
-                for (int p = 0; p < i; ++p) s = fmaf(-L[i][p], rhs[p], s);
-                rhs[i] = s * rinv[i];
-            }
-#pragma unroll
-            for (int i = 6; i >= 0; --i) {
-                float s = rhs[i];
-#pragma unroll
-                for (int p = i + 1; p < 7; ++p) s = fmaf(-L[p][i], rhs[p], s);
-                rhs[i] = s * rinv[i];
-            }
-        };
-        float kf[7], quv[7];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) { quv[i] = squ[i]; kf[i] = quv[i]; }
-        if constexpr (BOX) {  // kff = delta*: exactly the bound minus U_k on a clamped row
-#pragma unroll
-            for (int i = 0; i < 7; ++i) kf[i] = kfb[i];
-        } else {
-            solve(kf);
-#pragma unroll
-            for (int i = 0; i < 7; ++i) kf[i] = -kf[i];
-        }
-        float kcol[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (j < 13) {
-#pragma unroll
-            for (int i = 0; i < 7; ++i) kcol[i] = sQux[i * 13 + j];
-            if constexpr (BOX) {
-#pragma unroll
-                for (int i = 0; i < 7; ++i) kcol[i] = bx.on(i) ? 0.f : kcol[i];
-            }
-            solve(kcol);
-#pragma unroll
-            for (int i = 0; i < 7; ++i) kcol[i] = -kcol[i];
-            if constexpr (BOX) {  // rows of K at clamped controls: +0.0f, not the -0.0f of the line above
-#pragma unroll
-                for (int i = 0; i < 7; ++i) kcol[i] = bx.on(i) ? 0.f : kcol[i];
-            }
-            if (rb == 0) {
-#pragma unroll
-                for (int i = 0; i < 7; ++i) { sK[i * 13 + j] = kcol[i]; K[((k * 7 + i) * 13 + j) * B + b] = kcol[i]; }
-            }
-        }
-        float quukf[7];  // Quu kff (every lane)
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            float t = 0.f;
-#pragma unroll
-            for (int m = 0; m < 7; ++m) t = fmaf(Qs[i][m], kf[m], t);
-            quukf[i] = t;
-        }
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                kff[(k * 7 + i) * B + b] = kf[i];
-                dv1 += kf[i] * quv[i];
-                dv2 += 0.5f * kf[i] * quukf[i];
-            }
-        }
-        ilqr_sync();  // sK visible
-        // V_x(j) = Qx + K' Quu kff + K' Qu + Qux' kff ;  V_xx(i, j) = Qxx + K' Quu K + K' Qux + Qux' K
-        float vx = 0.f, vrow[4] = {0.f, 0.f, 0.f, 0.f};
-        if (j < 13) {
-            float w[7], quxj[7];  // w = Quu K(:, j) + Qux(:, j)
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                float sq = 0.f;
-#pragma unroll
-                for (int m = 0; m < 7; ++m) sq = fmaf(Qs[i][m], kcol[m], sq);
-                quxj[i] = sQux[i * 13 + j];
-                w[i] = sq + quxj[i];
-            }
-            vx = qx;
-#pragma unroll
-            for (int i = 0; i < 7; ++i) vx += kcol[i] * (quukf[i] + quv[i]) + quxj[i] * kf[i];
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                const int i = rb + 4 * n;
-                if (i < 13) {
-                    float sv = qxx[n];
-#pragma unroll
-                    for (int m = 0; m < 7; ++m) sv += sK[m * 13 + i] * w[m] + sQux[m * 13 + i] * kcol[m];
-                    vrow[n] = sv;
-                }
-            }
-        }
-        ilqr_sync();  // every lane has read the old V / Qux before they are overwritten
-        if (j < 13) {
-            if (rb == 0) svx[j] = vx;
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-                if (rb + 4 * n < 13) sV[(rb + 4 * n) * 13 + j] = vrow[n];
-        }
-        ilqr_sync();
-        // symmetrise V: entry (i, j) <- mean with (j, i); both read before either is written
-        float sym[4] = {0.f, 0.f, 0.f, 0.f};
-        if (j < 13) {
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-                if (rb + 4 * n < 13) sym[n] = 0.5f * (vrow[n] + sV[j * 13 + rb + 4 * n]);
-        }
-        ilqr_sync();
-        if (j < 13) {
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-                if (rb + 4 * n < 13) sV[(rb + 4 * n) * 13 + j] = sym[n];
-        }
-        ilqr_sync();
-        if (k - R::kDepth >= 0) issue(k - R::kDepth, slot);  // every read of this slot has retired (lgkmcnt(0) above)
-    }
-    if (threadIdx.x == 0) { dV[b] = dv1; dV[B + b] = dv2; }
-    if constexpr (BOX) {
-        if (threadIdx.x == 0 && box.stat != nullptr) { box.stat[b] = bx.iters; box.stat[B + b] = bx.capped; }
-    }
+// the same pass over a multiple-shooting iterate (the eight kernels of ilqr_shoot_inst.hip)
+template <bool NODE, bool NEWTON, bool BOX>
+__global__ __launch_bounds__(64) void k_ilqr_backward_shoot(const IlqrCost C, const NodeCost N, const float* __restrict__ X,
+                                                            const float* __restrict__ U, const float* __restrict__ A,
+                                                            const float* __restrict__ Bm, const float* __restrict__ Hz, long B,
+                                                            long H, float* __restrict__ K, float* __restrict__ kff,
+                                                            float* __restrict__ dV, const IlqrShootIn<true> sh,
+                                                            const IlqrBoxOut<BOX> box = {}) {
+#define AC_ILQR_SHOOT 1
+#include "ac_ilqr_backward_body.hpp"
+#undef AC_ILQR_SHOOT
 }
 
 // ---- costate sweep ------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 #include "ac_ilqr.hpp"
 #include "ac_goal.hpp"
 #include "ac_ilqr_rate.hpp"
+#include "ac_shoot.hpp"
 #include "ac_track.hpp"
 #include "ac_hess.hpp"
 #include "ac_hess_adj.hpp"
@@ -1325,6 +1326,83 @@ int ac_ilqr_backward_rate_box_f32(ac_handle* h, const ac_ilqr_cost* cost, const 
     AC_HIP(ilqr_box_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, rate_g, rate_h, B, H, K, Kp, kff, dV, act, stat,
                                     (hipStream_t)stream));
     note_launch(h, "k_ilqr_backward_rate_box", (int)B, 64, 0);
+    return AC_OK;
+}
+
+// ---- Gauss-Newton multiple shooting: the defects in the Riccati pass, direction, candidates, merit (ac_shoot.hpp) -------------
+int ac_ilqr_backward_shoot_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
+                               const float* node_glin, const float* node_uglin, const float* Hz, const float* X, const float* U,
+                               const float* A, const float* Bm, const float* F, long B, long H, float* K, float* kff, float* dV,
+                               float* Vx, float* Vxx, int box, signed char* act, int* stat, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !cost || !X || !U || !A || !Bm || !F || !K || !kff || !dV || B < 0 || H < 1) return AC_ERR_BAD_ARG;
+    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
+    if (node_uglin && !(node_q && Hz)) return AC_ERR_BAD_ARG;
+    if ((Vx != nullptr) != (Vxx != nullptr)) return fail(AC_ERR_BAD_ARG, "ac_ilqr_backward_shoot_f32: Vx and Vxx go together");
+    if (box && !box_ok(cost)) return AC_ERR_BAD_ARG;
+    NodeCost nc{node_q, node_xref, node_glin, B};
+    nc.uglin = node_uglin;
+    AC_HIP(ilqr_shoot_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, F, B, H, K, kff, dV, Vx, Vxx, box != 0,
+                                      box ? act : nullptr, box ? stat : nullptr, (hipStream_t)stream));
+    note_launch(h, box ? "k_ilqr_backward_shoot_box" : "k_ilqr_backward_shoot", (int)B, 64, 0);
+    return AC_OK;
+}
+
+int ac_shoot_direction_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X, const float* U, const float* F, const float* A,
+                           const float* Bm, const float* K, const float* kff, const float* Vx, const float* Vxx, long B, long H,
+                           float* dX, float* dU, float* Lam, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !X || !F || !A || !Bm || !K || !kff || !dX || !dU || B < 0 || H < 1) return AC_ERR_BAD_ARG;
+    if ((Vx != nullptr) != (Vxx != nullptr)) return fail(AC_ERR_BAD_ARG, "ac_shoot_direction_f32: Vx and Vxx go together");
+    if (Lam && !Vx) return fail(AC_ERR_BAD_ARG, "ac_shoot_direction_f32: Lam needs Vx and Vxx");
+    if (limits && (!U || !box_ok(limits))) return fail(AC_ERR_BAD_ARG, "ac_shoot_direction_f32: limits need U and finite bounds, u_min <= u_max");
+    IlqrCost lim;
+    memset(&lim, 0, sizeof(lim));
+    if (limits) lim = to_dev_cost(limits);
+    int grid = 0;
+    AC_HIP(shoot_launch_direction(lim, limits != nullptr, X, U, F, A, Bm, K, kff, Vx, Vxx, B, H, dX, dU, Vx ? Lam : nullptr,
+                                  (hipStream_t)stream, &grid));
+    note_launch(h, "k_shoot_direction", grid, 64, 0);
+    return AC_OK;
+}
+
+int ac_shoot_merit_weight_f32(ac_handle* h, const float* Lam, float factor, long B, long H, float* mu, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !Lam || !mu || B < 0 || H < 1 || !(factor >= 0.f) || !(factor <= 3.4028235e38f)) return AC_ERR_BAD_ARG;
+    int grid = 0;
+    AC_HIP(shoot_launch_merit_weight(Lam, factor, B, H, mu, (hipStream_t)stream, &grid));
+    note_launch(h, "k_shoot_merit_weight", grid, kBlock, 0);
+    return AC_OK;
+}
+
+int ac_shoot_candidates_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X, const float* U, const float* dX,
+                            const float* dU, const float* alphas, int n_alpha, long B, long H, float* Xc, float* Uc, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !limits || !X || !U || !dX || !dU || !alphas || !Xc || !Uc || B < 0 || H < 1) return AC_ERR_BAD_ARG;
+    if (n_alpha < 1 || n_alpha > 8) return AC_ERR_BAD_ARG;
+    AlphaSet al;
+    al.n = n_alpha;
+    for (int i = 0; i < 8; ++i) al.a[i] = i < n_alpha ? alphas[i] : 0.f;
+    int grid = 0;
+    AC_HIP(shoot_launch_candidates(to_dev_cost(limits), X, U, dX, dU, al, B, H, Xc, Uc, (hipStream_t)stream, &grid));
+    note_launch(h, "k_shoot_candidates", grid, kBlock, 0);
+    return AC_OK;
+}
+
+int ac_shoot_merit_f32(ac_handle* h, const float* J, const float* mu, long Bn, const float* R, const float* F, const float* X,
+                       long B, long H, float* phi, float* defect_inf, void* stream) {
+    AC_ENTER(h);
+    if (h && B == 0) return AC_OK;
+    if (!h || !J || !mu || !phi || !defect_inf || B < 0 || H < 1 || Bn < 1 || B % Bn != 0) return AC_ERR_BAD_ARG;
+    if (!R && !(F && X)) return fail(AC_ERR_BAD_ARG, "ac_shoot_merit_f32: R, or F and X");
+    if (!R && Bn != B) return fail(AC_ERR_BAD_ARG, "ac_shoot_merit_f32: the (F, X) form is the iterate's: Bn == B");
+    int grid = 0;
+    AC_HIP(shoot_launch_merit(J, mu, Bn, R, F, X, B, H, phi, defect_inf, (hipStream_t)stream, &grid));
+    note_launch(h, "k_shoot_merit", grid, kBlock, 0);
     return AC_OK;
 }
 

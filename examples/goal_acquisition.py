@@ -8,6 +8,7 @@ velocity constraint v_x(N) < -2 — solved here for B random restarts at once (p
 on the exact loss, where the reference hands ONE instance to IPOPT.  Prints the loss history (mean / best over the batch).
 
     python examples/goal_acquisition.py [--batch 64] [--iters 12] [--time variable] [--rate exact] [--box qp]
+    python examples/goal_acquisition.py --shooting multiple [--guess rollout|line]
 
 --rate: how the backward pass models the control-rate term — frozen neighbours (the default) or exactly, with u_{k-1} carried
 through the Riccati pass.  The loss that is printed is the exact one either way.
@@ -16,6 +17,10 @@ of Q_uu damps every step by itself; the exact model has no curvature along smoot
 are too long for the line search on most restarts (profiles/goal_acquisition_rate_*.txt).
 --box: where the control box acts — clip (the default: in the closed-loop rollout only) or qp (in the backward pass too: a QP per
 node, control-limited DDP).
+--shooting multiple: Gauss-Newton multiple shooting — the states are decision variables too, the line search evaluates every
+candidate as independent nodes and runs on the merit  loss + mu sum |defect|; the loss and the largest defect are printed.
+--guess (with it): the state guess — rollout (of the initial controls: no gaps) or line (positions interpolated from the initial
+state to the goal at the initial height, every other row held at the initial state).
 """
 import argparse
 import os
@@ -36,6 +41,8 @@ def main():
     ap.add_argument("--rate", choices=("frozen", "exact"), default="frozen")
     ap.add_argument("--reg", type=float, default=None)
     ap.add_argument("--box", choices=("clip", "qp"), default="clip")
+    ap.add_argument("--shooting", choices=("single", "multiple"), default="single")
+    ap.add_argument("--guess", choices=("rollout", "line"), default="rollout")
     args = ap.parse_args()
     reg = args.reg if args.reg is not None else (100.0 if args.rate == "exact" else 1.0)
     import torch
@@ -54,11 +61,21 @@ def main():
     U0 = np.zeros((H, 7, B), dtype=np.float32)
     U0[:, :3] = rng.normal(0, 0.3, (1, 3, B))                      # random restarts: a constant offset on the three surfaces
     il = GoalAcquisition(system=ac, goal=(150.0, 0.0), dt=0.01, num_nodes=H, vel_param=1.0, time=args.time,
-                         alphas=(1.0, 0.5, 0.25, 0.1, 0.03), reg=reg, rate=args.rate, box=args.box)
-    X, U, hist = il.solve(x0, torch.from_numpy(U0).to(dev), iters=args.iters, al_every=4)
+                         alphas=(1.0, 0.5, 0.25, 0.1, 0.03), reg=reg, rate=args.rate, box=args.box, shooting=args.shooting)
+    kw = {}
+    if args.guess == "line":
+        assert args.shooting == "multiple", "--guess line needs --shooting multiple: single shooting takes no state guess"
+        s = torch.linspace(0.0, 1.0, H + 1, device=dev)[:, None]
+        X0 = x0[None].expand(H + 1, 13, B).clone()
+        X0[:, 0] = x0[0][None] + s * (150.0 - x0[0][None])
+        X0[:, 1] = x0[1][None] + s * (0.0 - x0[1][None])
+        kw["X0"] = X0
+    X, U, hist = il.solve(x0, torch.from_numpy(U0).to(dev), iters=args.iters, al_every=4, **kw)
     h = hist.cpu().numpy()
+    dh = il.defect_history.cpu().numpy() if args.shooting == "multiple" else None
     for i, row in enumerate(h):
-        print(f"[rate={args.rate} reg={reg:g} box={args.box}] sweep {i:2d}  loss mean {row.mean():14.1f}  best {row.min():14.1f}")
+        gap = f"  defect max {dh[i].max():10.3e}" if dh is not None else ""
+        print(f"[rate={args.rate} reg={reg:g} box={args.box} shooting={args.shooting}] sweep {i:2d}  loss mean {row.mean():14.1f}  best {row.min():14.1f}{gap}")
     xN = X[-1].cpu().numpy()
     b = int(h[-1].argmin())
     print(f"best instance {b}: final p = ({xN[0, b]:.1f}, {xN[1, b]:.1f}, {xN[2, b]:.1f}) m, v = ({xN[3, b]:.1f}, {xN[4, b]:.1f}, {xN[5, b]:.1f}) m/s, "

@@ -400,6 +400,39 @@ int ac_ilqr_backward_rate_box_f32(ac_handle* h, const ac_ilqr_cost* cost, const 
                                   const float* X, const float* U, const float* A, const float* Bm, long B, long H, float* K,
                                   float* Kp, float* kff, float* dV, signed char* act, int* stat, void* stream);
 
+/* Gauss-Newton multiple shooting (Giftthaler et al. 2018): the iterate is (X, U) with X[0] = x0, every state a decision variable;
+ * node k has the gap  d_k = F(x_k, u_k) - x_{k+1}  (ac_shoot_defect_f32 returns R_k = -d_k) and the linearised dynamics read
+ * dx_{k+1} = A_k dx_k + B_k du_k + d_k.
+ *   ac_ilqr_backward_shoot_f32  the backward pass of ac_ilqr_backward_newton_f32 / _goal_f32 (box == 0) or ac_ilqr_backward_box_f32
+ *                               (box != 0; act / stat are used only then) in which node k reads  v = V'_x + V'_xx d_k  in place of
+ *                               V'_x.  F [H][13][B] = F(x_k, u_k) (ac_shoot_sens_f32).  Vx [H][13][B], Vxx [H][13][13][B]: both or
+ *                               neither (NULL); Vx[k], Vxx[k] = the value expansion of node k + 1, which node k starts from.
+ *   ac_shoot_direction_f32      one forward sweep: dX [H+1][13][B] (dX[0] = 0), dU [H][7][B] = kff + K dx, the solution of the
+ *                               equality-constrained QP, and Lam [H][13][B] (NULL, or with Vx and Vxx) = Vx[k] + Vxx[k] dx_{k+1}, the
+ *                               multipliers of its defect rows.  limits (NULL, or with U [H][7][B]): the step of the controls
+ *                               is clipped as it is formed, du_k = clip(U_k + kff_k + K_k dx_k, u_min, u_max) - U_k, and dX follows
+ *                               the clipped step: for a feasible U every candidate U + alpha dU is then inside the box to a rounding.
+ *   ac_shoot_merit_weight_f32   mu[b] = max(mu[b], factor max_{k,i} |Lam[k][i][b]|): the L1 penalty weight, never decreasing.
+ *   ac_shoot_candidates_f32     column a B + b of Xc [H+1][13][n_alpha B], Uc [H][7][n_alpha B]:  Xc = X + alpha_a dX (row block 0:
+ *                               X[0] bit for bit),  Uc = clip(U + alpha_a dU, limits->u_min, limits->u_max).
+ *   ac_shoot_merit_f32          per column c of B:  phi[c] = J[c] + mu[c % Bn] sum_k sum_i |R[k][i][c]|  (rows in their order, no
+ *                               atomics),  defect_inf[c] = max |R|.  R [H][13][B] (ac_shoot_defect_f32), or R == NULL and the
+ *                               iterate's F [H][13][B], X [H+1][13][B] (then Bn == B): R = X[k+1] - F[k].  phi may be J.
+ * AC_ERR_BAD_ARG for a NULL required pointer or Vx without Vxx; B == 0 is AC_OK.  Asynchronous on the stream, no allocation,
+ * capturable. */
+int ac_ilqr_backward_shoot_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
+                               const float* node_glin, const float* node_uglin, const float* Hz, const float* X, const float* U,
+                               const float* A, const float* Bm, const float* F, long B, long H, float* K, float* kff, float* dV,
+                               float* Vx, float* Vxx, int box, signed char* act, int* stat, void* stream);
+int ac_shoot_direction_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X, const float* U, const float* F, const float* A,
+                           const float* Bm, const float* K, const float* kff, const float* Vx, const float* Vxx, long B, long H,
+                           float* dX, float* dU, float* Lam, void* stream);
+int ac_shoot_merit_weight_f32(ac_handle* h, const float* Lam, float factor, long B, long H, float* mu, void* stream);
+int ac_shoot_candidates_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X, const float* U, const float* dX,
+                            const float* dU, const float* alphas, int n_alpha, long B, long H, float* Xc, float* Uc, void* stream);
+int ac_shoot_merit_f32(ac_handle* h, const float* J, const float* mu, long Bn, const float* R, const float* F, const float* X,
+                       long B, long H, float* phi, float* defect_inf, void* stream);
+
 /* Exact-Hessian (Newton / SQP) variant of the sweep, for the force models ac_shoot_hess_f32 supports:
  *   ac_ilqr_costate_f32        Lam [H][13][B]: multipliers of the defect rows at the current iterate,
  *                              Lam[H-1] = grad l_N(x_N), Lam[k-1] = grad l_k(x_k) + A_k' Lam[k]
