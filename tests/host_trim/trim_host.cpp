@@ -2,6 +2,9 @@
 // together with the host-compilable state_derivative of the analytic models, behind a small C API, so that
 // `pytest -m "not gpu"` checks the assembly, the Jacobian J_z and the whole LM loop against the float64 oracle without a
 // GPU.  The derivative sensitivities are formed like the device's k_deriv_sens (state_derivative in Dual<4> lane groups).
+// For the step-by-step tests (tests/test_trim_steps_ref.py, tests/test_gpu_trim_steps.py): trim_residual_jacobian on given
+// sensitivities, trim_step and trim_final_status on given inputs (the fp32 side of e32), and the whole solve with what
+// the device's workspace holds after it.
 // TEST INFRASTRUCTURE: nothing in aircraft_amd loads this.
 #define AC_HOST_CHECK 1
 #include "../../aircraft_amd/csrc/ac_trim.hpp"
@@ -70,8 +73,12 @@ template <int MODEL> void jac(const DevParams& P, int lateral, const float* targ
 }
 
 // The device's launch sequence for one instance: assemble (init on the first iteration), f-sensitivities, update.
+// `ws` (optional): the device workspace of the same call, six arrays of [rows][n] (Xw, Uw, Xdot, Fx, Fu, LM state).
+struct TraceOut {
+    float *Xw, *Uw, *Xd, *Fx, *Fu, *St;
+};
 template <int MODEL> void loop(const DevParams& P, const ac_trim_opts& o, const float* target, const float* Uhold, const float* Z0,
-                               int iters, long n, float* X, float* U, float* Z, float* R, int* status) {
+                               int iters, long n, float* X, float* U, float* Z, float* R, int* status, const TraceOut* ws = nullptr) {
     for (long u = 0; u < n; ++u) {
         TrimTarget t;
         float uh[4], z0[6], st[kTrimStateWords], x[13], uv[7], xd[13], fx[169], fu[91], zo[6], ro[6];
@@ -83,6 +90,13 @@ template <int MODEL> void loop(const DevParams& P, const ac_trim_opts& o, const 
         for (int k = 0; k < iters; ++k) {
             if (trim_assemble_unit(o, t, uh, c, k == 0, x, uv)) unit_deriv_sens<MODEL>(P, x, uv, xd, fx, fu);
             trim_update_unit(o, t, TrimSens{xd, fx, fu, 1}, c, k == iters - 1, zo, ro, s);
+        }
+        if (ws) {
+            for (int i = 0; i < 13; ++i) { ws->Xw[i * n + u] = x[i]; ws->Xd[i * n + u] = xd[i]; }
+            for (int i = 0; i < 7; ++i) ws->Uw[i * n + u] = uv[i];
+            for (int i = 0; i < 169; ++i) ws->Fx[i * n + u] = fx[i];
+            for (int i = 0; i < 91; ++i) ws->Fu[i * n + u] = fu[i];
+            for (int i = 0; i < kTrimStateWords; ++i) ws->St[i * n + u] = st[i];
         }
         trim_assemble(t, o.lateral, zo, uh, x, uv);
         for (int i = 0; i < 13; ++i) X[i * n + u] = x[i];
@@ -131,4 +145,56 @@ extern "C" int host_trim(const ac_params* p, const float* linear_W, const float*
 #define AC_CALL(M_) loop<M_>(P, *o, target, Uhold, Z0, iters, n, X, U, Z, R, status)
     AC_TRIM_MODELS(AC_CALL)
 #undef AC_CALL
+}
+
+// the whole solve, and what the device's workspace holds after it: Xw [13][n], Uw [7][n], Xdot [13][n], Fx [169][n], Fu [91][n],
+// the LM state [kTrimStateWords][n]
+extern "C" int host_trim_trace(const ac_params* p, const float* linear_W, const float* poly_coef, const float* poly_intercept,
+                               const ac_trim_opts* o, const float* target, const float* Uhold, const float* Z0, int iters, long n, float* X,
+                               float* U, float* Z, float* R, int* status, float* Xw, float* Uw, float* Xd, float* Fx, float* Fu,
+                               float* St) {
+    const DevParams P = make_params(p, linear_W, poly_coef, poly_intercept);
+    const TraceOut ws{Xw, Uw, Xd, Fx, Fu, St};
+#define AC_CALL(M_) loop<M_>(P, *o, target, Uhold, Z0, iters, n, X, U, Z, R, status, &ws)
+    AC_TRIM_MODELS(AC_CALL)
+#undef AC_CALL
+}
+
+// trim_residual_jacobian on GIVEN sensitivities Xdot [13][n], Fx [13][13][n], Fu [13][7][n] (the strided read of the device):
+// r [6][n], J_z [6][6][n] at z [6][n]
+extern "C" int host_trim_chain(int lateral, const float* target, const float* Z, const float* Xd, const float* Fx, const float* Fu,
+                               long n, float* R, float* J) {
+    for (long u = 0; u < n; ++u) {
+        const TrimTarget t = trim_target(target, n, u);
+        float z[6], r[6], jz[36];
+        for (int j = 0; j < 6; ++j) z[j] = Z[j * n + u];
+        trim_residual_jacobian(t, lateral, z, TrimSens{Xd + u, Fx + u, Fu + u, n}, r, jz);
+        for (int i = 0; i < 6; ++i) R[i * n + u] = r[i];
+        for (int k = 0; k < 36; ++k) J[k * n + u] = jz[k];
+    }
+    return 0;
+}
+
+// trim_step: z [6][n], r [6][n], J [6][6][n], lambda [n] -> the next candidate [6][n]
+extern "C" int host_trim_step(const ac_trim_opts* o, const float* Z, const float* R, const float* J, const float* lam, long n,
+                              float* Zn) {
+    for (long u = 0; u < n; ++u) {
+        float z[6], r[6], jz[36], zn[6];
+        for (int j = 0; j < 6; ++j) { z[j] = Z[j * n + u]; r[j] = R[j * n + u]; }
+        for (int k = 0; k < 36; ++k) jz[k] = J[k * n + u];
+        trim_step(*o, z, r, jz, lam[u], zn);
+        for (int j = 0; j < 6; ++j) Zn[j * n + u] = zn[j];
+    }
+    return 0;
+}
+
+// trim_final_status of a still-active instance
+extern "C" int host_trim_final_status(const ac_trim_opts* o, const float* Z, const float* R, const float* J, long n, int* status) {
+    for (long u = 0; u < n; ++u) {
+        float z[6], r[6], jz[36];
+        for (int j = 0; j < 6; ++j) { z[j] = Z[j * n + u]; r[j] = R[j * n + u]; }
+        for (int k = 0; k < 36; ++k) jz[k] = J[k * n + u];
+        status[u] = trim_final_status(*o, z, r, jz);
+    }
+    return 0;
 }

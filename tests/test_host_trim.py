@@ -30,7 +30,13 @@ def _lib_host():
     L.host_trim_assemble.argtypes = [C.c_int, FP, FP, FP, C.c_long, FP, FP]
     L.host_trim_jacobian.argtypes = [C.c_void_p, FP, FP, FP, C.c_int, FP, FP, FP, C.c_long, FP, FP]
     L.host_trim.argtypes = [C.c_void_p, FP, FP, FP, C.c_void_p, FP, FP, FP, C.c_int, C.c_long, FP, FP, FP, FP, C.POINTER(C.c_int)]
-    for f in (L.host_trim_assemble, L.host_trim_jacobian, L.host_trim):
+    IP = C.POINTER(C.c_int)
+    L.host_trim_trace.argtypes = L.host_trim.argtypes + [FP] * 6
+    L.host_trim_chain.argtypes = [C.c_int, FP, FP, FP, FP, FP, C.c_long, FP, FP]
+    L.host_trim_step.argtypes = [C.c_void_p, FP, FP, FP, FP, C.c_long, FP]
+    L.host_trim_final_status.argtypes = [C.c_void_p, FP, FP, FP, C.c_long, IP]
+    for f in (L.host_trim_assemble, L.host_trim_jacobian, L.host_trim, L.host_trim_trace, L.host_trim_chain, L.host_trim_step,
+              L.host_trim_final_status):
         f.restype = C.c_int
     return L
 
