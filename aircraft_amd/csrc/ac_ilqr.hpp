@@ -71,15 +71,17 @@ struct AlphaSet {
 //    address, lane-linear LDS image) into a ring kRing nodes deep, several nodes ahead of the one being processed,
 //    with a counted s_waitcnt vmcnt(N): nothing in the loop waits on an ordinary global load;
 //  * one wave = one workgroup, so LDS hand-offs need only lgkmcnt(0), never a cross-wave barrier.
-constexpr int kIlqrWork = 736;  // LDS floats of the per-instance work area (layout below)
-
-template <bool NODE, bool NEWTON, bool SHOOT = false> struct IlqrRing {
-    static constexpr bool kUglin = NODE && NEWTON;               // the control-gradient row (NodeCost::uglin) travels in the ring
-    static constexpr int kInstr = 6 + (NEWTON ? 7 : 0) + (kUglin ? 1 : 0) + (SHOOT ? 1 : 0);  // LDS-DMA wave-instructions per node
+// RATE (k_ilqr_backward_rate, ac_ilqr_rate.hpp): g and h travel as one more 14-lane instruction per node; uglin does not.
+template <bool NODE, bool NEWTON, bool SHOOT = false, bool RATE = false> struct IlqrRing {
+    static constexpr int kWork = 736 + (RATE ? 208 : 0);         // LDS floats of the per-instance work area (layout in the body); RATE: then Vxp, Vpp, Kp, Vp
+    static constexpr bool kUglin = NODE && NEWTON && !RATE;      // the control-gradient row (NodeCost::uglin) travels in the ring
+    static constexpr int kInstr = 6 + (NEWTON ? 7 : 0) + (kUglin ? 1 : 0) + (SHOOT ? 1 : 0) + (RATE ? 1 : 0);  // LDS-DMA wave-instructions per node
     static constexpr int kShoot = NEWTON ? 768 : 320;            // SHOOT: F_k at kShoot..+12, x_{k+1} at kShoot+13..+25
-    static constexpr int kNodeFloats = kShoot + (SHOOT ? 26 : 0);  // A 0..168, B 169..259, x 260, u 273, q 280, xref 293, glin 306, Hz 320..760, uglin 761..767
+    static constexpr int kRate = NEWTON ? 761 : 320;             // RATE: g at kRate..+6, h at kRate+7..+13 (after Hz / after glin)
+    static constexpr int kNodeFloats = RATE ? (NEWTON ? 776 : 336) : kShoot + (SHOOT ? 26 : 0);  // A 0..168, B 169..259, x 260, u 273, q 280, xref 293, glin 306, Hz 320..760, uglin 761..767
     static constexpr int kDepth = NEWTON ? 5 : 8;                // nodes in flight (kInstr * (kDepth - 1) <= 63)
     static_assert(kInstr * (kDepth - 1) <= 63, "vmcnt is a 6-bit counter");
+    static_assert(!RATE || kRate + 14 <= kNodeFloats, "node image");
 };
 
 // Outputs of the box-constrained pass (BOX, control-limited DDP: the control box enters the backward pass as a QP per node,
@@ -136,8 +138,9 @@ AC_DI void ilqr_glds(const float* g, float* lds_dst) {
 AC_DI void ilqr_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 
 // per-node cost arrays or the constant cost; second-order dynamics blocks or none; the control box as a QP per node or not at all.
-// The body is ac_ilqr_backward_body.hpp, shared with k_ilqr_backward_shoot below (its SHOOT switch is AC_ILQR_SHOOT).
-// A textual include under a second kernel name, not a fourth template parameter and not a body function: the mangled names of
+// The body is ac_ilqr_backward_body.hpp, shared with k_ilqr_backward_shoot below (switch AC_ILQR_SHOOT) and with
+// k_ilqr_backward_rate of ac_ilqr_rate.hpp (switch AC_ILQR_RATE): one recursion, one ring, one Cholesky, one BOX hook.
+// A textual include under a further kernel name, not a fourth template parameter and not a body function: the mangled names of
 // these kernels are pinned (tests/test_host_box.py looks for `Lb1EEEv`), a further parameter changes them, and a body inlined from
 // a function gives the existing kernels another schedule (the __restrict__ kernel arguments reach it as scoped alias information).
 template <bool NODE, bool NEWTON, bool BOX = false>
@@ -147,11 +150,13 @@ __global__ __launch_bounds__(64) void k_ilqr_backward(const IlqrCost C, const No
                                                       float* __restrict__ K, float* __restrict__ kff,
                                                       float* __restrict__ dV, const IlqrBoxOut<BOX> box = {}) {
 #define AC_ILQR_SHOOT 0
+#define AC_ILQR_RATE 0
 #include "ac_ilqr_backward_body.hpp"
+#undef AC_ILQR_RATE
 #undef AC_ILQR_SHOOT
 }
 
-// the same pass over a multiple-shooting iterate (the eight kernels of ilqr_shoot_inst.hip)
+// the same pass over a multiple-shooting iterate
 template <bool NODE, bool NEWTON, bool BOX>
 __global__ __launch_bounds__(64) void k_ilqr_backward_shoot(const IlqrCost C, const NodeCost N, const float* __restrict__ X,
                                                             const float* __restrict__ U, const float* __restrict__ A,
@@ -160,9 +165,27 @@ __global__ __launch_bounds__(64) void k_ilqr_backward_shoot(const IlqrCost C, co
                                                             float* __restrict__ dV, const IlqrShootIn<true> sh,
                                                             const IlqrBoxOut<BOX> box = {}) {
 #define AC_ILQR_SHOOT 1
+#define AC_ILQR_RATE 0
 #include "ac_ilqr_backward_body.hpp"
+#undef AC_ILQR_RATE
 #undef AC_ILQR_SHOOT
 }
+
+// Everything a backward pass takes.  ilqr_launch_backward (ilqr_backward_inst.hip: all 24 kernels) picks the family by F / rate_g
+// (never both), BOX by `box`, NODE by N.q and NEWTON by Hz; the C entry points fill this and share ONE validation.
+struct IlqrBackwardArgs {
+    IlqrCost C;
+    NodeCost N;
+    const float *X, *U, *A, *Bm, *Hz;
+    const float *rate_g, *rate_h;  // k_ilqr_backward_rate when rate_g != NULL (Kp then too)
+    const float* F;                // k_ilqr_backward_shoot when F != NULL (Vx, Vxx optional)
+    long B, H;
+    float *K, *Kp, *kff, *dV, *Vx, *Vxx;
+    bool box;
+    signed char* act;  // (box only)
+    int* stat;         // (box only)
+};
+hipError_t ilqr_launch_backward(const IlqrBackwardArgs& a, hipStream_t st);
 
 // ---- costate sweep ------------------------------------------------------------------------------------
 // Multipliers of the defect rows x_{k+1} = F(x_k, u_k) at the current iterate (the NLP's lambda estimate):

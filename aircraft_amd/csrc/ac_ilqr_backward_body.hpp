@@ -1,11 +1,15 @@
-// (no include guard: on purpose) The body of the Riccati backward kernels of ac_ilqr.hpp, included once per kernel: k_ilqr_backward<NODE, NEWTON, BOX>
-// (AC_ILQR_SHOOT 0) and k_ilqr_backward_shoot<NODE, NEWTON, BOX> (AC_ILQR_SHOOT 1: the defects of multiple shooting, `sh`).
-// Textual, not a function both kernels call: the single-shooting kernels keep the names AND the code they had before the switch
-// existed (an inlined body changes how the compiler sees the __restrict__ kernel arguments, and with it the schedule).
-    typedef IlqrRing<NODE, NEWTON, AC_ILQR_SHOOT != 0> R;
-    __shared__ float smem[kIlqrWork + R::kDepth * R::kNodeFloats];  // ONE array: work area, then the node ring
+// (no include guard: on purpose) The ONE body of the Riccati backward kernels, included once per kernel under two switches:
+//   k_ilqr_backward<NODE, NEWTON, BOX>        (ac_ilqr.hpp)       AC_ILQR_SHOOT 0, AC_ILQR_RATE 0
+//   k_ilqr_backward_shoot<NODE, NEWTON, BOX>  (ac_ilqr.hpp)       AC_ILQR_SHOOT 1: the defects of multiple shooting, `sh`
+//   k_ilqr_backward_rate<NODE, NEWTON, BOX>   (ac_ilqr_rate.hpp)  AC_ILQR_RATE 1: u_{k-1} carried as seven more states (`rate_g`,
+//                                                                 `rate_h`, `Kp`; the formulas head ac_ilqr_rate.hpp)
+// Textual, not a function the kernels call: each kernel keeps the name AND the code it had before its switch existed (an inlined
+// body changes how the compiler sees the __restrict__ kernel arguments, and with it the schedule).
+    static_assert(!(AC_ILQR_SHOOT && AC_ILQR_RATE), "the rate terms over a multiple-shooting iterate are not written");
+    typedef IlqrRing<NODE, NEWTON, AC_ILQR_SHOOT != 0, AC_ILQR_RATE != 0> R;
+    __shared__ float smem[R::kWork + R::kDepth * R::kNodeFloats];  // ONE array: work area, then the node ring
     float* S = smem;
-    float* ring = smem + kIlqrWork;
+    float* ring = smem + R::kWork;
     const int t = threadIdx.x, rb = t >> 4, j = t & 15;
     const long b = blockIdx.x;  // grid = B
     float* sV = S;            // [13][13]
@@ -19,6 +23,12 @@
     float* squ = S + 686;     // [7]
 #if AC_ILQR_SHOOT
     float* svd = S + 693;     // [13]: v = V_x + V_xx d_k
+#endif
+#if AC_ILQR_RATE
+    float* sVxp = S + 736;    // [13][7]
+    float* sVpp = S + 827;    // [7][7]
+    float* sKp = S + 876;     // [7][7]
+    float* svp = S + 925;     // [7]
 #endif
 
     // gather node k into ring slot `slot` (wave-uniform); element e of an array lives B floats after element e-1
@@ -58,6 +68,12 @@
             if (t < 26) ilqr_glds(src, dst + R::kShoot);
         }
 #endif
+#if AC_ILQR_RATE
+        {  // lanes 0-6 g_k, 7-13 h_k
+            const float* src = (t < 7 ? rate_g + (k * 7 + t) * B : rate_h + (k * 7 + (t - 7)) * B) + b;
+            if (t < 14) ilqr_glds(src, dst + R::kRate);
+        }
+#endif
     };
     const float ug_on = (R::kUglin && N.uglin) ? 1.f : 0.f;
 
@@ -70,6 +86,13 @@
         if (rb == 0) svx[j] = fmaf(qterm, xn - xr, gl);
         for (int i = rb; i < 13; i += 4) sV[i * 13 + j] = (i == j) ? qterm : 0.f;
     }
+#if AC_ILQR_RATE
+    if (j < 7) {  // terminal: V_p = 0, V_xp = 0, V_pp = 0
+        if (rb == 0) svp[j] = 0.f;
+        for (int i = rb; i < 13; i += 4) sVxp[i * 7 + j] = 0.f;
+        for (int i = rb; i < 7; i += 4) sVpp[i * 7 + j] = 0.f;
+    }
+#endif
     float dv1 = 0.f, dv2 = 0.f;
     IlqrBoxNode bx;  // (BOX only)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -112,11 +135,18 @@
             }
         }
 #endif
+#if AC_ILQR_RATE
+        const float* srg = nd + R::kRate;      // [7] rate gradient
+        const float* srh = nd + R::kRate + 7;  // [7] rate curvature
+        const float gj = (j < 7) ? srg[j] : 0.f, hj = (j < 7) ? srh[j] : 0.f;
+        if (j < 7 && rb == 0) squ[j] = fmaf(C.r[j], nd[273 + j], C.u_lin[j]) + gj + svp[j];  // l_u + g + V'p
+#else
         if (j < 7 && rb == 0) {
             float g = fmaf(C.r[j], nd[273 + j], C.u_lin[j]);
             if constexpr (R::kUglin) g = fmaf(ug_on, nd[761 + j], g);
             squ[j] = g;
         }
+#endif
         ilqr_sync();
         // This lane's columns of A_k and B_k stay in registers for the node (read once from the ring slot).
         float acol[13], bcol[13];
@@ -148,10 +178,16 @@
         const float* hz = nd + 320;  // [21][21] (NEWTON only)
         {
             float vacol[13], vbcol[13], vxs[13];  // column j of VA / VB, and V_x
+#if AC_ILQR_RATE
+            float vxpcol[13];  // column j of V'xp (read in the loop below: a loop of its own gives the rate kernels another schedule)
+#endif
 #pragma unroll
             for (int m = 0; m < 13; ++m) {
                 vacol[m] = (j < 13) ? sVA[m * 13 + j] : 0.f;
                 vbcol[m] = (j < 7) ? sVB[m * 7 + j] : 0.f;
+#if AC_ILQR_RATE
+                vxpcol[m] = (j < 7) ? sVxp[m * 7 + j] : 0.f;
+#endif
 #if AC_ILQR_SHOOT
                 vxs[m] = svd[m];
 #else
@@ -176,26 +212,39 @@
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 const int i = rb + 4 * n;
-                if (i < 7) {  // column i of B_k serves row i of Qux and of Quu
+                if (i < 7) {  // column i of B_k (RATE: and of V'xp) serves row i of Qux and of Quu
                     float sx = NEWTON ? ((j < 13) ? hz[(13 + i) * 21 + j] : 0.f) : 0.f;
+#if AC_ILQR_RATE
+                    float su = (i == j) ? C.r[j < 7 ? j : 0] + C.reg + hj : 0.f;
+#else
                     float su = (i == j) ? C.r[j < 7 ? j : 0] + C.reg : 0.f;
+#endif
                     if constexpr (NEWTON) su += (j < 7) ? hz[(13 + i) * 21 + 13 + j] : 0.f;
+#if AC_ILQR_RATE
+                    su += (j < 7) ? sVpp[i * 7 + j] : 0.f;
+#endif
 #pragma unroll
                     for (int m = 0; m < 13; ++m) {
                         const float bi = sB[m * 7 + i];
                         sx = fmaf(bi, vacol[m], sx);
                         su = fmaf(bi, vbcol[m], su);
+#if AC_ILQR_RATE
+                        const float pi = sVxp[m * 7 + i];
+                        sx = fmaf(pi, acol[m], sx);     // V'px A
+                        su = fmaf(bi, vxpcol[m], su);   // B'V'xp
+                        su = fmaf(pi, bcol[m], su);     // V'px B
+#endif
                     }
                     if (j < 13) sQux[i * 13 + j] = sx;
                     if (j < 7) sQuu[i * 7 + j] = su;
                 }
             }
         }
-        ilqr_sync();  // Qux, Quu complete; sqx / squ / svx fully read
+        ilqr_sync();  // Qux, Quu complete; sqx / squ / svx (/ svp) fully read
         if (j < 7 && rb == 0) squ[j] = qu;  // now holds Qu
         ilqr_sync();
-        // Cholesky Quu = L L' (every lane, in registers; reciprocal diagonal via rsq, no divisions), then
-        // K(:, j) = -Quu^-1 Qux(:, j), kff = -Quu^-1 Qu
+        // Cholesky Quu = L L' once (every lane, in registers; reciprocal diagonal via rsq, no divisions), then
+        // K(:, j) = -Quu^-1 Qux(:, j), kff = -Quu^-1 Qu (RATE: and Kp(:, j), 13 + 7 + 1 right-hand sides)
         float Qs[7][7];  // symmetrised Quu
 #pragma unroll
         for (int i = 0; i < 7; ++i)
@@ -274,6 +323,28 @@
                 for (int i = 0; i < 7; ++i) { sK[i * 13 + j] = kcol[i]; K[((k * 7 + i) * 13 + j) * B + b] = kcol[i]; }
             }
         }
+#if AC_ILQR_RATE
+        float kpcol[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // Kp(:, j) = -Quu^-1 Qup(:, j),  Qup(:, j) = -h_j e_j
+        if (j < 7) {
+#pragma unroll
+            for (int i = 0; i < 7; ++i) kpcol[i] = (i == j) ? -hj : 0.f;
+            if constexpr (BOX) {
+#pragma unroll
+                for (int i = 0; i < 7; ++i) kpcol[i] = bx.on(i) ? 0.f : kpcol[i];
+            }
+            solve(kpcol);
+#pragma unroll
+            for (int i = 0; i < 7; ++i) kpcol[i] = -kpcol[i];
+            if constexpr (BOX) {  // the same rows of Kp
+#pragma unroll
+                for (int i = 0; i < 7; ++i) kpcol[i] = bx.on(i) ? 0.f : kpcol[i];
+            }
+            if (rb == 0) {
+#pragma unroll
+                for (int i = 0; i < 7; ++i) { sKp[i * 7 + j] = kpcol[i]; Kp[((k * 7 + i) * 7 + j) * B + b] = kpcol[i]; }
+            }
+        }
+#endif
         float quukf[7];  // Quu kff (every lane)
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
@@ -290,7 +361,7 @@
                 dv2 += 0.5f * kf[i] * quukf[i];
             }
         }
-        ilqr_sync();  // sK visible
+        ilqr_sync();  // sK (and sKp) visible
         // V_x(j) = Qx + K' Quu kff + K' Qu + Qux' kff ;  V_xx(i, j) = Qxx + K' Quu K + K' Qux + Qux' K
         float vx = 0.f, vrow[4] = {0.f, 0.f, 0.f, 0.f};
         if (j < 13) {
@@ -317,6 +388,44 @@
                 }
             }
         }
+#if AC_ILQR_RATE
+        // V_p(j), V_xp(:, j), V_pp(:, j) from Kp(:, j) the same way
+        float vp = 0.f, vxprow[4] = {0.f, 0.f, 0.f, 0.f}, vpprow[2] = {0.f, 0.f};
+        if (j < 7) {
+            float wp[7];  // wp = Quu Kp(:, j) + Qup(:, j)
+#pragma unroll
+            for (int i = 0; i < 7; ++i) {
+                float sq = 0.f;
+#pragma unroll
+                for (int m = 0; m < 7; ++m) sq = fmaf(Qs[i][m], kpcol[m], sq);
+                wp[i] = sq + ((i == j) ? -hj : 0.f);
+            }
+            vp = -gj;
+#pragma unroll
+            for (int i = 0; i < 7; ++i) vp += kpcol[i] * (quukf[i] + quv[i]) + ((i == j) ? -hj * kf[i] : 0.f);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int i = rb + 4 * n;
+                if (i < 13) {
+                    float sv = 0.f;
+#pragma unroll
+                    for (int m = 0; m < 7; ++m) sv += sK[m * 13 + i] * wp[m] + sQux[m * 13 + i] * kpcol[m];
+                    vxprow[n] = sv;
+                }
+            }
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                const int i = rb + 4 * n;
+                if (i < 7) {
+                    float sv = (i == j) ? hj : 0.f;
+#pragma unroll
+                    for (int m = 0; m < 7; ++m) sv += sKp[m * 7 + i] * wp[m];
+                    sv -= srh[i] * sKp[i * 7 + j];   // Qup' Kp: row i of Qup' is -h_i e_i'
+                    vpprow[n] = sv;
+                }
+            }
+        }
+#endif
         ilqr_sync();  // every lane has read the old V / Qux before they are overwritten
         if (j < 13) {
             if (rb == 0) svx[j] = vx;
@@ -324,20 +433,46 @@
             for (int n = 0; n < 4; ++n)
                 if (rb + 4 * n < 13) sV[(rb + 4 * n) * 13 + j] = vrow[n];
         }
+#if AC_ILQR_RATE
+        if (j < 7) {
+            if (rb == 0) svp[j] = vp;
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+                if (rb + 4 * n < 13) sVxp[(rb + 4 * n) * 7 + j] = vxprow[n];
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+                if (rb + 4 * n < 7) sVpp[(rb + 4 * n) * 7 + j] = vpprow[n];
+        }
+#endif
         ilqr_sync();
-        // symmetrise V: entry (i, j) <- mean with (j, i); both read before either is written
+        // symmetrise V (RATE: and V_pp): entry (i, j) <- mean with (j, i); both read before either is written
         float sym[4] = {0.f, 0.f, 0.f, 0.f};
         if (j < 13) {
 #pragma unroll
             for (int n = 0; n < 4; ++n)
                 if (rb + 4 * n < 13) sym[n] = 0.5f * (vrow[n] + sV[j * 13 + rb + 4 * n]);
         }
+#if AC_ILQR_RATE
+        float symp[2] = {0.f, 0.f};
+        if (j < 7) {
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+                if (rb + 4 * n < 7) symp[n] = 0.5f * (vpprow[n] + sVpp[j * 7 + rb + 4 * n]);
+        }
+#endif
         ilqr_sync();
         if (j < 13) {
 #pragma unroll
             for (int n = 0; n < 4; ++n)
                 if (rb + 4 * n < 13) sV[(rb + 4 * n) * 13 + j] = sym[n];
         }
+#if AC_ILQR_RATE
+        if (j < 7) {
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+                if (rb + 4 * n < 7) sVpp[(rb + 4 * n) * 7 + j] = symp[n];
+        }
+#endif
         ilqr_sync();
         if (k - R::kDepth >= 0) issue(k - R::kDepth, slot);  // every read of this slot has retired (lgkmcnt(0) above)
     }

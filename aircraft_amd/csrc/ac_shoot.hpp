@@ -2,7 +2,7 @@
 // Gauss-Newton shooting methods"): launchers of the kernels of ilqr_shoot_inst.hip.
 //
 // The iterate is (X, U) with X[0] = x0; node k has the gap  d_k = F(x_k, u_k) - x_{k+1}  (ac_shoot_defect_f32 returns R_k = -d_k).
-//   backward   k_ilqr_backward_shoot<NODE, NEWTON, BOX> (ac_ilqr.hpp): node k reads  v = V'_x + V'_xx d_k  in place of V'_x
+//   backward   k_ilqr_backward_shoot<NODE, NEWTON, BOX> (ac_ilqr.hpp, ilqr_backward_inst.hip): node k reads  v = V'_x + V'_xx d_k  in place of V'_x
 //   direction  dx_0 = 0,  du_k = kff_k + K_k dx_k (optionally clipped so that U + du stays in the box),
 //              dx_{k+1} = A_k dx_k + B_k du_k + d_k,  lam_k = V_x^{k+1} + V_xx^{k+1} dx_{k+1}
 //              — the solution of the equality-constrained QP and the multipliers of its defect rows
@@ -13,9 +13,6 @@
 
 namespace ac {
 
-hipError_t ilqr_shoot_launch_backward(const IlqrCost& C, const NodeCost& N, const float* X, const float* U, const float* A,
-                                      const float* Bm, const float* Hz, const float* F, long B, long H, float* K, float* kff,
-                                      float* dV, float* Vx, float* Vxx, bool box, signed char* act, int* stat, hipStream_t st);
 hipError_t shoot_launch_direction(const IlqrCost& C, bool clip, const float* X, const float* U, const float* F, const float* A,
                                   const float* Bm, const float* K, const float* kff, const float* Vx, const float* Vxx, long B, long H,
                                   float* dX, float* dU, float* Lam, hipStream_t st, int* grid);

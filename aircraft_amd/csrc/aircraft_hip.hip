@@ -1147,6 +1147,45 @@ static IlqrCost to_dev_cost(const ac_ilqr_cost* c) {
     return d;
 }
 
+static bool box_ok(const ac_ilqr_cost* c) {
+    for (int i = 0; i < 7; ++i) {
+        const float lo = c->u_min[i], hi = c->u_max[i];
+        if (!(fabsf(lo) <= 3.4028235e38f) || !(fabsf(hi) <= 3.4028235e38f) || lo > hi) return false;
+    }
+    return true;
+}
+
+// ---- the Riccati backward pass (ac_ilqr.hpp, ac_ilqr_rate.hpp, ac_boxqp.hpp): every entry point fills IlqrBackwardArgs, then ONE
+// validation and ONE launcher (ilqr_backward_inst.hip: all 24 kernels) ----------------------------------------------------------
+static IlqrBackwardArgs backward_args(const float* node_q, const float* node_xref, const float* node_glin, const float* node_uglin,
+                                      const float* Hz, const float* X, const float* U, const float* A, const float* Bm, long B,
+                                      long H, float* K, float* kff, float* dV) {
+    IlqrBackwardArgs a{};  // (C is filled in by backward_run, once the cost is known to be there)
+    a.N = NodeCost{node_q, node_xref, node_glin, B, node_uglin};
+    a.X = X, a.U = U, a.A = A, a.Bm = Bm, a.Hz = Hz;
+    a.B = B, a.H = H;
+    a.K = K, a.kff = kff, a.dV = dV;
+    return a;
+}
+
+// `extra`: the arrays this entry point cannot do without beyond X, U, A, Bm, K, kff, dV are all there; `name`: what the launch
+// is noted under.  The rules of every entry point: the node arrays go together, node_uglin needs them and Hz, Vx and Vxx go
+// together, a box has finite bounds with u_min <= u_max.
+static int backward_run(ac_handle* h, const ac_ilqr_cost* cost, IlqrBackwardArgs& a, bool extra, const char* name, void* stream) {
+    AC_ENTER(h);
+    if (h && a.B == 0) return AC_OK;
+    if (!h || !cost || !extra || !a.X || !a.U || !a.A || !a.Bm || !a.K || !a.kff || !a.dV || a.B < 0 || a.H < 1) return AC_ERR_BAD_ARG;
+    const NodeCost& n = a.N;
+    if ((n.q || n.xref || n.glin) && !(n.q && n.xref && n.glin)) return AC_ERR_BAD_ARG;
+    if (n.uglin && !(n.q && a.Hz)) return AC_ERR_BAD_ARG;
+    if ((a.Vx != nullptr) != (a.Vxx != nullptr)) return fail(AC_ERR_BAD_ARG, "ac_ilqr_backward_shoot_f32: Vx and Vxx go together");
+    if (a.box && !box_ok(cost)) return AC_ERR_BAD_ARG;
+    a.C = to_dev_cost(cost);
+    AC_HIP(ilqr_launch_backward(a, (hipStream_t)stream));
+    note_launch(h, name, (int)a.B, 64, 0);  // one wave per instance
+    return AC_OK;
+}
+
 int ac_ilqr_backward_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* X, const float* U, const float* A,
                          const float* Bm, long B, long H, float* K, float* kff, float* dV, void* stream) {
     return ac_ilqr_backward_node_f32(h, cost, nullptr, nullptr, nullptr, X, U, A, Bm, B, H, K, kff, dV, stream);
@@ -1178,23 +1217,8 @@ int ac_ilqr_costate_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* nod
 int ac_ilqr_backward_newton_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
                                 const float* node_glin, const float* Hz, const float* X, const float* U, const float* A,
                                 const float* Bm, long B, long H, float* K, float* kff, float* dV, void* stream) {
-    AC_ENTER(h);
-    if (h && B == 0) return AC_OK;
-    if (!h || !cost || !X || !U || !A || !Bm || !K || !kff || !dV || B < 0 || H < 1) return AC_ERR_BAD_ARG;
-    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
-    const NodeCost nc{node_q, node_xref, node_glin, B};
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = (int)B;  // one wave per instance
-#define AC_BACKWARD(NODE_, NEWTON_) \
-    hipLaunchKernelGGL((k_ilqr_backward<NODE_, NEWTON_>), grid, 64, 0, st, to_dev_cost(cost), nc, X, U, A, Bm, Hz, B, H, K, kff, dV)
-    if (node_q && Hz) AC_BACKWARD(true, true);
-    else if (node_q) AC_BACKWARD(true, false);
-    else if (Hz) AC_BACKWARD(false, true);
-    else AC_BACKWARD(false, false);
-#undef AC_BACKWARD
-    note_launch(h, "k_ilqr_backward", grid, 64, 0);
-    AC_HIP(hipGetLastError());
-    return AC_OK;
+    IlqrBackwardArgs a = backward_args(node_q, node_xref, node_glin, nullptr, Hz, X, U, A, Bm, B, H, K, kff, dV);
+    return backward_run(h, cost, a, true, "k_ilqr_backward", stream);
 }
 
 // ---- the goal-acquisition loss of the reference's MPC driver (main/control/control.py:44-68; ac_goal.hpp) ----------------
@@ -1254,18 +1278,8 @@ int ac_ilqr_backward_goal_f32(ac_handle* h, const ac_ilqr_cost* cost, const floa
                               const float* node_glin, const float* node_uglin, const float* Hz, const float* X,
                               const float* U, const float* A, const float* Bm, long B, long H, float* K, float* kff,
                               float* dV, void* stream) {
-    AC_ENTER(h);
-    if (h && B == 0) return AC_OK;
-    if (!h || !cost || !node_q || !node_xref || !node_glin || !Hz || !X || !U || !A || !Bm || !K || !kff || !dV || B < 0 || H < 1)
-        return AC_ERR_BAD_ARG;
-    NodeCost nc{node_q, node_xref, node_glin, B};
-    nc.uglin = node_uglin;
-    const int grid = (int)B;  // one wave per instance
-    hipLaunchKernelGGL((k_ilqr_backward<true, true>), grid, 64, 0, (hipStream_t)stream, to_dev_cost(cost), nc, X, U, A, Bm, Hz,
-                       B, H, K, kff, dV);
-    note_launch(h, "k_ilqr_backward", grid, 64, 0);
-    AC_HIP(hipGetLastError());
-    return AC_OK;
+    IlqrBackwardArgs a = backward_args(node_q, node_xref, node_glin, node_uglin, Hz, X, U, A, Bm, B, H, K, kff, dV);
+    return backward_run(h, cost, a, node_q && node_xref && node_glin && Hz, "k_ilqr_backward", stream);  // always <true, true>
 }
 
 // ---- the control-rate term modelled exactly: u_{k-1} carried through the Riccati pass (ac_ilqr_rate.hpp) -------------------
@@ -1273,60 +1287,29 @@ int ac_ilqr_backward_rate_f32(ac_handle* h, const ac_ilqr_cost* cost, const floa
                               const float* node_glin, const float* Hz, const float* rate_g, const float* rate_h, const float* X,
                               const float* U, const float* A, const float* Bm, long B, long H, float* K, float* Kp, float* kff,
                               float* dV, void* stream) {
-    AC_ENTER(h);
-    if (h && B == 0) return AC_OK;
-    if (!h || !cost || !rate_g || !rate_h || !X || !U || !A || !Bm || !K || !Kp || !kff || !dV || B < 0 || H < 1)
-        return AC_ERR_BAD_ARG;
-    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
-    const NodeCost nc{node_q, node_xref, node_glin, B};
-    AC_HIP(ilqr_rate_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, rate_g, rate_h, B, H, K, Kp, kff, dV,
-                                     (hipStream_t)stream));
-    note_launch(h, "k_ilqr_backward_rate", (int)B, 64, 0);
-    return AC_OK;
+    IlqrBackwardArgs a = backward_args(node_q, node_xref, node_glin, nullptr, Hz, X, U, A, Bm, B, H, K, kff, dV);
+    a.rate_g = rate_g, a.rate_h = rate_h, a.Kp = Kp;
+    return backward_run(h, cost, a, rate_g && rate_h && Kp, "k_ilqr_backward_rate", stream);
 }
 
-// ---- the control box in the backward pass: a 7-variable QP per node (ac_boxqp.hpp; the eight kernels of ilqr_box_inst.hip) -------
-static bool box_ok(const ac_ilqr_cost* c) {
-    for (int i = 0; i < 7; ++i) {
-        const float lo = c->u_min[i], hi = c->u_max[i];
-        if (!(fabsf(lo) <= 3.4028235e38f) || !(fabsf(hi) <= 3.4028235e38f) || lo > hi) return false;
-    }
-    return true;
-}
-
+// ---- the control box in the backward pass: a 7-variable QP per node (ac_boxqp.hpp; the BOX kernels) ------------------------------
 int ac_ilqr_backward_box_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
                              const float* node_glin, const float* node_uglin, const float* Hz, const float* X, const float* U,
                              const float* A, const float* Bm, long B, long H, float* K, float* kff, float* dV, signed char* act,
                              int* stat, void* stream) {
-    AC_ENTER(h);
-    if (h && B == 0) return AC_OK;
-    if (!h || !cost || !X || !U || !A || !Bm || !K || !kff || !dV || B < 0 || H < 1) return AC_ERR_BAD_ARG;
-    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
-    if (node_uglin && !(node_q && Hz)) return AC_ERR_BAD_ARG;
-    if (!box_ok(cost)) return AC_ERR_BAD_ARG;
-    NodeCost nc{node_q, node_xref, node_glin, B};
-    nc.uglin = node_uglin;
-    AC_HIP(ilqr_box_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, nullptr, nullptr, B, H, K, nullptr, kff, dV, act, stat,
-                                    (hipStream_t)stream));
-    note_launch(h, "k_ilqr_backward_box", (int)B, 64, 0);
-    return AC_OK;
+    IlqrBackwardArgs a = backward_args(node_q, node_xref, node_glin, node_uglin, Hz, X, U, A, Bm, B, H, K, kff, dV);
+    a.box = true, a.act = act, a.stat = stat;
+    return backward_run(h, cost, a, true, "k_ilqr_backward_box", stream);
 }
 
 int ac_ilqr_backward_rate_box_f32(ac_handle* h, const ac_ilqr_cost* cost, const float* node_q, const float* node_xref,
                                   const float* node_glin, const float* Hz, const float* rate_g, const float* rate_h,
                                   const float* X, const float* U, const float* A, const float* Bm, long B, long H, float* K,
                                   float* Kp, float* kff, float* dV, signed char* act, int* stat, void* stream) {
-    AC_ENTER(h);
-    if (h && B == 0) return AC_OK;
-    if (!h || !cost || !rate_g || !rate_h || !X || !U || !A || !Bm || !K || !Kp || !kff || !dV || B < 0 || H < 1)
-        return AC_ERR_BAD_ARG;
-    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
-    if (!box_ok(cost)) return AC_ERR_BAD_ARG;
-    const NodeCost nc{node_q, node_xref, node_glin, B};
-    AC_HIP(ilqr_box_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, rate_g, rate_h, B, H, K, Kp, kff, dV, act, stat,
-                                    (hipStream_t)stream));
-    note_launch(h, "k_ilqr_backward_rate_box", (int)B, 64, 0);
-    return AC_OK;
+    IlqrBackwardArgs a = backward_args(node_q, node_xref, node_glin, nullptr, Hz, X, U, A, Bm, B, H, K, kff, dV);
+    a.rate_g = rate_g, a.rate_h = rate_h, a.Kp = Kp;
+    a.box = true, a.act = act, a.stat = stat;
+    return backward_run(h, cost, a, rate_g && rate_h && Kp, "k_ilqr_backward_rate_box", stream);
 }
 
 // ---- Gauss-Newton multiple shooting: the defects in the Riccati pass, direction, candidates, merit (ac_shoot.hpp) -------------
@@ -1334,19 +1317,10 @@ int ac_ilqr_backward_shoot_f32(ac_handle* h, const ac_ilqr_cost* cost, const flo
                                const float* node_glin, const float* node_uglin, const float* Hz, const float* X, const float* U,
                                const float* A, const float* Bm, const float* F, long B, long H, float* K, float* kff, float* dV,
                                float* Vx, float* Vxx, int box, signed char* act, int* stat, void* stream) {
-    AC_ENTER(h);
-    if (h && B == 0) return AC_OK;
-    if (!h || !cost || !X || !U || !A || !Bm || !F || !K || !kff || !dV || B < 0 || H < 1) return AC_ERR_BAD_ARG;
-    if ((node_q || node_xref || node_glin) && !(node_q && node_xref && node_glin)) return AC_ERR_BAD_ARG;
-    if (node_uglin && !(node_q && Hz)) return AC_ERR_BAD_ARG;
-    if ((Vx != nullptr) != (Vxx != nullptr)) return fail(AC_ERR_BAD_ARG, "ac_ilqr_backward_shoot_f32: Vx and Vxx go together");
-    if (box && !box_ok(cost)) return AC_ERR_BAD_ARG;
-    NodeCost nc{node_q, node_xref, node_glin, B};
-    nc.uglin = node_uglin;
-    AC_HIP(ilqr_shoot_launch_backward(to_dev_cost(cost), nc, X, U, A, Bm, Hz, F, B, H, K, kff, dV, Vx, Vxx, box != 0,
-                                      box ? act : nullptr, box ? stat : nullptr, (hipStream_t)stream));
-    note_launch(h, box ? "k_ilqr_backward_shoot_box" : "k_ilqr_backward_shoot", (int)B, 64, 0);
-    return AC_OK;
+    IlqrBackwardArgs a = backward_args(node_q, node_xref, node_glin, node_uglin, Hz, X, U, A, Bm, B, H, K, kff, dV);
+    a.F = F, a.Vx = Vx, a.Vxx = Vxx;
+    a.box = box != 0, a.act = act, a.stat = stat;
+    return backward_run(h, cost, a, F != nullptr, box ? "k_ilqr_backward_shoot_box" : "k_ilqr_backward_shoot", stream);
 }
 
 int ac_shoot_direction_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* X, const float* U, const float* F, const float* A,

@@ -1,5 +1,5 @@
-// The exact control-rate Riccati pass and the quadratic rate cost: k_ilqr_backward_rate<NODE, NEWTON> (all four),
-// k_ilqr_rate_model, k_ilqr_rate_cost and their launchers (see ac_ilqr_rate.hpp).
+// The quadratic control-rate cost and its model for the exact rate pass: k_ilqr_rate_model, k_ilqr_rate_cost and their launchers
+// (see ac_ilqr_rate.hpp; the k_ilqr_backward_rate kernels are in ilqr_backward_inst.hip).
 #include "ac_ilqr_rate.hpp"
 
 namespace ac {
@@ -44,22 +44,6 @@ __global__ __launch_bounds__(kBlock) void k_ilqr_rate_cost(const RateWeights W, 
         }
     }
     cost[o] += acc;
-}
-
-hipError_t ilqr_rate_launch_backward(const IlqrCost& C, const NodeCost& N, const float* X, const float* U, const float* A,
-                                     const float* Bm, const float* Hz, const float* rate_g, const float* rate_h, long B, long H,
-                                     float* K, float* Kp, float* kff, float* dV, hipStream_t st) {
-    const int grid = (int)B;  // one wave per instance
-#define AC_BACKWARD_RATE(NODE_, NEWTON_)                                                                                      \
-    hipLaunchKernelGGL((k_ilqr_backward_rate<NODE_, NEWTON_>), grid, 64, 0, st, C, N, X, U, A, Bm, Hz, rate_g, rate_h, B, H, K, \
-                       Kp, kff, dV)
-    const bool node = N.q != nullptr;
-    if (node && Hz) AC_BACKWARD_RATE(true, true);
-    else if (node) AC_BACKWARD_RATE(true, false);
-    else if (Hz) AC_BACKWARD_RATE(false, true);
-    else AC_BACKWARD_RATE(false, false);
-#undef AC_BACKWARD_RATE
-    return hipGetLastError();
 }
 
 hipError_t ilqr_rate_launch_model(const RateWeights& W, const float* U, const float* u_prev, long B, long H, float* rate_g,

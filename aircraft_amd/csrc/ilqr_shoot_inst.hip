@@ -1,5 +1,5 @@
-// Gauss-Newton multiple shooting: the eight k_ilqr_backward_shoot<NODE, NEWTON, BOX> kernels (the SHOOT switch of the Riccati
-// pass, ac_ilqr.hpp), k_shoot_direction, k_shoot_merit_weight, k_shoot_candidates, k_shoot_merit and their launchers (ac_shoot.hpp).
+// Gauss-Newton multiple shooting: k_shoot_direction, k_shoot_merit_weight, k_shoot_candidates, k_shoot_merit and their launchers
+// (ac_shoot.hpp; the k_ilqr_backward_shoot kernels are in ilqr_backward_inst.hip).
 #include "ac_shoot.hpp"
 
 namespace ac {
@@ -152,30 +152,6 @@ __global__ __launch_bounds__(kBlock) void k_shoot_merit(const float* __restrict_
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
-hipError_t ilqr_shoot_launch_backward(const IlqrCost& C, const NodeCost& N, const float* X, const float* U, const float* A,
-                                      const float* Bm, const float* Hz, const float* F, long B, long H, float* K, float* kff,
-                                      float* dV, float* Vx, float* Vxx, bool box, signed char* act, int* stat, hipStream_t st) {
-    const int grid = (int)B;  // one wave per instance
-    const IlqrShootIn<true> sh{F, Vx, Vxx};
-    const IlqrBoxOut<true> bo{act, stat};
-#define AC_BACKWARD_SHOOT(NODE_, NEWTON_)                                                                                          \
-    do {                                                                                                                           \
-        if (box)                                                                                                                   \
-            hipLaunchKernelGGL((k_ilqr_backward_shoot<NODE_, NEWTON_, true>), grid, 64, 0, st, C, N, X, U, A, Bm, Hz, B, H, K, kff, \
-                               dV, sh, bo);                                                                                        \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((k_ilqr_backward_shoot<NODE_, NEWTON_, false>), grid, 64, 0, st, C, N, X, U, A, Bm, Hz, B, H, K,    \
-                               kff, dV, sh);                                                                                       \
-    } while (0)
-    const bool node = N.q != nullptr;
-    if (node && Hz) AC_BACKWARD_SHOOT(true, true);
-    else if (node) AC_BACKWARD_SHOOT(true, false);
-    else if (Hz) AC_BACKWARD_SHOOT(false, true);
-    else AC_BACKWARD_SHOOT(false, false);
-#undef AC_BACKWARD_SHOOT
-    return hipGetLastError();
-}
-
 hipError_t shoot_launch_direction(const IlqrCost& C, bool clip, const float* X, const float* U, const float* F, const float* A,
                                   const float* Bm, const float* K, const float* kff, const float* Vx, const float* Vxx, long B, long H,
                                   float* dX, float* dU, float* Lam, hipStream_t st, int* grid) {

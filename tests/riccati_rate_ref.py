@@ -10,7 +10,7 @@ whose inputs, metric and bars it uses.
  * `forward_rate`: the closed-loop law  u_k = clip(U_k + alpha k_k + Kx_k (x - Xnom_k) + Kp_k (u_applied_{k-1} - U_{k-1}))
    over the oracle's state_update.
 
-Ring depths of k_ilqr_backward_rate (IlqrRateRing<NODE, NEWTON>::kDepth, beside kInstr = 7 / 14 DMA instructions per node):
+Ring depths of k_ilqr_backward_rate (IlqrRing<NODE, NEWTON, false, true>::kDepth, beside kInstr = 7 / 14 DMA instructions per node):
 8 without the second-order blocks, 5 with them — the depths of k_ilqr_backward, so `riccati_ref.horizons` is the set of
 ring edges of this kernel too; stated here once as K_DEPTH."""
 from __future__ import annotations
@@ -23,7 +23,7 @@ import ilqr_oracle as io
 from tests.helpers import f32_exact
 from tests.riccati_ref import E32_MAX, FACTOR, QUU_MIN, bar_of, node_rel, row_rel, synthetic_riccati  # noqa: F401
 
-K_DEPTH = {False: 8, True: 5}    # IlqrRateRing<., NEWTON>::kDepth
+K_DEPTH = {False: 8, True: 5}    # IlqrRing<., NEWTON, false, true>::kDepth
 PARENT_B = 7
 WIDE_B = 65
 

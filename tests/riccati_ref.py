@@ -16,6 +16,10 @@ tests/test_riccati_ref.py checks all of this on the CPU; tests/test_gpu_riccati.
 from __future__ import annotations
 
 import functools
+import os
+import re
+import subprocess
+import tempfile
 
 import numpy as np
 
@@ -43,6 +47,37 @@ COSTATE_BLOCK = 256   # kBlock of ac_kernels_analytic.hpp: lanes per workgroup o
 def k_depth(newton):
     """IlqrRing<NODE, NEWTON>::kDepth: nodes in flight (the ring is shallower when the 21 x 21 blocks travel too)."""
     return 5 if newton else 8
+
+
+def ring_lds_bytes(newton, shoot=False, rate=False):
+    """LDS of one backward kernel from the constants of IlqrRing<NODE, NEWTON, SHOOT, RATE> (ac_ilqr.hpp):
+    4 x (kWork + kDepth x kNodeFloats) — the work area, then the node ring."""
+    work = 944 if rate else 736
+    node_floats = (776 if newton else 336) if rate else (768 if newton else 320) + (26 if shoot else 0)
+    return 4 * (work + k_depth(newton) * node_floats)
+
+
+@functools.lru_cache(maxsize=None)
+def backward_unit_resources():
+    """The compiler's resource remarks for csrc/ilqr_backward_inst.hip, the unit of all 24 backward kernels, compiled ONCE per
+    test run with the flags of the build -> {mangled name: dict(family, node, newton, box, vgpr, scratch, lds)}."""
+    from aircraft_amd import build as B
+
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = ["hipcc", *B.CFLAGS, *B.UNIT_FLAGS.get("ilqr_backward_inst", []), "-S", "--cuda-device-only",
+               "-Rpass-analysis=kernel-resource-usage", os.path.join(B.CSRC, "ilqr_backward_inst.hip"), "-o", os.path.join(tmp, "backward.s")]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = {}
+    for b in re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]:
+        name = b.split("\n")[0].split()[0]
+        m = re.match(r"_ZN2ac\d+k_ilqr_backward(_shoot|_rate|)ILb([01])ELb([01])ELb([01])EE", name)
+        if m:
+            out[name] = dict(family=m.group(1).lstrip("_"), node=m.group(2) == "1", newton=m.group(3) == "1", box=m.group(4) == "1",
+                             vgpr=int(re.search(r"VGPRs: (\d+)", b).group(1)),
+                             scratch=int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)),
+                             lds=int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1)))
+    return out
 
 
 def horizons(newton):

@@ -1,4 +1,4 @@
-"""Gauss-Newton multiple shooting (aircraft_amd/csrc/ac_shoot.hpp, ilqr_shoot_inst.hip, the SHOOT switch of ac_ilqr.hpp,
+"""Gauss-Newton multiple shooting (aircraft_amd/csrc/ac_shoot.hpp, ilqr_shoot_inst.hip, ilqr_backward_inst.hip, the SHOOT switch of ac_ilqr.hpp,
 ILQR(shooting="multiple")) restated in NumPy.  TEST INFRASTRUCTURE, NOT PRODUCT.  In the style of tests/riccati_ref.py and
 tests/box_ddp_ref.py, whose inputs, metric and bars it uses.
 

@@ -1,5 +1,5 @@
 """The box-constrained Riccati kernels k_ilqr_backward<NODE, NEWTON, true> and k_ilqr_backward_rate<NODE, NEWTON, true>
-(aircraft_amd/csrc/ilqr_box_inst.hip) against the float64 restatement of tests/box_ddp_ref.py, and ILQR(box="qp") end to end.
+(aircraft_amd/csrc/ilqr_backward_inst.hip) against the float64 restatement of tests/box_ddp_ref.py, and ILQR(box="qp") end to end.
 
 Matrix: the five ways the plain kernel is fed and the four rate kernels, B = 7 at H in {1, 2, kDepth + 1, 2 kDepth + 1}, B = 65 at
 H = kDepth + 1, a symmetric box and one with rows 3-5 pinned.  Per case: the active set equal to the reference's everywhere; every

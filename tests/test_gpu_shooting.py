@@ -1,5 +1,6 @@
-"""Gauss-Newton multiple shooting on the card: the eight k_ilqr_backward_shoot<NODE, NEWTON, BOX> kernels, k_shoot_direction,
-k_shoot_merit_weight, k_shoot_candidates, k_shoot_merit (aircraft_amd/csrc/ilqr_shoot_inst.hip) against the float64 restatement of
+"""Gauss-Newton multiple shooting on the card: the eight k_ilqr_backward_shoot<NODE, NEWTON, BOX> kernels
+(aircraft_amd/csrc/ilqr_backward_inst.hip), k_shoot_direction, k_shoot_merit_weight, k_shoot_candidates, k_shoot_merit
+(aircraft_amd/csrc/ilqr_shoot_inst.hip) against the float64 restatement of
 tests/shooting_ref.py, and ILQR(shooting="multiple") end to end.
 
 Kernels: synthetic inputs (tests/riccati_ref.py) with gaps of 0.3 N(0, 1) at every node; every (node, instance) of K, kff, Vx, Vxx,

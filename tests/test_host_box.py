@@ -1,8 +1,8 @@
-"""Host-side checks of the box-constrained backward pass (ILQR(box="qp"), csrc/ac_boxqp.hpp, csrc/ilqr_box_inst.hip):
+"""Host-side checks of the box-constrained backward pass (ILQR(box="qp"), csrc/ac_boxqp.hpp, csrc/ilqr_backward_inst.hip):
  1. the two ABI functions are declared, the solvers take the option, and box="clip" calls exactly what it called before;
  2. the QP routine itself, compiled as plain C++ into a stand-alone program (tests/host_boxqp/boxqp_host.cpp) under
     -fsanitize=address,undefined, against tests/box_ddp_ref.py on the random problems of test_box_ddp_ref.py;
- 3. registers and scratch of the eight box kernels from the compiler's resource remarks."""
+ 3. registers, scratch and LDS of all 24 backward kernels, the eight box kernels among them, from the compiler's resource remarks."""
 import ctypes as C
 import os
 import re
@@ -13,6 +13,7 @@ import pytest
 
 from aircraft_amd import _lib
 from tests import box_ddp_ref as bx
+from tests import riccati_ref as rr
 from tests.helpers import make_aircraft
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_boxqp")
@@ -173,24 +174,16 @@ def test_host_program_solution_within_the_fp32_bar(host_results):
     assert (got <= 8 * e32).all(), (cond[got > 8 * e32], got.max())
 
 
-# ---- 3. resources of the eight kernels -------------------------------------------------------------------------------------------------
-def test_box_kernels_registers_and_scratch(tmp_path):
-    from aircraft_amd import build as B
-
-    src = os.path.join(B.CSRC, "ilqr_box_inst.hip")
-    cmd = ["hipcc", *B.CFLAGS, *B.UNIT_FLAGS.get("ilqr_box_inst", []), "-S", "--cuda-device-only",
-           "-Rpass-analysis=kernel-resource-usage", src, "-o", str(tmp_path / "box.s")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
-    mine = [b for b in blocks if re.match(r"_ZN2ac\d+k_ilqr_backward", b)]
+# ---- 3. resources of the kernels ---------------------------------------------------------------------------------------------------
+def test_box_kernels_registers_and_scratch():
+    res = rr.backward_unit_resources()
+    assert len(res) == 24   # every <NODE, NEWTON, BOX> of k_ilqr_backward, _shoot and _rate, from the one unit
+    for name, k in res.items():
+        print(name[:60], "VGPRs", k["vgpr"], "scratch", k["scratch"], "LDS", k["lds"])
+        assert k["scratch"] == 0 and k["vgpr"] <= 256, (name, k)
+        assert k["lds"] == rr.ring_lds_bytes(k["newton"], shoot=k["family"] == "shoot", rate=k["family"] == "rate"), (name, k)
+    mine = [name for name, k in res.items() if k["box"] and k["family"] != "shoot"]
     assert len(mine) == 8
-    assert sum("k_ilqr_backward_rate" in b.split("\n")[0] for b in mine) == 4
-    for b in mine:
-        name = b.split("\n")[0].split()[0]
+    assert sum("k_ilqr_backward_rate" in name for name in mine) == 4
+    for name in mine:
         assert "Lb1EEEv" in name, name   # BOX = true instantiations only
-        vgpr = int(re.search(r"VGPRs: (\d+)", b).group(1))
-        scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-        lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-        print(name[:60], "VGPRs", vgpr, "scratch", scratch, "LDS", lds)
-        assert scratch == 0 and vgpr <= 256, (name, vgpr, scratch)

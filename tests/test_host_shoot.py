@@ -1,4 +1,5 @@
-"""Host-side checks of the multiple-shooting mode (ILQR(shooting="multiple"), csrc/ac_shoot.hpp, csrc/ilqr_shoot_inst.hip):
+"""Host-side checks of the multiple-shooting mode (ILQR(shooting="multiple"), csrc/ac_shoot.hpp, csrc/ilqr_shoot_inst.hip,
+csrc/ilqr_backward_inst.hip):
  1. the five ABI functions are declared in the header and the ctypes table, and the library exports them;
  2. the option, its refusals, and the call sequence of one iteration (the default mode's sequence is pinned by test_host_box.py);
  3. registers, scratch and LDS of the eight k_ilqr_backward_shoot kernels from the compiler's resource remarks."""
@@ -10,6 +11,7 @@ import subprocess
 import pytest
 
 from aircraft_amd import _lib
+from tests import riccati_ref as rr
 from tests.helpers import make_aircraft
 from tests.test_host_box import _iterate
 
@@ -100,28 +102,27 @@ def test_call_sequence_of_one_iteration():
 def test_shoot_kernels_registers_scratch_and_lds(tmp_path):
     from aircraft_amd import build as B
 
+    res = rr.backward_unit_resources()   # the eight kernels are in the unit of all backward kernels
+    mine = {name: k for name, k in res.items() if k["family"] == "shoot"}
+    assert len(mine) == 8
+    names = set()
+    for name, k in mine.items():
+        sw = re.search(r"k_ilqr_backward_shootILb([01])ELb([01])ELb([01])EE", name).groups()   # NODE, NEWTON, BOX
+        names.add(sw)
+        newton = sw[1] == "1"
+        vgpr, scratch, lds = k["vgpr"], k["scratch"], k["lds"]
+        print(name[:48], "VGPRs", vgpr, "scratch", scratch, "LDS", lds)
+        assert scratch == 0 and vgpr <= 256, (name, vgpr, scratch)   # two waves per SIMD, as the unswitched kernels
+        # work area + ring: depth x (node image + 26 floats of F_k, x_{k+1})
+        assert lds == 4 * (736 + (5 * (768 + 26) if newton else 8 * (320 + 26))), (name, lds)
+    assert len(names) == 8   # every <NODE, NEWTON, BOX>
+    # the four small kernels stay in ilqr_shoot_inst.hip
     src = os.path.join(B.CSRC, "ilqr_shoot_inst.hip")
     cmd = ["hipcc", *B.CFLAGS, *B.UNIT_FLAGS.get("ilqr_shoot_inst", []), "-S", "--cuda-device-only",
            "-Rpass-analysis=kernel-resource-usage", src, "-o", str(tmp_path / "shoot.s")]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
-    mine = [b for b in blocks if re.match(r"_ZN2ac\d+k_ilqr_backward_shoot", b)]
-    assert len(mine) == 8
-    names = set()
-    for b in mine:
-        name = b.split("\n")[0].split()[0]
-        sw = re.search(r"k_ilqr_backward_shootILb([01])ELb([01])ELb([01])EE", name).groups()   # NODE, NEWTON, BOX
-        names.add(sw)
-        newton = sw[1] == "1"
-        vgpr = int(re.search(r"VGPRs: (\d+)", b).group(1))
-        scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-        lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-        print(name[:48], "VGPRs", vgpr, "scratch", scratch, "LDS", lds)
-        assert scratch == 0 and vgpr <= 256, (name, vgpr, scratch)   # two waves per SIMD, as the unswitched kernels
-        # work area + ring: depth x (node image + 26 floats of F_k, x_{k+1})
-        assert lds == 4 * (736 + (5 * (768 + 26) if newton else 8 * (320 + 26))), (name, lds)
-    assert len(names) == 8   # every <NODE, NEWTON, BOX>
     small = [b for b in blocks if re.match(r"_ZN2ac\d+k_shoot_", b)]
     assert len(small) == 4
     for b in small:
