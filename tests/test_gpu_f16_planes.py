@@ -53,6 +53,12 @@ def test_f16_hidden_layers_every_unit_against_the_oracle_and_against_bf16(units)
     print(f"f16 hidden layers:  F {eF:.2e} A {eA.max():.2e} B {eB.max():.2e}")
     print(f"bf16 hidden layers: F {bF:.2e} A {bA.max():.2e} B {bB.max():.2e}")
     assert eF < 5e-6 and eA.max() < 5e-6 and eB.max() < 5e-6, (eF, eA.max(), eB.max())
+    # c = dF/ddt of both routes, every unit, at the suite's line for it (SENS_TOL, tests/test_gpu_parity.py).  (The per-block bar
+    # of tests/test_gpu_plane_routes.py is not taken here: at this dt = 0.01 the fp32 format of A's diagonal alone puts e_ref of
+    # the (v, v) and (omega, omega) blocks above its cap — see tests/sens_blocks_ref.py::DT.)
+    ec, bc = float(unit_max_rel(c, cr).max()), float(unit_max_rel(cb, cr).max())
+    print(f"c: f16 {ec:.2e} bf16 {bc:.2e}")
+    assert ec < 1e-5 and bc < 1e-5, (ec, bc)
     # f16 against bf16, unit by unit: no further apart than the two routes' own measured errors against the oracle allow
     dA, dB = unit_max_rel(A, Ab), unit_max_rel(Bm, Bb)
     sA = (eA + bA) * np.abs(Ar).reshape(-1, N).max(axis=0) / np.abs(Ab).reshape(-1, N).max(axis=0)
