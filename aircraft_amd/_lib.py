@@ -23,6 +23,7 @@ WGRAD_SEEDS, WGRAD_STEP, WGRAD_ROLLOUT = 0, 1, 2      # ac_wgrad_which
 CGRAD_STEP, CGRAD_ROLLOUT = 0, 1                      # ac_cgrad_which
 AIRFRAME_GRAD_FLOATS = 22                             # AC_AIRFRAME_GRAD_FLOATS: mass, inertia[9], inertia_inv[9], com[3]
 TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac_trim_f32 status per instance
+LQR_STATUS = {0: "converged", 1: "max_iter", 2: "breakdown", 3: "non_finite"}  # ac_lqr_f32 status per instance
 NUM_STATES = 13
 NUM_CONTROLS = 7
 AERO_ROWS = 22
@@ -61,6 +62,11 @@ class GoalLoss(C.Structure):
 class TrimOpts(C.Structure):
     """struct ac_trim_opts (include/aircraft_hip.h)."""
     _fields_ = [("lateral", C.c_int), ("tol_v", C.c_float), ("tol_w", C.c_float), ("lo", C.c_float * 6), ("hi", C.c_float * 6)]
+
+
+class LqrOpts(C.Structure):
+    """struct ac_lqr_opts (include/aircraft_hip.h)."""
+    _fields_ = [("q", C.c_float * 12), ("r", C.c_float * 7), ("tol", C.c_float)]
 
 
 class MppiOpts(C.Structure):
@@ -184,6 +190,11 @@ PROTOTYPES = {
     "ac_trim_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_trim_f32": (C.c_int, [_VP, C.POINTER(TrimOpts), _VP, _VP, _VP, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
                               _VP]),
+    "ac_lqr_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_lqr_f32": (C.c_int, [_VP, C.POINTER(LqrOpts), _VP, _VP, C.c_float, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                             C.c_size_t, _VP]),
+    "ac_lqr_gains_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP]),
+    "ac_steady_error_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, _VP, _VP]),
     "ac_mppi_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_mppi_sample_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP]),
     "ac_mppi_update_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP,

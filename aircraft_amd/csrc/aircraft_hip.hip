@@ -26,6 +26,7 @@
 #include "ac_vjp.hpp"
 #include "ac_trim.hpp"
 #include "ac_mppi.hpp"
+#include "ac_lqr.hpp"
 #include "ac_wgrad.hpp"
 #include "ac_cgrad.hpp"
 #include "ac_agrad.hpp"
@@ -2190,6 +2191,75 @@ int ac_trim_f32(ac_handle* h, const ac_trim_opts* o, const float* target, const 
         AC_HIP(hipGetLastError());
     }
     note_launch(h, "k_trim_update", grid, kTrimBlock, 0);
+    return AC_OK;
+}
+
+// ---- LQR about steady-flight trims (ac_lqr.hpp, lqr_inst.hip) ----------------------------------------------------------------------
+namespace {
+constexpr size_t kLqrWsPad = 3 * 64;  // the three workspace buffers each start on a 256-byte boundary
+size_t lqr_ws_floats(long n) { return (size_t)n * (size_t)kLqrWsFloats + kLqrWsPad; }
+const char* const kLqrFixedWing = "the LQR about a trim is defined for the fixed-wing models only";
+}  // namespace
+
+int ac_lqr_workspace_floats(const ac_handle* h, long n, size_t* floats) {
+    if (!h || !floats || n < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kLqrFixedWing);
+    *floats = lqr_ws_floats(n);
+    return AC_OK;
+}
+
+int ac_lqr_f32(ac_handle* h, const ac_lqr_opts* o, const float* X, const float* U, float dt, int iters, long n, float* Axi,
+               float* Bxi, float* P, float* K, float* resid, int* status, int* used_iters, float* ws, size_t ws_floats,
+               void* stream) {
+    AC_ENTER(h);
+    if (!h || !o || iters < 1 || n < 0) return AC_ERR_BAD_ARG;
+    if (!(dt > 0.f) || !(dt <= 3.0e38f)) return fail(AC_ERR_BAD_ARG, "lqr: dt must be finite and > 0");
+    for (int i = 0; i < 12; ++i)
+        if (!(o->q[i] >= 0.f) || !(o->q[i] <= 3.0e38f)) return fail(AC_ERR_BAD_ARG, "lqr: q must be finite and >= 0");
+    for (int j = 0; j < 7; ++j)
+        if (!(o->r[j] > 0.f) || !(o->r[j] <= 3.0e38f)) return fail(AC_ERR_BAD_ARG, "lqr: r must be finite and > 0");
+    if (!(o->tol >= 0.f)) return fail(AC_ERR_BAD_ARG, "lqr: tol must be >= 0");
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kLqrFixedWing);
+    if (n == 0) return AC_OK;
+    if (!X || !U || !Axi || !Bxi || !P || !K || !resid || !status || !used_iters) return AC_ERR_BAD_ARG;
+    int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    if (!ws || ws_floats < lqr_ws_floats(n)) return fail(AC_ERR_WORKSPACE, "lqr workspace too small: see ac_lqr_workspace_floats");
+    const size_t N = (size_t)n;
+    float* const Xp = align256(ws);
+    float* const A = align256(Xp + 13 * N);
+    float* const Bm = align256(A + 169 * N);  // ends at most ws + 273 N + 3 * 63 floats
+    rc = sens_impl(h, X, U, dt, nullptr, n, n, Xp, A, Bm, nullptr, stream);
+    if (rc != AC_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int grid = 0, lds = 0;
+    AC_HIP(lqr_launch_project(X, U, Xp, A, Bm, n, Axi, Bxi, st, &grid));
+    AC_HIP(lqr_launch_dare(*o, iters, Axi, Bxi, n, P, K, resid, status, used_iters, st, &grid, &lds));
+    note_launch(h, "k_lqr_dare", grid, kLqrGroups * kLqrLanes, lds);
+    return AC_OK;
+}
+
+int ac_lqr_gains_f32(ac_handle* h, const float* Xnom, const float* K, long n, long H, float* Kx, void* stream) {
+    AC_ENTER(h);
+    if (!h || n < 0 || H < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kLqrFixedWing);
+    if (n == 0 || H == 0) return AC_OK;
+    if (!Xnom || !K || !Kx) return AC_ERR_BAD_ARG;
+    int grid = 0;
+    AC_HIP(lqr_launch_gains(Xnom, K, n, H, Kx, (hipStream_t)stream, &grid));
+    note_launch(h, "k_lqr_gains", grid, kLqrBlock, 0);
+    return AC_OK;
+}
+
+int ac_steady_error_f32(ac_handle* h, const float* X, const float* Xnom, long n, float* xi, void* stream) {
+    AC_ENTER(h);
+    if (!h || n < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kLqrFixedWing);
+    if (n == 0) return AC_OK;
+    if (!X || !Xnom || !xi) return AC_ERR_BAD_ARG;
+    int grid = 0;
+    AC_HIP(lqr_launch_error(X, Xnom, n, xi, (hipStream_t)stream, &grid));
+    note_launch(h, "k_steady_error", grid, kLqrBlock, 0);
     return AC_OK;
 }
 

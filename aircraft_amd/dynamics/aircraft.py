@@ -19,7 +19,7 @@ from ..utils import AircraftConfiguration
 from .base import SixDOF, SixDOFOpts
 from .coefficient_models import COEFF_MODEL_REGISTRY, CoefficientModel, DefaultModel
 
-__all__ = ["Aircraft", "AircraftOpts", "TrimResult"]
+__all__ = ["Aircraft", "AircraftOpts", "TrimResult", "LqrResult"]
 
 
 def _torch_mod():
@@ -61,6 +61,35 @@ class TrimResult:
     residual: Any
     status: Any
     converged: Any
+
+
+@dataclass
+class LqrResult:
+    """Aircraft.lqr's result for n instances (numpy in -> numpy out; tensors stay on the device).
+    K (7, 12, n): the constant gain of u = u_b - K xi in the steady-flight chart xi (Aircraft.steady_error); P (12, 12, n): the
+    solution of the discrete Riccati equation; A (12, 12, n), B (12, 7, n): the step linearised in the chart; x (13, n),
+    u (7, n): the nominal; residual (n,): max|Q + A'PA - A'PB K - P| / max|P|; status (n,): 0 converged, 1 not converged
+    within iters, 2 breakdown, 3 non-finite input (include/aircraft_hip.h, ac_lqr_f32); converged (n,) = status == 0;
+    iterations (n,): doubling steps taken.  dt, q, r: what the gain was designed for."""
+    K: Any
+    P: Any
+    A: Any
+    B: Any
+    x: Any
+    u: Any
+    residual: Any
+    status: Any
+    converged: Any
+    iterations: Any
+    dt: float = 0.0
+    q: Any = None
+    r: Any = None
+    system: Any = field(default=None, repr=False)
+
+    def gains(self, Xnom):
+        """Raw-state gains K_x,k = -K E(x_k) along a nominal Xnom (H+1, 13, n) -> (H, 7, 13, n): the feedback
+        u = U_k + K_x,k (x - Xnom_k) of ac_rollout_policy_f32 / ILQR.closed_loop."""
+        return self.system._lqr_gains(Xnom, self.K)
 
 
 def inertia_about_com(cfg_Ixx, cfg_Iyy, cfg_Izz, cfg_Ixz, mass, com):
@@ -263,6 +292,156 @@ class Aircraft(SixDOF):
             X, U, Z, R = (t.cpu().numpy().astype(np.float64) for t in (X, U, Z, R))
             S = S.cpu().numpy()
         return TrimResult(X, U, Z, R, S, S == 0)
+
+    # ---- LQR about a steady-flight trim (include/aircraft_hip.h, ac_lqr_f32) ---------------------------
+    LQR_Q_DEFAULT = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.0, 1.0, 1.0, 1.0)  # the eight-state stability augmentation
+
+    def lqr_workspace(self, n: int):
+        """Device workspace of an LQR design of n instances (ac_lqr_workspace_floats); allocate it before capturing a graph."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_lqr_workspace_floats(self._handle, int(n), C.byref(need)), "ac_lqr_workspace_floats")
+        return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
+
+    def lqr(self, trim_or_xu, dt, q=None, r=None, iters=24, tol=1e-6, ws=None) -> LqrResult:
+        """Constant-gain discrete LQR about steady flight for n instances: `trim_or_xu` is a TrimResult or an (x (13, n),
+        u (7, n)) pair.  The step of length dt is linearised in the 12 steady-flight error coordinates (steady_error), in
+        which a trim is a fixed point, and P = Q + A'PA - A'PB (R + B'PB)^-1 B'PA is solved with Q = diag(q), R = diag(r).
+        q (12,) >= 0: weights of (along-track, cross-track, down, body velocity (3), tilt (2), heading, body rates (3)); a 0 on
+        along-track, cross-track, down or heading drops that coordinate from the design.  The default weights 1 on body
+        velocity, tilt and rates only: the eight-state stability augmentation; q = 1 on 1, 2, 8 as well holds the path.
+        r (7,) > 0: control weights (default 1).  `iters` doubling steps at most (an instance is frozen once its iterate
+        moves by less than tol, relative); no host synchronisation (graph-capturable with a workspace from lqr_workspace(n))."""
+        torch = _torch_mod()
+        if isinstance(trim_or_xu, TrimResult):
+            x, u = trim_or_xu.x, trim_or_xu.u
+        elif isinstance(trim_or_xu, (tuple, list)) and len(trim_or_xu) == 2:
+            x, u = trim_or_xu
+        else:
+            raise ValueError("lqr: pass a TrimResult or an (x, u) pair")
+        shp = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)  # noqa: E731
+        sx, su = shp(x), shp(u)
+        if len(sx) not in (1, 2) or sx[0] != 13 or len(su) != len(sx) or su[0] != _lib.NUM_CONTROLS or sx[1:] != su[1:]:
+            raise ValueError(f"lqr: expected x (13, n) and u (7, n), got {sx} and {su}")
+        if isinstance(dt, bool) or np.ndim(dt) != 0 or not np.isfinite(float(dt)) or float(dt) <= 0:
+            raise ValueError(f"lqr: dt must be a finite scalar > 0, got {dt!r}")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 1:
+            raise ValueError(f"lqr: iters must be an integer >= 1, got {iters!r}")
+        if np.ndim(tol) != 0 or not np.isfinite(float(tol)) or float(tol) < 0:
+            raise ValueError(f"lqr: tol must be a finite scalar >= 0, got {tol!r}")
+        qv = np.asarray(self.LQR_Q_DEFAULT if q is None else q, dtype=np.float64)
+        rv = np.ones(_lib.NUM_CONTROLS) if r is None else np.asarray(r, dtype=np.float64)
+        if qv.shape != (12,) or not np.isfinite(qv).all() or (qv < 0).any():
+            raise ValueError("lqr: q must be 12 finite weights >= 0")
+        if rv.shape != (_lib.NUM_CONTROLS,) or not np.isfinite(rv).all() or (rv <= 0).any():
+            raise ValueError("lqr: r must be 7 finite weights > 0")
+        if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.float32 or not ws.is_cuda
+                               or not ws.is_contiguous()):
+            raise ValueError("lqr: ws must be a contiguous float32 device tensor (lqr_workspace(n))")
+
+        # ---- device side ----
+        lib = self._sync()
+        X, npx, vec = self._in(x, self.num_states, "x")
+        U, _, _ = self._in(u, _lib.NUM_CONTROLS, "u")
+        n = X.shape[1]
+        dev = X.device
+        opts = _lib.LqrOpts()
+        opts.q[:] = [float(v) for v in qv]
+        opts.r[:] = [float(v) for v in rv]
+        opts.tol = float(tol)
+        if ws is None:
+            ws = self.lqr_workspace(n)
+        f32 = dict(device=dev, dtype=torch.float32)
+        A, Bm = torch.empty((12, 12, n), **f32), torch.empty((12, 7, n), **f32)
+        P, K = torch.empty((12, 12, n), **f32), torch.empty((7, 12, n), **f32)
+        res = torch.empty((n,), **f32)
+        S, it = torch.empty((n,), device=dev, dtype=torch.int32), torch.empty((n,), device=dev, dtype=torch.int32)
+        _lib.check(lib.ac_lqr_f32(self._handle, C.byref(opts), X.data_ptr(), U.data_ptr(), C.c_float(float(dt)), int(iters), n,
+                                  A.data_ptr(), Bm.data_ptr(), P.data_ptr(), K.data_ptr(), res.data_ptr(), S.data_ptr(),
+                                  it.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "ac_lqr_f32")
+        if npx:
+            K, P, A, Bm, X, U, res = (t.cpu().numpy().astype(np.float64) for t in (K, P, A, Bm, X, U, res))
+            S, it = S.cpu().numpy(), it.cpu().numpy()
+        if vec:
+            K, P, A, Bm, X, U, res, S, it = (t[..., 0] for t in (K, P, A, Bm, X, U, res, S, it))
+        return LqrResult(K, P, A, Bm, X, U, res, S, S == 0, it, float(dt), qv, rv, self)
+
+    def _lqr_gains(self, Xnom, K):
+        torch = _torch_mod()
+        lib = self._sync()
+        dev = self._device_obj()
+        from_np = not isinstance(Xnom, torch.Tensor)
+        Xt = torch.as_tensor(np.asarray(Xnom, dtype=np.float32) if from_np else Xnom).to(device=dev, dtype=torch.float32)
+        Kt = torch.as_tensor(np.asarray(K, dtype=np.float32) if not isinstance(K, torch.Tensor) else K).to(device=dev, dtype=torch.float32)
+        vec = Xt.dim() == 2
+        if vec:
+            Xt, Kt = Xt.unsqueeze(-1), Kt.unsqueeze(-1)
+        if Xt.dim() != 3 or Xt.shape[0] < 1 or Xt.shape[1] != 13 or tuple(Kt.shape) != (7, 12, Xt.shape[2]):
+            raise ValueError(f"gains: expected Xnom (H+1, 13, n) and K (7, 12, n), got {tuple(Xt.shape)} and {tuple(Kt.shape)}")
+        Xt, Kt = Xt.contiguous(), Kt.contiguous()
+        H, n = Xt.shape[0] - 1, Xt.shape[2]
+        Kx = torch.empty((H, 7, 13, n), device=dev, dtype=torch.float32)
+        _lib.check(lib.ac_lqr_gains_f32(self._handle, Xt.data_ptr(), Kt.data_ptr(), n, H, Kx.data_ptr(), self._stream()),
+                   "ac_lqr_gains_f32")
+        if from_np:
+            Kx = Kx.cpu().numpy().astype(np.float64)
+        return Kx[..., 0] if vec else Kx
+
+    def steady_error(self, x, xnom):
+        """xi (12, n): the steady-flight error coordinates of x (13, n) about the nominal xnom (13, n): heading-frame position
+        error (along-track, cross-track, down), body-velocity error, tilt about the heading frame's forward and right axes,
+        heading error, body-rate error.  Exactly 0 for x = xnom."""
+        torch = _torch_mod()
+        lib = self._sync()
+        X, npx, vec = self._in(x, self.num_states, "x")
+        Xb, _, _ = self._in(xnom, self.num_states, "xnom")
+        if Xb.shape != X.shape:
+            raise ValueError("x and xnom must have the same shape")
+        n = X.shape[1]
+        xi = torch.empty((12, n), device=X.device, dtype=torch.float32)
+        _lib.check(lib.ac_steady_error_f32(self._handle, X.data_ptr(), Xb.data_ptr(), n, xi.data_ptr(), self._stream()),
+                   "ac_steady_error_f32")
+        return self._out(xi, npx, vec)
+
+    def rollout_lqr(self, res: LqrResult, x0, H, dt=None, limits=None):
+        """Fly the closed loop u_k = clip(u_b + K_x,k (x_k - Xnom_k)) for H steps from x0 (13, n): Xnom is this handle's
+        rollout of the design's nominal (res.x, res.u), the gains come from res.gains(Xnom), the loop runs through
+        ac_rollout_policy_f32 (and inherits its model restrictions).  dt defaults to the design's; limits = (u_min (7,),
+        u_max (7,)) (default: none).  -> X (H+1, 13, n), U (H, 7, n), Xnom (H+1, 13, n)."""
+        torch = _torch_mod()
+        if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or H < 1:
+            raise ValueError(f"rollout_lqr: H must be an integer >= 1, got {H!r}")
+        dt = res.dt if dt is None else float(dt)
+        lo, hi = (np.full(7, -np.inf), np.full(7, np.inf)) if limits is None else (np.asarray(b, dtype=np.float64) for b in limits)
+        if lo.shape != (7,) or hi.shape != (7,) or np.isnan(lo).any() or np.isnan(hi).any() or (lo > hi).any():
+            raise ValueError("rollout_lqr: limits must be (u_min (7,), u_max (7,)) with u_min <= u_max")
+        lib = self._sync()
+        X0, npx, vec = self._in(x0, self.num_states, "x0")
+        Xb, _, _ = self._in(res.x, self.num_states, "res.x")
+        Ub, _, _ = self._in(res.u, _lib.NUM_CONTROLS, "res.u")
+        n = X0.shape[1]
+        if Xb.shape[1] != n or Ub.shape[1] != n:
+            raise ValueError("rollout_lqr: x0 and the design's nominal must have the same number of columns")
+        Un = Ub.unsqueeze(0).expand(H, -1, -1).contiguous()
+        Xnom = self.rollout(Xb, Un, dt)
+        K = res.K if isinstance(res.K, torch.Tensor) else torch.as_tensor(np.asarray(res.K, dtype=np.float32))
+        K = K.to(device=X0.device, dtype=torch.float32).reshape(7, 12, n)
+        Kx = self._lqr_gains(Xnom, K)
+        kff = torch.zeros((H, 7, n), device=X0.device, dtype=torch.float32)
+        Xc = torch.empty((H + 1, 13, n), device=X0.device, dtype=torch.float32)
+        Uc = torch.empty((H, 7, n), device=X0.device, dtype=torch.float32)
+        lim = _lib.IlqrCost()
+        lim.u_min[:] = [float(v) for v in lo]
+        lim.u_max[:] = [float(v) for v in hi]
+        lim.dt_row = 0
+        alphas = (C.c_float * 1)(1.0)
+        _lib.check(lib.ac_rollout_policy_f32(self._handle, C.byref(lim), X0.data_ptr(), Xnom.data_ptr(), Un.data_ptr(),
+                                             Kx.data_ptr(), kff.data_ptr(), alphas, 1, C.c_float(dt), n, H, Xc.data_ptr(),
+                                             Uc.data_ptr(), self._stream()), "ac_rollout_policy_f32")
+        out = (Xc, Uc, Xnom)
+        if npx:
+            out = tuple(t.cpu().numpy().astype(np.float64) for t in out)
+        return tuple(t[..., 0] for t in out) if vec else out
 
     # what the test oracle needs to rebuild the same airframe (tests only)
     def airframe_dict(self) -> dict:

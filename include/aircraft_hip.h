@@ -623,6 +623,39 @@ int ac_trim_f32(ac_handle* h, const ac_trim_opts* o,
                 float* X /* [13][n] */, float* U /* [7][n] */, float* Z /* [6][n] */, float* R /* [6][n] */, int* status /* [n] */,
                 float* ws, size_t ws_floats, void* stream);
 
+/* ---- LQR stabiliser about steady-flight trims (fixed-wing models) -------------------------------------------------
+ * The steady-flight chart: for a state x and a nominal xb, with Z = R_z(yaw of q_b),
+ *     xi = ( Z' (p - p_b),  R(q)' v - R(q_b)' v_b,  Z' 2 vec(q (x) q_b^-1),  omega - omega_b )
+ * (R(q): body -> NED, quaternions normalised, the sign of q (x) q_b^-1 such that its scalar part is >= 0).  Coordinates:
+ * 0 along-track, 1 cross-track, 2 down (heading frame), 3-5 body velocity, 6-7 tilt about the heading frame's forward and right
+ * axes, 8 heading, 9-11 body rates.  Steady flight (an ac_trim_f32 result) is a fixed point of the chart.
+ * ac_lqr_f32, per instance, at the nominal (X, U):
+ *   1. the handle's own ac_step_sens_f32 launch writes x+ = F(x, u, dt), A, B into the workspace (every model and engine);
+ *   2. k_lqr_project: A_xi = E(x+) A T(x) [12][12], B_xi = E(x+) B [12][7]  (T = dx/dxi, E = dxi/dx, analytic);
+ *   3. k_lqr_dare: P = Q + A'PA - A'PB (R + B'PB)^-1 B'PA with Q = diag(q), R = diag(r) by `iters` steps of the structured
+ *      doubling algorithm (an instance whose iterate moved by less than tol, relative in the max norm, is frozen: later
+ *      steps leave it bit-identical), then K = (R + B'PB)^-1 B'PA [7][12] (u = u_b - K xi) and
+ *      resid = max|Q + A'PA - A'PB K - P| / max|P|.
+ * q[i] >= 0; q[i] == 0 for i in {0, 1, 2, 8} DROPS that coordinate (it feeds no other one: its rows and columns of P and its
+ * column of K are exactly 0); r[j] > 0.  The thrust columns of B are exactly zero, so rows 3-5 of K are exactly 0.
+ * status [n]: 0 converged, 1 not converged within iters, 2 breakdown (a pivot <= 0 or a non-finite intermediate: P, K, resid
+ * are NaN), 3 non-finite input (NaN outputs).  used_iters [n]: doubling steps taken.  No instance affects another.
+ * ws / ws_floats: caller-owned device scratch of at least ac_lqr_workspace_floats(h, n) floats, else AC_ERR_WORKSPACE; after
+ * the call it holds x+ [13][n], A [13][13][n], B [13][7][n], each on a 256-byte boundary, in this order.
+ * AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG for iters < 1, n < 0, dt <= 0, a negative or non-finite q, r <= 0,
+ * tol < 0 or NULL pointers.  Asynchronous, no allocation, no synchronisation, hipGraph-capturable.
+ * ac_lqr_gains_f32: K_x,k = -K E(x_k) for the nodes k < H of Xnom [H+1][13][n] -> Kx [H][7][13][n], the gains
+ * ac_rollout_policy_f32 reads (with kff = 0: u = clip(U_k + K_x,k (x - Xnom_k))).
+ * ac_steady_error_f32: xi [12][n] of X about Xnom (both [13][n]); exactly 0 for X = Xnom. */
+typedef struct ac_lqr_opts { float q[12]; float r[7]; float tol; } ac_lqr_opts;
+int ac_lqr_workspace_floats(const ac_handle* h, long n, size_t* floats);
+int ac_lqr_f32(ac_handle* h, const ac_lqr_opts* o, const float* X /* [13][n] */, const float* U /* [7][n] */, float dt, int iters,
+               long n, float* Axi /* [12][12][n] */, float* Bxi /* [12][7][n] */, float* P /* [12][12][n] */,
+               float* K /* [7][12][n] */, float* resid /* [n] */, int* status /* [n] */, int* used_iters /* [n] */, float* ws,
+               size_t ws_floats, void* stream);
+int ac_lqr_gains_f32(ac_handle* h, const float* Xnom, const float* K, long n, long H, float* Kx, void* stream);
+int ac_steady_error_f32(ac_handle* h, const float* X, const float* Xnom, long n, float* xi, void* stream);
+
 /* ---- sampling-based MPC: MPPI (every model kind) ---------------------------------------------------------------
  * One MPPI iteration draws K perturbed control sequences per instance (ac_mppi_sample_f32), rolls them out and costs them with
  * the calls above (candidate k of instance b is column o = k*B + b, the layout ac_rollout_policy_f32 writes), and blends them by
