@@ -205,6 +205,7 @@ PROTOTYPES = {
     "ac_hess_workspace": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_size_t)]),
     "ac_last_launch": (C.c_int, [_VP, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                  C.POINTER(C.c_int)]),
+    "ac_f16_split_check": (C.c_int, [C.POINTER(C.c_ulonglong)]),
 }
 
 _lib = None

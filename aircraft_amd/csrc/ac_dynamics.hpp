@@ -1216,6 +1216,22 @@ template <class C> AC_DI void provider_mark(C& coeffs, int id) {
 #endif
 }
 
+// Providers that set kStageParams have the parameters read anew in every RK4 stage, through a pointer the optimiser cannot
+// see through (as PolyTab does for the fit tables): scalar loads from the kernel-argument segment where they are used.
+// Hoisted out of the stage loop they are ~100 loop-invariant scalars more than the scalar file holds across forward(), and
+// the register allocator parks them in vector lanes (v_writelane in the prologue, a v_readlane per use in every stage).
+template <class C, class = void> struct stage_params : std::false_type {};
+template <class C> struct stage_params<C, std::enable_if_t<C::kStageParams>> : std::true_type {};
+template <class C> AC_DI const DevParams& stage_params_ref(const DevParams& P) {
+    if constexpr (stage_params<C>::value) {
+        const AC_CONSTANT DevParams* p = (const AC_CONSTANT DevParams*)&P;
+        AC_OPAQUE_S(p);
+        return *(const DevParams*)p;
+    } else {
+        return P;
+    }
+}
+
 // One RK4 step from primal inputs; xo = F(x0, u, h) with tangents w.r.t. this lane's N directions.
 template <int N, class Coeffs, class Acc>
 AC_DI void rk4_step_seeded(const DevParams& P, Coeffs& coeffs, int g, const float xv[13], const float uv[7],
@@ -1232,13 +1248,14 @@ AC_DI void rk4_step_seeded(const DevParams& P, Coeffs& coeffs, int g, const floa
     }
 #pragma nounroll
     for (int s = 0; s < 4; ++s) {
-        coeffs.prefetch(P, xs, uv);
+        const DevParams& Ps = stage_params_ref<Coeffs>(P);
+        coeffs.prefetch(Ps, xs, uv);
         int gg = g;
         AC_OPAQUE_V(gg);  // keep the seed patterns out of loop-invariant registers
         {
             T u[7];
             Seeds::template controls<Coeffs::kModel == AC_MODEL_QUAD>(gg, uv, u);
-            state_derivative(P, coeffs, xs, u, k);
+            state_derivative(Ps, coeffs, xs, u, k);
         }
         if (s == 3) provider_mark(coeffs, 8);  // [8] the last stage's dual rigid body
         const float wsum = (s == 1 || s == 2) ? 2.0f : 1.0f;

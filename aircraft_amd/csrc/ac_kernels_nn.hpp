@@ -32,6 +32,17 @@ struct WaveUnit {
           unit(task_unit(tid, task) < n ? task_unit(tid, task) : n - 1), live(task_unit(tid, task) < n), ua(unit, blk) {}
 };
 
+// The parameters where the kernel received them: DevParams is the FIRST argument of the step kernels below, so it lies at
+// offset 0 of the kernel-argument segment.  SEG (the f16 units): hand the stage loop that address instead of the by-value
+// copy, whose address would be a private one — rk4_step_seeded reads the parameters from it anew in every stage
+// (stage_params_ref, ac_dynamics.hpp).
+template <bool SEG> AC_DI const DevParams& params_where_passed(const DevParams& P) {
+#ifndef AC_HOST_CHECK
+    if constexpr (SEG) return *(const DevParams*)(const AC_CONSTANT DevParams*)__builtin_amdgcn_kernarg_segment_ptr();
+#endif
+    return P;
+}
+
 // HID: how the hidden layers run (kHiddenFp32 / kHiddenBf16 / kHiddenF16, ac_mlp.hpp).  The default is the product form of the
 // (WT, USE_MFMA) pair; the two-plane f16 form is instantiated beside it for width 128 (nn_inst_wt8_f16_*.hip) and chosen per net.
 template <int WT, bool USE_MFMA, int HID = (USE_MFMA && WT == 8 ? kDefaultHidden : kHiddenFp32)>
@@ -71,7 +82,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_nn_step_sens(const DevParams P, c
         load_rows<7>(U, w.ua, uv);
         const float hv = dt_per_unit ? dt_per_unit[w.unit] : dt;
         Dual<4> x[13];
-        sens_update<4>(P, coeffs, w.g, w.col, w.ua, xv, uv, hv, x, A, Bm, c, w.live);
+        sens_update<4>(params_where_passed<Engine::F16>(P), coeffs, w.g, w.col, w.ua, xv, uv, hv, x, A, Bm, c, w.live);
         AC_MARK(eng.st, 7);  // [7] dual aero + rigid body + RK4 combine (everything outside forward())
         if (w.live) {
             const UnitAddr uo = w.ua.late();
@@ -193,7 +204,7 @@ AC_DI void sens_pair_body(const DevParams& P, const MlpPlan& plan, const float* 
     const int g8 = 4 * (Engine::kNoValue ? 1 : 0) + g;
     Dual<2> x[13];
     MlpPairCoeffs<Engine, TOFF> coeffs(eng, xch);
-    sens_update<2>(P, coeffs, g8, col, ua, xv, uv, hv, x, A, Bm, c, live);
+    sens_update<2>(params_where_passed<Engine::F16>(P), coeffs, g8, col, ua, xv, uv, hv, x, A, Bm, c, live);
     eng.drain();
     if (live) {
         const UnitAddr uo = ua.late();

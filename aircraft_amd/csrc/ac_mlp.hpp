@@ -452,13 +452,26 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
     // x - (the f16 in the low / high half of u), exact: the half is read as an operand, no conversion instruction
     AC_DI static float sub_f16_lo(float x, unsigned u) {
         float d;
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(u), "v"(x));
+        asm volatile("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(u), "v"(x));
         return d;
     }
     AC_DI static float sub_f16_hi(float x, unsigned u) {
         float d;
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(u), "v"(x));
+        asm volatile("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(u), "v"(x));
         return d;
+    }
+    // f16(r S) into the low / high half of a register, the other half kept: one instruction where a multiply and a share of
+    // a v_cvt_pk_f16_f32 stood.  r S is exact in fp32 (S a power of two, |r| < 2^5), so the one rounding of the fused form is
+    // the rounding of the conversion; an exact-cancellation residual is +0 and the +0 addend keeps it so.  S from an SGPR
+    // (the mix forms take no literal).
+    AC_DI static unsigned scale_f16_lo(float r) {
+        unsigned q;
+        asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(q) : "v"(r), "s"(kLoScale));
+        return q;
+    }
+    AC_DI static unsigned scale_f16_hi(unsigned q, float r) {
+        asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(q) : "v"(r), "s"(kLoScale));
+        return q;
     }
     AC_DI static f32x4 mfma_bf(const frag8& w, const frag8& x, f32x4 c) {
         if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, x, c, 0, 0, 0);
@@ -566,7 +579,8 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
         if constexpr (F16) {
             const unsigned h = cvt_pk_f16(f32x2{x, y});
             q[0][i] = h;
-            q[1][i] = cvt_pk_f16(f32x2{sub_f16_lo(x, h) * kLoScale, sub_f16_hi(y, h) * kLoScale});
+            const float rx = sub_f16_lo(x, h), ry = sub_f16_hi(y, h);
+            q[1][i] = scale_f16_hi(scale_f16_lo(rx), ry);
             return;
         }
         unsigned u = cvt_pk_bf16(x, y);
@@ -681,21 +695,19 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
         } else {
             constexpr int p = U - 2 * WT, c = p / 4, i = p % 4;
             if constexpr (F16) {
-                // split_pair()'s f16 form in three stages of two instructions
+                // split_pair()'s f16 form, five instructions in three stages (2, 2, 1).  A half-register write does not sit
+                // next to the residual it reads nor next to its other half (each costs a hazard wait): the low half goes
+                // behind the high residual, the high half into the next stage
                 if constexpr (K == 0) {
                     r.sxy[p] = f32x2{a[us][2 * c + (i >> 1)][(2 * i) & 3], a[us][2 * c + (i >> 1)][(2 * i + 1) & 3]};
                     r.su[p] = cvt_pk_f16(r.sxy[p]);
                     r.xq[c][0][i] = r.su[p];
-                    float x = sub_f16_lo(r.sxy[p][0], r.su[p]);
-                    bf_pin(x);
-                    r.sxy[p][0] = x;
+                    r.sxy[p][0] = sub_f16_lo(r.sxy[p][0], r.su[p]);
                 } else if constexpr (K == 1) {
-                    float y = sub_f16_hi(r.sxy[p][1], r.su[p]), x = r.sxy[p][0] * kLoScale;
-                    bf_pin(x); bf_pin(y);
-                    r.sxy[p] = f32x2{x, y};
+                    r.sxy[p][1] = sub_f16_hi(r.sxy[p][1], r.su[p]);
+                    r.sa[p] = scale_f16_lo(r.sxy[p][0]);
                 } else {
-                    r.sxy[p][1] *= kLoScale;
-                    r.xq[c][1][i] = cvt_pk_f16(r.sxy[p]);
+                    r.xq[c][1][i] = scale_f16_hi(r.sa[p], r.sxy[p][1]);
                 }
             } else if constexpr (K == 0) {
                 r.sxy[p] = f32x2{a[us][2 * c + (i >> 1)][(2 * i) & 3], a[us][2 * c + (i >> 1)][(2 * i + 1) & 3]};
@@ -1686,6 +1698,7 @@ struct MlpEngineCoopReg {
 template <class Engine, bool FUSED = false> struct MlpCoeffs {
     static constexpr int kModel = AC_MODEL_NN;
     static constexpr bool kFusedTangent = FUSED && Engine::kTangent;
+    static constexpr bool kStageParams = Engine::F16;  // rk4_step_seeded: parameters read per stage, not kept
     Engine& eng;
     float y[6];
     float J[Engine::kTangent ? 6 : 1][5];
@@ -1762,6 +1775,7 @@ template <class Engine, bool FUSED = false> struct MlpCoeffs {
 // next evaluation's hidden layers lie between these reads and the next writes) and applies act'(y) of the last layer.
 template <class Engine, int TOFF> struct MlpPairCoeffs {
     static constexpr int kModel = AC_MODEL_NN;
+    static constexpr bool kStageParams = Engine::F16;  // rk4_step_seeded: parameters read per stage, not kept
     Engine& eng;
     float* xch;
     float y[6];

@@ -719,6 +719,10 @@ int ac_set_hidden_route(ac_handle* h, int route);
 int ac_hidden_route_of(const ac_handle* h, int* route, int* gate);
 /* Name + launch geometry of the kernel the last call on this handle dispatched (for profiling). */
 int ac_last_launch(const ac_handle* h, char* name, size_t len, int* grid, int* block, int* lds_bytes);
+/* Test aid (csrc/f16_split_check.hip): the multiply form and the fused form of the f16 activation split over every finite
+ * fp32 pattern with |x| < 2^15.  out[0] / out[1]: patterns whose residual plane differs in the low / high half of the pair,
+ * out[2]: patterns visited (2 * 0x47000000), out[3]: one differing pattern + 1, or 0.  Allocates and synchronises. */
+int ac_f16_split_check(unsigned long long out[4]);
 
 #ifdef __cplusplus
 }
