@@ -24,6 +24,8 @@ CGRAD_STEP, CGRAD_ROLLOUT = 0, 1                      # ac_cgrad_which
 AIRFRAME_GRAD_FLOATS = 22                             # AC_AIRFRAME_GRAD_FLOATS: mass, inertia[9], inertia_inv[9], com[3]
 TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac_trim_f32 status per instance
 LQR_STATUS = {0: "converged", 1: "max_iter", 2: "breakdown", 3: "non_finite"}  # ac_lqr_f32 status per instance
+EKF_ROWS = 15                                         # ac_ekf_*: GPS p, GPS v, gyro, air data, magnetometer (3 rows each)
+EKF_REJECTED, EKF_NONFINITE = 1, 2                    # ac_ekf_step_f32 status bits per instance
 NUM_STATES = 13
 NUM_CONTROLS = 7
 AERO_ROWS = 22
@@ -67,6 +69,11 @@ class TrimOpts(C.Structure):
 class LqrOpts(C.Structure):
     """struct ac_lqr_opts (include/aircraft_hip.h)."""
     _fields_ = [("q", C.c_float * 12), ("r", C.c_float * 7), ("tol", C.c_float)]
+
+
+class EkfOpts(C.Structure):
+    """struct ac_ekf_opts (include/aircraft_hip.h)."""
+    _fields_ = [("mag_ned", C.c_float * 3), ("predict", C.c_int)]
 
 
 class MppiOpts(C.Structure):
@@ -195,6 +202,12 @@ PROTOTYPES = {
                              C.c_size_t, _VP]),
     "ac_lqr_gains_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP]),
     "ac_steady_error_f32": (C.c_int, [_VP, _VP, _VP, C.c_long, _VP, _VP]),
+    "ac_ekf_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_ekf_measure_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, C.c_long, _VP, _VP]),
+    "ac_ekf_step_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, _VP, _VP, _VP, _VP,
+                                  _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_ekf_filter_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
+                                    _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_mppi_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_mppi_sample_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP]),
     "ac_mppi_update_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP,

@@ -27,6 +27,7 @@
 #include "ac_trim.hpp"
 #include "ac_mppi.hpp"
 #include "ac_lqr.hpp"
+#include "ac_ekf.hpp"
 #include "ac_wgrad.hpp"
 #include "ac_cgrad.hpp"
 #include "ac_agrad.hpp"
@@ -2260,6 +2261,115 @@ int ac_steady_error_f32(ac_handle* h, const float* X, const float* Xnom, long n,
     int grid = 0;
     AC_HIP(lqr_launch_error(X, Xnom, n, xi, (hipStream_t)stream, &grid));
     note_launch(h, "k_steady_error", grid, kLqrBlock, 0);
+    return AC_OK;
+}
+
+// ---- extended Kalman filter over the step sensitivities (ac_ekf.hpp, ekf_inst.hip) -------------------------------------------------
+namespace {
+constexpr size_t kEkfWsPad = 7 * 64;  // the seven workspace buffers each start on a 256-byte boundary
+size_t ekf_ws_floats(long n) { return (size_t)n * (size_t)(kEkfSensFloats + kEkfChainFloats) + kEkfWsPad; }
+const char* const kEkfFixedWing = "the extended Kalman filter is defined for the fixed-wing models only";
+
+// one step: the handle's sensitivity launch into the workspace, then k_ekf_step.  ll_in: added to this step's ll (or NULL).
+int ekf_step_impl(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                  const int* mask, const float* Qd, const float* Rd, long n, const float* ll_in, float* Xo, float* Po, float* nu,
+                  float* S, float* nis, float* ll, int* used, int* status, float* Xpred, float* Ppred, float* Abar, float* ws,
+                  void* stream) {
+    const size_t N = (size_t)n;
+    float* const Xp = align256(ws);
+    float* const A = align256(Xp + 13 * N);
+    float* const Bm = align256(A + 169 * N);
+    if (o->predict) {
+        const int rc = sens_impl(h, X, U, dt, nullptr, n, n, Xp, A, Bm, nullptr, stream);
+        if (rc != AC_OK) return rc;
+    }
+    const EkfIo io{X, P, Xp, A, Z, Qd, Rd, mask, ll_in, Xo, Po, nu, S, nis, ll, used, status, Xpred, Ppred, Abar, n};
+    int grid = 0, lds = 0;
+    AC_HIP(ekf_launch_step(*o, h->dp.p.epsilon, io, (hipStream_t)stream, &grid, &lds));
+    note_launch(h, "k_ekf_step", grid, kEkfGroups * kEkfLanes, lds);
+    return AC_OK;
+}
+
+// the checks both entry points share; *go = false: nothing to do (AC_OK)
+int ekf_check(ac_handle* h, const ac_ekf_opts* o, float dt, long n, long T, const float* ws, size_t ws_floats, bool* go) {
+    *go = false;
+    if (!h || !o || n < 0 || T < 0) return AC_ERR_BAD_ARG;
+    if (o->predict && (!(dt > 0.f) || !(dt <= 3.0e38f))) return fail(AC_ERR_BAD_ARG, "ekf: dt must be finite and > 0");
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    if (n == 0 || T == 0) return AC_OK;
+    const int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    if (!ws || ws_floats < ekf_ws_floats(n)) return fail(AC_ERR_WORKSPACE, "ekf workspace too small: see ac_ekf_workspace_floats");
+    *go = true;
+    return AC_OK;
+}
+}  // namespace
+
+int ac_ekf_workspace_floats(const ac_handle* h, long n, size_t* floats) {
+    if (!h || !floats || n < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    *floats = ekf_ws_floats(n);
+    return AC_OK;
+}
+
+int ac_ekf_measure_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, long n, float* Z, void* stream) {
+    AC_ENTER(h);
+    if (!h || !o || n < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    if (n == 0) return AC_OK;
+    if (!X || !Z) return fail(AC_ERR_BAD_ARG, "ekf measure: X and Z must not be NULL");
+    int grid = 0;
+    AC_HIP(ekf_launch_measure(*o, h->dp.p.epsilon, X, n, Z, (hipStream_t)stream, &grid));
+    note_launch(h, "k_ekf_measure", grid, kEkfBlock, 0);
+    return AC_OK;
+}
+
+int ac_ekf_step_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                    const int* mask, const float* Qd, const float* Rd, long n, float* Xo, float* Po, float* nu, float* S, float* nis,
+                    float* ll, int* used, int* status, float* Xpred, float* Ppred, float* Abar, float* ws, size_t ws_floats,
+                    void* stream) {
+    AC_ENTER(h);
+    bool go = false;
+    const int rc = ekf_check(h, o, dt, n, 1, ws, ws_floats, &go);
+    if (rc != AC_OK || !go) return rc;
+    if (!X || !P || !Z || !Rd || !Xo || !Po || !nu || !S || !nis || !ll || !used || !status)
+        return fail(AC_ERR_BAD_ARG, "ekf step: a required pointer is NULL");
+    if (o->predict && (!U || !Qd)) return fail(AC_ERR_BAD_ARG, "ekf step: U and Qd are required when predict is set");
+    return ekf_step_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, nullptr, Xo, Po, nu, S, nis, ll, used, status, Xpred, Ppred, Abar, ws,
+                         stream);
+}
+
+int ac_ekf_filter_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                      const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
+                      float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    bool go = false;
+    int rc = ekf_check(h, o, dt, n, T, ws, ws_floats, &go);
+    if (rc != AC_OK || !go) return rc;
+    if (!X || !P || !Z || !Rd || !Xo || !Po || !ll) return fail(AC_ERR_BAD_ARG, "ekf filter: a required pointer is NULL");
+    if (o->predict && (!U || !Qd)) return fail(AC_ERR_BAD_ARG, "ekf filter: U and Qd are required when predict is set");
+    const size_t N = (size_t)n;
+    float* buf[4];  // x, P | x, P behind the sensitivity outputs
+    buf[0] = align256(align256(align256(align256(ws) + 13 * N) + 169 * N) + 91 * N);
+    buf[1] = align256(buf[0] + 13 * N);
+    buf[2] = align256(buf[1] + 144 * N);
+    buf[3] = align256(buf[2] + 13 * N);  // ends at most ws + 587 N + 7 * 63 floats
+    const float *xin = X, *pin = P;
+    for (long t = 0; t < T; ++t) {
+        const bool last = t == T - 1;
+        float* const xo = last ? Xo : buf[2 * (t & 1)];
+        float* const po = last ? Po : buf[2 * (t & 1) + 1];
+        const size_t k = (size_t)t;
+        rc = ekf_step_impl(h, o, xin, pin, U ? U + k * 7 * N : nullptr, dt, Z + k * 15 * N, mask ? mask + k * N : nullptr, Qd, Rd, n,
+                           t ? ll : nullptr, xo, po, nu ? nu + k * 15 * N : nullptr, S ? S + k * 15 * N : nullptr,
+                           nis ? nis + k * N : nullptr, ll, used ? used + k * N : nullptr, status ? status + k * N : nullptr, nullptr,
+                           nullptr, nullptr, ws, stream);
+        if (rc != AC_OK) return rc;
+        if (Xs) AC_HIP(hipMemcpyAsync(Xs + k * 13 * N, xo, 13 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        if (Ps) AC_HIP(hipMemcpyAsync(Ps + k * 144 * N, po, 144 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        xin = xo;
+        pin = po;
+    }
     return AC_OK;
 }
 

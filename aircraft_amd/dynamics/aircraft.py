@@ -92,6 +92,148 @@ class LqrResult:
         return self.system._lqr_gains(Xnom, self.K)
 
 
+@dataclass
+class EkfTrace:
+    """What a filter step (EKF.step / EKF.update) or T of them (EKF.filter: a leading axis T on everything but ll) report for
+    n instances (numpy in -> numpy out; tensors stay on the device).  X (13, n), P (12, 12, n): the posterior estimate and
+    its covariance in the error coordinates (dp, dv, dtheta, dw); nu, S (15, n): innovation and innovation variance of every
+    used row in the order the rows were applied (row i given the rows before it), 0 for unused rows; nis (n,) = sum nu^2 / S;
+    ll (n,): the log-likelihood -1/2 sum (log 2 pi S + nu^2 / S), for a filter summed over its steps; used (n,): bits of the
+    used rows; status (n,): 0, bit 1 a used row was rejected (S <= 0 or non-finite), bit 2 the prediction was not finite
+    (include/aircraft_hip.h, ac_ekf_step_f32)."""
+    X: Any
+    P: Any
+    nu: Any
+    S: Any
+    nis: Any
+    ll: Any
+    used: Any
+    status: Any
+
+
+class EKF:
+    """A bank of n extended Kalman filters over one Aircraft's step sensitivities (Aircraft.ekf).  `x`
+    (13, n) and `P` (12, 12, n) are the current estimate; step / update / filter advance it and return an EkfTrace.
+    Measurement rows z (15, n): GPS position (3), GPS velocity NED (3), gyro (3), air data V, alpha, beta (3), magnetometer (3);
+    a row is used when its mask bit is set (mask (n,) integers, bit i = row i; None: all) and its z is finite, so a sensor
+    that did not report is a NaN or a cleared bit.  No host synchronisation: with `ws` from Aircraft.ekf_workspace(n) the
+    calls can be captured in a graph."""
+
+    def __init__(self, system, X, P, Qd, Rd, mag_ned, ws, from_np, vec):
+        self.system, self._X, self._P, self._Qd, self._Rd, self._ws = system, X, P, Qd, Rd, ws
+        self.mag_ned = tuple(float(v) for v in mag_ned)
+        self._np, self._vec = from_np, vec
+
+    @property
+    def n(self):
+        return self._X.shape[1]
+
+    def _give(self, t):
+        if self._np:
+            t = t.cpu().numpy()
+            t = t.astype(np.float64) if t.dtype == np.float32 else t
+        return t[..., 0] if self._vec else t
+
+    @property
+    def x(self):
+        return self._give(self._X)
+
+    @property
+    def P(self):
+        return self._give(self._P)
+
+    def _opts(self, predict):
+        o = _lib.EkfOpts()
+        o.mag_ned[:] = self.mag_ned
+        o.predict = int(predict)
+        return o
+
+    def _rows(self, a, lead, rows, name, dtype=None):
+        """-> contiguous device tensor (*lead, rows, n) (rows None: (*lead, n))"""
+        torch = _torch_mod()
+        dtype = dtype or torch.float32
+        want = tuple(lead) + (() if rows is None else (rows,)) + (self.n,)
+        if not isinstance(a, torch.Tensor):
+            a = np.asarray(a)
+            if self._vec and a.shape == want[:-1]:
+                a = a[..., None]
+            if a.shape != want:
+                raise ValueError(f"ekf: {name} must have shape {want}, got {a.shape}")
+            a = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32 if dtype == torch.int32 else np.float32))
+        else:
+            if self._vec and tuple(a.shape) == want[:-1]:
+                a = a.unsqueeze(-1)
+            if tuple(a.shape) != want:
+                raise ValueError(f"ekf: {name} must have shape {want}, got {tuple(a.shape)}")
+        return a.to(device=self._X.device, dtype=dtype).contiguous()
+
+    @staticmethod
+    def _dt(dt, predict):
+        if not predict:
+            return 0.0
+        if isinstance(dt, bool) or np.ndim(dt) != 0 or not np.isfinite(float(dt)) or float(dt) <= 0:
+            raise ValueError(f"ekf: dt must be a finite scalar > 0, got {dt!r}")
+        return float(dt)
+
+    def _one(self, u, dt, z, mask, predict):
+        torch = _torch_mod()
+        dt = self._dt(dt, predict)
+        Z = self._rows(z, (), _lib.EKF_ROWS, "z")
+        U = self._rows(u, (), _lib.NUM_CONTROLS, "u") if predict else None
+        M = None if mask is None else self._rows(mask, (), None, "mask", torch.int32)
+        sysm, n, dev = self.system, self.n, self._X.device
+        lib = sysm._sync()
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        Xo, Po = torch.empty((13, n), **f32), torch.empty((12, 12, n), **f32)
+        nu, S = torch.empty((_lib.EKF_ROWS, n), **f32), torch.empty((_lib.EKF_ROWS, n), **f32)
+        nis, ll = torch.empty((n,), **f32), torch.empty((n,), **f32)
+        used, st = torch.empty((n,), **i32), torch.empty((n,), **i32)
+        o = self._opts(predict)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        _lib.check(lib.ac_ekf_step_f32(sysm._handle, C.byref(o), self._X.data_ptr(), self._P.data_ptr(), ptr(U), C.c_float(dt),
+                                       Z.data_ptr(), ptr(M), self._Qd.data_ptr(), self._Rd.data_ptr(), n, Xo.data_ptr(), Po.data_ptr(),
+                                       nu.data_ptr(), S.data_ptr(), nis.data_ptr(), ll.data_ptr(), used.data_ptr(), st.data_ptr(),
+                                       None, None, None, self._ws.data_ptr(), self._ws.numel(), sysm._stream()), "ac_ekf_step_f32")
+        self._X, self._P = Xo, Po
+        return EkfTrace(*(self._give(t) for t in (Xo, Po, nu, S, nis, ll, used, st)))
+
+    def step(self, u, dt, z, mask=None) -> EkfTrace:
+        """Time update over one step of length dt under the controls u (7, n), then the measurement update with z (15, n)."""
+        return self._one(u, dt, z, mask, True)
+
+    def update(self, z, mask=None) -> EkfTrace:
+        """The measurement update alone, at the current estimate."""
+        return self._one(None, 0.0, z, mask, False)
+
+    def filter(self, U, dt, Z, mask=None) -> EkfTrace:
+        """T steps: U (T, 7, n), Z (T, 15, n), mask (T, n) or None -> the per-step EkfTrace (leading axis T; ll (n,) summed)."""
+        torch = _torch_mod()
+        dt = self._dt(dt, True)
+        shape = tuple(Z.shape) if isinstance(Z, torch.Tensor) else np.shape(Z)
+        if len(shape) < 2:
+            raise ValueError(f"ekf: Z must have shape (T, 15, n), got {shape}")
+        T = shape[0]
+        Zt = self._rows(Z, (T,), _lib.EKF_ROWS, "Z")
+        Ut = self._rows(U, (T,), _lib.NUM_CONTROLS, "U")
+        M = None if mask is None else self._rows(mask, (T,), None, "mask", torch.int32)
+        sysm, n, dev = self.system, self.n, self._X.device
+        lib = sysm._sync()
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        Xo, Po, ll = torch.empty((13, n), **f32), torch.empty((12, 12, n), **f32), torch.zeros((n,), **f32)
+        Xs, Ps = torch.empty((T, 13, n), **f32), torch.empty((T, 12, 12, n), **f32)
+        nu, S = torch.empty((T, _lib.EKF_ROWS, n), **f32), torch.empty((T, _lib.EKF_ROWS, n), **f32)
+        nis, used, st = torch.empty((T, n), **f32), torch.empty((T, n), **i32), torch.empty((T, n), **i32)
+        o = self._opts(True)
+        _lib.check(lib.ac_ekf_filter_f32(sysm._handle, C.byref(o), self._X.data_ptr(), self._P.data_ptr(), Ut.data_ptr(), C.c_float(dt),
+                                         Zt.data_ptr(), None if M is None else M.data_ptr(), self._Qd.data_ptr(), self._Rd.data_ptr(),
+                                         n, T, Xo.data_ptr(), Po.data_ptr(), ll.data_ptr(), Xs.data_ptr(), Ps.data_ptr(), nu.data_ptr(),
+                                         S.data_ptr(), nis.data_ptr(), used.data_ptr(), st.data_ptr(), self._ws.data_ptr(),
+                                         self._ws.numel(), sysm._stream()), "ac_ekf_filter_f32")
+        if T:
+            self._X, self._P = Xo, Po
+        return EkfTrace(*(self._give(t) for t in (Xs, Ps, nu, S, nis, ll, used, st)))
+
+
 def inertia_about_com(cfg_Ixx, cfg_Iyy, cfg_Izz, cfg_Ixz, mass, com):
     """I = I0 + m K(com)   (reference dynamics/aircraft.py:137-141, 168-187), float64."""
     x, y, z = (float(c) for c in com)
@@ -442,6 +584,78 @@ class Aircraft(SixDOF):
         if npx:
             out = tuple(t.cpu().numpy().astype(np.float64) for t in out)
         return tuple(t[..., 0] for t in out) if vec else out
+
+    # ---- extended Kalman filter (include/aircraft_hip.h, ac_ekf_step_f32) -------------------------------
+    EKF_MAG_NED = (0.45, 0.03, 0.89)  # a northern mid-latitude field direction (north, east, down), the default of mag_ned
+
+    def ekf_workspace(self, n: int):
+        """Device workspace of a bank of n filters (ac_ekf_workspace_floats); allocate it before capturing a graph."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_ekf_workspace_floats(self._handle, int(n), C.byref(need)), "ac_ekf_workspace_floats")
+        return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
+
+    def ekf(self, x0, P0, *, q, r, mag_ned=EKF_MAG_NED, ws=None) -> EKF:
+        """A bank of n extended Kalman filters started at x0 (13, n) with covariance P0 (12, 12, n) in the error coordinates
+        (dp NED, dv NED, dtheta body-frame rotation vector, dw).  q: process-noise variances per step, (12,) for every
+        instance or (12, n); r: measurement variances > 0 of the 15 rows, (15,) or (15, n); mag_ned: the magnetic field in NED
+        (in the units the magnetometer reports).  Shapes, the symmetry and positive diagonal of P0 and the sign of q and r
+        are checked before any device is touched (values of tensors already on a device are not read)."""
+        torch = _torch_mod()
+        host = lambda a: not (isinstance(a, torch.Tensor) and a.is_cuda)  # noqa: E731
+        shp = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)  # noqa: E731
+        val = lambda a: a.detach().cpu().numpy().astype(np.float64) if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64)  # noqa: E731
+        sx, sp = shp(x0), shp(P0)
+        if len(sx) not in (1, 2) or sx[0] != 13 or sp != (12, 12) + sx[1:]:
+            raise ValueError(f"ekf: expected x0 (13, n) and P0 (12, 12, n), got {sx} and {sp}")
+        n = sx[1] if len(sx) == 2 else 1
+        for a, rows, name in ((q, 12, "q"), (r, _lib.EKF_ROWS, "r")):
+            if shp(a) not in ((rows,), (rows, n)):
+                raise ValueError(f"ekf: {name} must have shape ({rows},) or ({rows}, {n}), got {shp(a)}")
+        mg = np.asarray(mag_ned, dtype=np.float64)
+        if mg.shape != (3,) or not np.isfinite(mg).all():
+            raise ValueError("ekf: mag_ned must be 3 finite numbers")
+        if host(P0):
+            Pv = val(P0).reshape(12, 12, -1)
+            if not np.isfinite(Pv).all() or not np.array_equal(Pv, Pv.transpose(1, 0, 2)):
+                raise ValueError("ekf: P0 must be finite and symmetric")
+            if (Pv[np.arange(12), np.arange(12)] <= 0).any():
+                raise ValueError("ekf: the diagonal of P0 must be > 0")
+        if host(q) and (not np.isfinite(val(q)).all() or (val(q) < 0).any()):
+            raise ValueError("ekf: q must be finite and >= 0")
+        if host(r) and (not np.isfinite(val(r)).all() or (val(r) <= 0).any()):
+            raise ValueError("ekf: r must be finite and > 0")
+        if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.float32 or not ws.is_cuda
+                               or not ws.is_contiguous()):
+            raise ValueError("ekf: ws must be a contiguous float32 device tensor (ekf_workspace(n))")
+
+        # ---- device side ----
+        self._sync()
+        X, npx, vec = self._in(x0, self.num_states, "x0")
+        dev = X.device
+        to = lambda a: (torch.as_tensor(np.asarray(a, dtype=np.float32)) if not isinstance(a, torch.Tensor) else a).to(device=dev, dtype=torch.float32)  # noqa: E731
+        P = to(P0).reshape(12, 12, n).contiguous().clone()
+        Qd = to(q).reshape(12, -1).expand(12, n).contiguous()
+        Rd = to(r).reshape(_lib.EKF_ROWS, -1).expand(_lib.EKF_ROWS, n).contiguous()
+        if ws is None:
+            ws = self.ekf_workspace(n)
+        return EKF(self, X.clone(), P, Qd, Rd, mg, ws, npx, vec)
+
+    def measure(self, x, mag_ned=EKF_MAG_NED):
+        """z (15, n) = h(x): what the filter's sensors read at the state x (13, n) without noise: GPS position, GPS velocity
+        (NED), gyro, air data (V, alpha, beta: the airspeed, alpha, beta getters bit for bit), magnetometer R(q)' mag_ned."""
+        torch = _torch_mod()
+        mg = np.asarray(mag_ned, dtype=np.float64)
+        if mg.shape != (3,) or not np.isfinite(mg).all():
+            raise ValueError("measure: mag_ned must be 3 finite numbers")
+        lib = self._sync()
+        X, npx, vec = self._in(x, self.num_states, "x")
+        n = X.shape[1]
+        Z = torch.empty((_lib.EKF_ROWS, n), device=X.device, dtype=torch.float32)
+        o = _lib.EkfOpts()
+        o.mag_ned[:] = [float(v) for v in mg]
+        _lib.check(lib.ac_ekf_measure_f32(self._handle, C.byref(o), X.data_ptr(), n, Z.data_ptr(), self._stream()), "ac_ekf_measure_f32")
+        return self._out(Z, npx, vec)
 
     # what the test oracle needs to rebuild the same airframe (tests only)
     def airframe_dict(self) -> dict:

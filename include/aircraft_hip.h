@@ -656,6 +656,48 @@ int ac_lqr_f32(ac_handle* h, const ac_lqr_opts* o, const float* X /* [13][n] */,
 int ac_lqr_gains_f32(ac_handle* h, const float* Xnom, const float* K, long n, long H, float* Kx, void* stream);
 int ac_steady_error_f32(ac_handle* h, const float* X, const float* Xnom, long n, float* xi, void* stream);
 
+/* ---- extended Kalman filter over the step sensitivities (fixed-wing models) ---------------------------------------
+ * Error state about an estimate x: d = (dp NED, dv NED, dtheta body-frame rotation vector, dw) [12], with
+ *     x [+] d = ( p + dp, v + dv, (q (x) (dtheta/2, 1)) / |.|, w + dw )      (Hamilton, xyzw; no heading singularity).
+ * One step, per instance:
+ *   1. the handle's own ac_step_sens_f32 launch writes x- = F(x, u, dt), A, B into the workspace (every model and engine);
+ *   2. k_ekf_step: Abar = E(x-) A G(x) [12][12] (G = d(x [+] d)/dd, E = dd/dx, analytic), P- = Abar P Abar' + diag(Qd), symmetrised;
+ *      nu = z - h(x-) and H [15][12] (analytic) once, at x-; fifteen scalar updates in row order over the USED rows (mask bit
+ *      set, NULL mask: all; and z finite):  s = h P h' + r,  rho = nu_i - h d,  d += P h' rho / s,  P -= (P h')(P h')' / s;
+ *      x+ = x- [+] d (x- itself, bit for bit, when no row was applied).  No reset Jacobian is applied to P.
+ * Measurement rows h(x): 0-2 GPS position p, 3-5 GPS velocity v (NED), 6-8 gyro w, 9-11 air data (V, alpha, beta [rad]) = rows
+ * 3-5 of ac_aero_f32 bit for bit, 12-14 magnetometer R(q/|q|)' mag_ned.  R = diag(Rd).
+ * Outputs: Xo [13][n], Po [12][12][n] (bitwise symmetric); nu, S [15][n]: rho and s of every used row in the order they were
+ * applied (the innovation of row i given the rows before it; nu = z - h(x-) for the first), 0 for unused rows; nis [n] =
+ * sum rho^2 / s (= nu' S^-1 nu of the batch update); ll [n] = -1/2 sum (log 2 pi s + rho^2 / s); used [n]: bits of the used rows;
+ * status [n]: 0, or bit 1 (value 1): a used row had s <= 0 or a non-finite s and was skipped; bit 2 (value 2): the prediction
+ * (x-, P-) is not finite: Xo, Po are the prediction, no row is applied, nu = S = nis = ll = used = 0.  No instance affects
+ * another; no atomics, every sum in a fixed order: an instance's bits depend neither on n nor on its place in the batch.
+ * Xpred [13][n], Ppred, Abar [12][12][n]: optional (NULL), the prediction and the projected Jacobian (what a smoother needs).
+ * predict == 0: the measurement update alone (Abar = I, U, dt, Qd ignored and may be NULL / 0, no sensitivity launch).
+ * ws / ws_floats: caller-owned device scratch of at least ac_ekf_workspace_floats floats, else AC_ERR_WORKSPACE; after a
+ * predicting step it holds x- [13][n], A [13][13][n], B [13][7][n], each on a 256-byte boundary, in this order.
+ * ac_ekf_filter_f32: T steps as a host loop over the step (U [T][7][n], Z [T][15][n], mask [T][n] or NULL), the estimate
+ * ping-ponging through the workspace; Xo, Po: the final estimate; ll [n]: summed over the steps in step order; the per-step
+ * outputs Xs [T][13][n], Ps [T][12][12][n], nu, S [T][15][n], nis, used, status [T][n] may each be NULL.
+ * ac_ekf_measure_f32: Z [15][n] = h(X) (predict is ignored).
+ * AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG for n < 0, T < 0, a NULL required pointer, or (predict set) a dt that
+ * is not finite and > 0; n == 0 or T == 0 is AC_OK.  Asynchronous, no allocation, no synchronisation, hipGraph-capturable. */
+typedef struct ac_ekf_opts { float mag_ned[3]; int predict; } ac_ekf_opts;
+int ac_ekf_workspace_floats(const ac_handle* h, long n, size_t* floats);
+int ac_ekf_measure_f32(ac_handle* h, const ac_ekf_opts* o, const float* X /* [13][n] */, long n, float* Z /* [15][n] */, void* stream);
+int ac_ekf_step_f32(ac_handle* h, const ac_ekf_opts* o, const float* X /* [13][n] */, const float* P /* [12][12][n] */,
+                    const float* U /* [7][n] */, float dt, const float* Z /* [15][n] */, const int* mask /* [n] bits 0-14 | NULL */,
+                    const float* Qd /* [12][n] */, const float* Rd /* [15][n] */, long n, float* Xo, float* Po,
+                    float* nu /* [15][n] */, float* S /* [15][n] */, float* nis, float* ll /* [n] */, int* used /* [n] */,
+                    int* status /* [n] */, float* Xpred, float* Ppred, float* Abar /* optional, may be NULL */, float* ws,
+                    size_t ws_floats, void* stream);
+int ac_ekf_filter_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U /* [T][7][n] */, float dt,
+                      const float* Z /* [T][15][n] */, const int* mask /* [T][n] | NULL */, const float* Qd, const float* Rd,
+                      long n, long T, float* Xo, float* Po, float* ll /* [n] */, float* Xs, float* Ps, float* nu, float* S,
+                      float* nis, int* used, int* status /* per step, each may be NULL */, float* ws, size_t ws_floats,
+                      void* stream);
+
 /* ---- sampling-based MPC: MPPI (every model kind) ---------------------------------------------------------------
  * One MPPI iteration draws K perturbed control sequences per instance (ac_mppi_sample_f32), rolls them out and costs them with
  * the calls above (candidate k of instance b is column o = k*B + b, the layout ac_rollout_policy_f32 writes), and blends them by
