@@ -26,6 +26,7 @@ TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac
 LQR_STATUS = {0: "converged", 1: "max_iter", 2: "breakdown", 3: "non_finite"}  # ac_lqr_f32 status per instance
 EKF_ROWS = 15                                         # ac_ekf_*: GPS p, GPS v, gyro, air data, magnetometer (3 rows each)
 EKF_REJECTED, EKF_NONFINITE = 1, 2                    # ac_ekf_step_f32 status bits per instance
+RTS_NOT_PD, RTS_NONFINITE = 1, 2                      # ac_ekf_smooth_f32 status bits per link and instance
 NUM_STATES = 13
 NUM_CONTROLS = 7
 AERO_ROWS = 22
@@ -208,6 +209,9 @@ PROTOTYPES = {
                                   _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_ekf_filter_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_ekf_filter_rec_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
+                                        _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_ekf_smooth_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ac_mppi_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_mppi_sample_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP]),
     "ac_mppi_update_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP,

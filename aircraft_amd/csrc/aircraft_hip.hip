@@ -28,6 +28,7 @@
 #include "ac_mppi.hpp"
 #include "ac_lqr.hpp"
 #include "ac_ekf.hpp"
+#include "ac_rts.hpp"
 #include "ac_wgrad.hpp"
 #include "ac_cgrad.hpp"
 #include "ac_agrad.hpp"
@@ -2339,10 +2340,12 @@ int ac_ekf_step_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const fl
                          stream);
 }
 
-int ac_ekf_filter_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
-                      const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
-                      float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* ws, size_t ws_floats, void* stream) {
-    AC_ENTER(h);
+namespace {
+// T steps as a host loop over the step; Xpreds, Ppreds, Abars: the per-step records a smoother reads (each may be NULL)
+int ekf_filter_impl(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                    const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
+                    float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds, float* Ppreds, float* Abars,
+                    float* ws, size_t ws_floats, void* stream) {
     bool go = false;
     int rc = ekf_check(h, o, dt, n, T, ws, ws_floats, &go);
     if (rc != AC_OK || !go) return rc;
@@ -2362,14 +2365,66 @@ int ac_ekf_filter_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const 
         const size_t k = (size_t)t;
         rc = ekf_step_impl(h, o, xin, pin, U ? U + k * 7 * N : nullptr, dt, Z + k * 15 * N, mask ? mask + k * N : nullptr, Qd, Rd, n,
                            t ? ll : nullptr, xo, po, nu ? nu + k * 15 * N : nullptr, S ? S + k * 15 * N : nullptr,
-                           nis ? nis + k * N : nullptr, ll, used ? used + k * N : nullptr, status ? status + k * N : nullptr, nullptr,
-                           nullptr, nullptr, ws, stream);
+                           nis ? nis + k * N : nullptr, ll, used ? used + k * N : nullptr, status ? status + k * N : nullptr,
+                           Xpreds ? Xpreds + k * 13 * N : nullptr, Ppreds ? Ppreds + k * 144 * N : nullptr,
+                           Abars ? Abars + k * 144 * N : nullptr, ws, stream);
         if (rc != AC_OK) return rc;
         if (Xs) AC_HIP(hipMemcpyAsync(Xs + k * 13 * N, xo, 13 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         if (Ps) AC_HIP(hipMemcpyAsync(Ps + k * 144 * N, po, 144 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         xin = xo;
         pin = po;
     }
+    return AC_OK;
+}
+
+// do two spans of floats share an element? (a NULL span shares none)
+struct RtsSpan { const float* p; size_t floats; };
+bool rts_overlap(const RtsSpan& a, const RtsSpan& b) {
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a.p && b.p && a0 < b0 + b.floats * sizeof(float) && b0 < a0 + a.floats * sizeof(float);
+}
+}  // namespace
+
+int ac_ekf_filter_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                      const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
+                      float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    return ekf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, nullptr, nullptr,
+                           nullptr, ws, ws_floats, stream);
+}
+
+int ac_ekf_filter_rec_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt,
+                          const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po,
+                          float* ll, float* Xs, float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds,
+                          float* Ppreds, float* Abars, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    return ekf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, Xpreds, Ppreds,
+                           Abars, ws, ws_floats, stream);
+}
+
+// ---- RTS smoother over the EKF trace (ac_rts.hpp, rts_inst.hip) ---------------------------------------------------------------------
+int ac_ekf_smooth_f32(ac_handle* h, const float* X0, const float* P0, const float* Xf, const float* Pf, const float* Xpred,
+                      const float* Ppred, const float* Abar, long n, long T, float* Xs, float* Ps, float* Xs0, float* Ps0, float* Cg,
+                      int* status, void* stream) {
+    AC_ENTER(h);
+    if (!h || n < 0 || T < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    const int given = (X0 != nullptr) + (P0 != nullptr) + (Xs0 != nullptr) + (Ps0 != nullptr);
+    if (given != 0 && given != 4) return fail(AC_ERR_BAD_ARG, "ekf smooth: X0, P0, Xs0, Ps0 go together (all or none)");
+    if (n == 0 || T == 0) return AC_OK;
+    if (!Xf || !Pf || !Xpred || !Ppred || !Abar || !Xs || !Ps || !status)
+        return fail(AC_ERR_BAD_ARG, "ekf smooth: a required pointer is NULL");
+    const size_t N = (size_t)n, K = (size_t)T;
+    const RtsSpan in[] = {{X0, 13 * N}, {P0, 144 * N}, {Xf, K * 13 * N}, {Pf, K * 144 * N}, {Xpred, K * 13 * N}, {Ppred, K * 144 * N},
+                          {Abar, K * 144 * N}};
+    const RtsSpan out[] = {{Xs, K * 13 * N}, {Ps, K * 144 * N}, {Xs0, 13 * N}, {Ps0, 144 * N}, {Cg, K * 144 * N}};
+    for (const RtsSpan& a : out)
+        for (const RtsSpan& b : in)
+            if (rts_overlap(a, b)) return fail(AC_ERR_BAD_ARG, "ekf smooth: an output overlaps an input");
+    const RtsIo io{X0, P0, Xf, Pf, Xpred, Ppred, Abar, Xs, Ps, Xs0, Ps0, Cg, status, n, T};
+    int grid = 0, lds = 0;
+    AC_HIP(rts_launch_smooth(io, (hipStream_t)stream, &grid, &lds));
+    note_launch(h, "k_ekf_smooth", grid, kRtsGroups * kEkfLanes, lds);
     return AC_OK;
 }
 

@@ -19,7 +19,7 @@ from ..utils import AircraftConfiguration
 from .base import SixDOF, SixDOFOpts
 from .coefficient_models import COEFF_MODEL_REGISTRY, CoefficientModel, DefaultModel
 
-__all__ = ["Aircraft", "AircraftOpts", "TrimResult", "LqrResult"]
+__all__ = ["Aircraft", "AircraftOpts", "TrimResult", "LqrResult", "EKF", "EkfTrace", "EkfSmooth"]
 
 
 def _torch_mod():
@@ -100,7 +100,9 @@ class EkfTrace:
     used row in the order the rows were applied (row i given the rows before it), 0 for unused rows; nis (n,) = sum nu^2 / S;
     ll (n,): the log-likelihood -1/2 sum (log 2 pi S + nu^2 / S), for a filter summed over its steps; used (n,): bits of the
     used rows; status (n,): 0, bit 1 a used row was rejected (S <= 0 or non-finite), bit 2 the prediction was not finite
-    (include/aircraft_hip.h, ac_ekf_step_f32)."""
+    (include/aircraft_hip.h, ac_ekf_step_f32).  EKF.filter(record=True) adds what EKF.smooth reads: Xpred (T, 13, n), Ppred,
+    Abar (T, 12, 12, n), the prediction of every step and the Jacobian that carried the error state into it, and X0, P0, the
+    estimate the run started from."""
     X: Any
     P: Any
     nu: Any
@@ -108,6 +110,31 @@ class EkfTrace:
     nis: Any
     ll: Any
     used: Any
+    status: Any
+    Xpred: Any = None
+    Ppred: Any = None
+    Abar: Any = None
+    X0: Any = None
+    P0: Any = None
+
+
+@dataclass
+class EkfSmooth:
+    """What EKF.smooth returns for a recorded filter run of T steps (numpy in -> numpy out; tensors stay on the device): the
+    fixed-interval (Rauch-Tung-Striebel) estimate of every node given the whole run (include/aircraft_hip.h,
+    ac_ekf_smooth_f32).
+    X (T, 13, n), P (T, 12, 12, n): the smoothed states and their covariances in the error coordinates (dp, dv, dtheta, dw);
+    the last node is the filtered one.  X0 (13, n), P0 (12, 12, n): the smoothed initial estimate (initial=True; else None).
+    C (T, 12, 12, n) (gains=True; else None): the smoother gain C_k of link k, which carries node k's correction back to node
+    k-1 (C[0] belongs to the initial node and is zero without it); the lag-one smoothed covariance is
+    Cov(d_k, d_{k-1} | all data) = P^s_k C_k', the cross term an EM estimate of Q and R needs.
+    status (T, n): per link 0, bit 1 (value 1) the predicted covariance of node k was not positive definite, bit 2 (value 2) an
+    operand of the link was not finite; in both cases the gain of that link is zero and node k-1 is the filtered one."""
+    X: Any
+    P: Any
+    X0: Any
+    P0: Any
+    C: Any
     status: Any
 
 
@@ -117,7 +144,8 @@ class EKF:
     Measurement rows z (15, n): GPS position (3), GPS velocity NED (3), gyro (3), air data V, alpha, beta (3), magnetometer (3);
     a row is used when its mask bit is set (mask (n,) integers, bit i = row i; None: all) and its z is finite, so a sensor
     that did not report is a NaN or a cleared bit.  No host synchronisation: with `ws` from Aircraft.ekf_workspace(n) the
-    calls can be captured in a graph."""
+    calls can be captured in a graph.  For a recorded flight, filter(..., record=True) keeps what smooth(trace) reads: the
+    fixed-interval (RTS) estimate of every step given the whole run."""
 
     def __init__(self, system, X, P, Qd, Rd, mag_ned, ws, from_np, vec):
         self.system, self._X, self._P, self._Qd, self._Rd, self._ws = system, X, P, Qd, Rd, ws
@@ -205,8 +233,9 @@ class EKF:
         """The measurement update alone, at the current estimate."""
         return self._one(None, 0.0, z, mask, False)
 
-    def filter(self, U, dt, Z, mask=None) -> EkfTrace:
-        """T steps: U (T, 7, n), Z (T, 15, n), mask (T, n) or None -> the per-step EkfTrace (leading axis T; ll (n,) summed)."""
+    def filter(self, U, dt, Z, mask=None, record=False) -> EkfTrace:
+        """T steps: U (T, 7, n), Z (T, 15, n), mask (T, n) or None -> the per-step EkfTrace (leading axis T; ll (n,) summed).
+        record=True: the trace also carries Xpred, Ppred, Abar of every step and the starting X0, P0 (what smooth reads)."""
         torch = _torch_mod()
         dt = self._dt(dt, True)
         shape = tuple(Z.shape) if isinstance(Z, torch.Tensor) else np.shape(Z)
@@ -224,14 +253,51 @@ class EKF:
         nu, S = torch.empty((T, _lib.EKF_ROWS, n), **f32), torch.empty((T, _lib.EKF_ROWS, n), **f32)
         nis, used, st = torch.empty((T, n), **f32), torch.empty((T, n), **i32), torch.empty((T, n), **i32)
         o = self._opts(True)
-        _lib.check(lib.ac_ekf_filter_f32(sysm._handle, C.byref(o), self._X.data_ptr(), self._P.data_ptr(), Ut.data_ptr(), C.c_float(dt),
-                                         Zt.data_ptr(), None if M is None else M.data_ptr(), self._Qd.data_ptr(), self._Rd.data_ptr(),
-                                         n, T, Xo.data_ptr(), Po.data_ptr(), ll.data_ptr(), Xs.data_ptr(), Ps.data_ptr(), nu.data_ptr(),
-                                         S.data_ptr(), nis.data_ptr(), used.data_ptr(), st.data_ptr(), self._ws.data_ptr(),
-                                         self._ws.numel(), sysm._stream()), "ac_ekf_filter_f32")
+        head = (sysm._handle, C.byref(o), self._X.data_ptr(), self._P.data_ptr(), Ut.data_ptr(), C.c_float(dt), Zt.data_ptr(),
+                None if M is None else M.data_ptr(), self._Qd.data_ptr(), self._Rd.data_ptr(), n, T, Xo.data_ptr(), Po.data_ptr(),
+                ll.data_ptr(), Xs.data_ptr(), Ps.data_ptr(), nu.data_ptr(), S.data_ptr(), nis.data_ptr(), used.data_ptr(), st.data_ptr())
+        tail = (self._ws.data_ptr(), self._ws.numel(), sysm._stream())
+        rec = ()
+        if record:
+            rec = (torch.empty((T, 13, n), **f32), torch.empty((T, 12, 12, n), **f32), torch.empty((T, 12, 12, n), **f32), self._X, self._P)
+            _lib.check(lib.ac_ekf_filter_rec_f32(*head, *(t.data_ptr() for t in rec[:3]), *tail), "ac_ekf_filter_rec_f32")
+        else:
+            _lib.check(lib.ac_ekf_filter_f32(*head, *tail), "ac_ekf_filter_f32")
         if T:
             self._X, self._P = Xo, Po
-        return EkfTrace(*(self._give(t) for t in (Xs, Ps, nu, S, nis, ll, used, st)))
+        return EkfTrace(*(self._give(t) for t in (Xs, Ps, nu, S, nis, ll, used, st) + rec))
+
+    def smooth(self, trace, initial=True, gains=False) -> EkfSmooth:
+        """The fixed-interval (RTS) smoother over a recorded run, trace = filter(..., record=True): every node's estimate given
+        the whole run, in one backward sweep on the device.  initial: also smooth the estimate the run started from (trace.X0,
+        trace.P0); gains: also return the smoother gains C.  -> EkfSmooth."""
+        torch = _torch_mod()
+        if not isinstance(trace, EkfTrace):
+            raise ValueError("ekf smooth: expected the EkfTrace of filter(..., record=True)")
+        need = ("X", "P", "Xpred", "Ppred", "Abar") + (("X0", "P0") if initial else ())
+        missing = [k for k in need if getattr(trace, k) is None]
+        if missing:
+            raise ValueError(f"ekf smooth: the trace carries no {', '.join(missing)}: run filter(..., record=True)")
+        shape = tuple(trace.X.shape) if isinstance(trace.X, torch.Tensor) else np.shape(trace.X)
+        if len(shape) != (2 if self._vec else 3):
+            raise ValueError(f"ekf smooth: trace.X must have shape (T, 13, n), got {shape}")
+        T = shape[0]
+        Xf, Xp = (self._rows(getattr(trace, k), (T,), 13, f"trace.{k}") for k in ("X", "Xpred"))
+        Pf, Pp, Ab = (self._rows(getattr(trace, k), (T, 12), 12, f"trace.{k}") for k in ("P", "Ppred", "Abar"))
+        X0 = self._rows(trace.X0, (), 13, "trace.X0") if initial else None
+        P0 = self._rows(trace.P0, (12,), 12, "trace.P0") if initial else None
+        sysm, n, dev = self.system, self.n, self._X.device
+        lib = sysm._sync()
+        f32 = dict(device=dev, dtype=torch.float32)
+        Xs, Ps = torch.empty((T, 13, n), **f32), torch.empty((T, 12, 12, n), **f32)
+        Xs0, Ps0 = (torch.empty((13, n), **f32), torch.empty((12, 12, n), **f32)) if initial else (None, None)
+        Cg = torch.empty((T, 12, 12, n), **f32) if gains else None
+        st = torch.empty((T, n), device=dev, dtype=torch.int32)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        _lib.check(lib.ac_ekf_smooth_f32(sysm._handle, ptr(X0), ptr(P0), Xf.data_ptr(), Pf.data_ptr(), Xp.data_ptr(), Pp.data_ptr(),
+                                         Ab.data_ptr(), n, T, Xs.data_ptr(), Ps.data_ptr(), ptr(Xs0), ptr(Ps0), ptr(Cg), st.data_ptr(),
+                                         sysm._stream()), "ac_ekf_smooth_f32")
+        return EkfSmooth(*(None if t is None else self._give(t) for t in (Xs, Ps, Xs0, Ps0, Cg, st)))
 
 
 def inertia_about_com(cfg_Ixx, cfg_Iyy, cfg_Izz, cfg_Ixz, mass, com):

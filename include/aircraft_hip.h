@@ -673,13 +673,16 @@ int ac_steady_error_f32(ac_handle* h, const float* X, const float* Xnom, long n,
  * status [n]: 0, or bit 1 (value 1): a used row had s <= 0 or a non-finite s and was skipped; bit 2 (value 2): the prediction
  * (x-, P-) is not finite: Xo, Po are the prediction, no row is applied, nu = S = nis = ll = used = 0.  No instance affects
  * another; no atomics, every sum in a fixed order: an instance's bits depend neither on n nor on its place in the batch.
- * Xpred [13][n], Ppred, Abar [12][12][n]: optional (NULL), the prediction and the projected Jacobian (what a smoother needs).
+ * Xpred [13][n], Ppred, Abar [12][12][n]: optional (NULL), the prediction and the projected Jacobian (what ac_ekf_smooth_f32 reads).
  * predict == 0: the measurement update alone (Abar = I, U, dt, Qd ignored and may be NULL / 0, no sensitivity launch).
  * ws / ws_floats: caller-owned device scratch of at least ac_ekf_workspace_floats floats, else AC_ERR_WORKSPACE; after a
  * predicting step it holds x- [13][n], A [13][13][n], B [13][7][n], each on a 256-byte boundary, in this order.
  * ac_ekf_filter_f32: T steps as a host loop over the step (U [T][7][n], Z [T][15][n], mask [T][n] or NULL), the estimate
  * ping-ponging through the workspace; Xo, Po: the final estimate; ll [n]: summed over the steps in step order; the per-step
  * outputs Xs [T][13][n], Ps [T][12][12][n], nu, S [T][15][n], nis, used, status [T][n] may each be NULL.
+ * ac_ekf_filter_rec_f32: ac_ekf_filter_f32 with three more per-step outputs after status, the records a smoother reads:
+ * Xpreds [T][13][n], Ppreds, Abars [T][12][12][n] (each may be NULL), bit for bit what T calls of ac_ekf_step_f32 write to
+ * Xpred, Ppred, Abar; every other output is ac_ekf_filter_f32's bit for bit.
  * ac_ekf_measure_f32: Z [15][n] = h(X) (predict is ignored).
  * AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG for n < 0, T < 0, a NULL required pointer, or (predict set) a dt that
  * is not finite and > 0; n == 0 or T == 0 is AC_OK.  Asynchronous, no allocation, no synchronisation, hipGraph-capturable. */
@@ -697,6 +700,36 @@ int ac_ekf_filter_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const 
                       long n, long T, float* Xo, float* Po, float* ll /* [n] */, float* Xs, float* Ps, float* nu, float* S,
                       float* nis, int* used, int* status /* per step, each may be NULL */, float* ws, size_t ws_floats,
                       void* stream);
+int ac_ekf_filter_rec_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt,
+                          const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po,
+                          float* ll, float* Xs, float* Ps, float* nu, float* S, float* nis, int* used, int* status,
+                          float* Xpreds, float* Ppreds, float* Abars /* per step, each may be NULL */, float* ws, size_t ws_floats,
+                          void* stream);
+
+/* ---- RTS smoother over the trace of the extended Kalman filter (fixed-wing models) --------------------------------
+ * The fixed-interval Rauch-Tung-Striebel estimate of every node of a recorded filter run, given the whole run: one launch
+ * (k_ekf_smooth) sweeps backward in time, one instance per 16-lane group.  Nodes k = 0 .. T-1 are the filter's steps: Xf, Pf
+ * the filtered estimate (ac_ekf_filter_rec_f32's Xs, Ps), Xpred, Ppred the prediction, Abar the Jacobian that maps the error
+ * state of node k-1 to node k (its Xpreds, Ppreds, Abars).  X0, P0: the estimate the run started from, node "-1"; given (with
+ * Xs0, Ps0) it is smoothed too.  Node T-1 is copied bit for bit.  Link k = T-1 .. 1 (and 0 with X0, P0), per instance:
+ *     L L' = P-_k (plain Cholesky),   C_k = P_{k-1} Abar_k' (P-_k)^-1,   e = x^s_k [-] x-_k  ([-]: the inverse of [+]),
+ *     x^s_{k-1} = x^_{k-1} [+] C_k e,   P^s_{k-1} = 1/2 (X + X'),  X = P_{k-1} + (C_k (P^s_k - P-_k)) C_k'.
+ * As in the filter, no reset Jacobian is applied: P_k is taken as the covariance about x^_k.
+ * Outputs: Xs [T][13][n], Ps [T][12][12][n] (bitwise symmetric); Xs0 [13][n], Ps0 [12][12][n] with X0, P0, else NULL; Cg
+ * [T][12][12][n] or NULL: C_k of link k (entry 0 is zero without X0, P0); the lag-one smoothed covariance is
+ * Cov(d_k, d_{k-1} | all data) = P^s_k C_k'.  status [T][n]: entry k describes link k (entry 0 is 0 without X0, P0): 0, or
+ * value 2: an operand of the link (x^_{k-1}, P_{k-1}, x-_k, P-_k, Abar_k, the carried x^s_k, P^s_k) was not finite, else
+ * value 1: a pivot of the Cholesky was <= 0 or not finite.  In both cases C_k = 0, node k-1 is the filtered (x^_{k-1}, P_{k-1})
+ * bit for bit and the recursion goes on from it.  No instance affects another; no atomics, every sum in a fixed order: an
+ * instance's bits depend neither on n nor on its place in the batch.
+ * No workspace.  AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG for n < 0, T < 0, a NULL required pointer, X0, P0, Xs0,
+ * Ps0 not given all together, or an output that overlaps an input; n == 0 or T == 0 is AC_OK.  Asynchronous, no allocation,
+ * no synchronisation, hipGraph-capturable. */
+int ac_ekf_smooth_f32(ac_handle* h, const float* X0 /* [13][n] | NULL */, const float* P0 /* [12][12][n] | NULL */,
+                      const float* Xf /* [T][13][n] */, const float* Pf /* [T][12][12][n] */, const float* Xpred, const float* Ppred,
+                      const float* Abar, long n, long T, float* Xs /* [T][13][n] */, float* Ps /* [T][12][12][n] */,
+                      float* Xs0, float* Ps0 /* with X0, P0; else NULL */, float* Cg /* [T][12][12][n] | NULL: C_k of link k */,
+                      int* status /* [T][n] */, void* stream);
 
 /* ---- sampling-based MPC: MPPI (every model kind) ---------------------------------------------------------------
  * One MPPI iteration draws K perturbed control sequences per instance (ac_mppi_sample_f32), rolls them out and costs them with
