@@ -27,6 +27,9 @@ LQR_STATUS = {0: "converged", 1: "max_iter", 2: "breakdown", 3: "non_finite"}  #
 EKF_ROWS = 15                                         # ac_ekf_*: GPS p, GPS v, gyro, air data, magnetometer (3 rows each)
 EKF_REJECTED, EKF_NONFINITE = 1, 2                    # ac_ekf_step_f32 status bits per instance
 RTS_NOT_PD, RTS_NONFINITE = 1, 2                      # ac_ekf_smooth_f32 status bits per link and instance
+EIG_STATUS = {0: "converged", 1: "max_iter", 3: "non_finite"}  # ac_eig_f32 / ac_modes_f32 status per instance
+EIG_MAX_M = 13                                        # ac_eig_f32: 1 <= m <= 13
+MODES_FLIGHT = 0xEF8                                  # ac_modes_opts.coords: chart coordinates 3-7 and 9-11
 NUM_STATES = 13
 NUM_CONTROLS = 7
 AERO_ROWS = 22
@@ -70,6 +73,11 @@ class TrimOpts(C.Structure):
 class LqrOpts(C.Structure):
     """struct ac_lqr_opts (include/aircraft_hip.h)."""
     _fields_ = [("q", C.c_float * 12), ("r", C.c_float * 7), ("tol", C.c_float)]
+
+
+class ModesOpts(C.Structure):
+    """struct ac_modes_opts (include/aircraft_hip.h)."""
+    _fields_ = [("coords", C.c_uint), ("max_iters", C.c_int)]
 
 
 class EkfOpts(C.Structure):
@@ -212,6 +220,10 @@ PROTOTYPES = {
     "ac_ekf_filter_rec_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
                                         _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_ekf_smooth_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ac_eig_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP]),
+    "ac_modes_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_modes_f32": (C.c_int, [_VP, C.POINTER(ModesOpts), _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                               _VP, C.c_size_t, _VP]),
     "ac_mppi_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_mppi_sample_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP]),
     "ac_mppi_update_f32": (C.c_int, [_VP, C.POINTER(MppiOpts), _VP, _VP, _VP, _VP, C.c_int, C.c_long, C.c_long, _VP, _VP, _VP,

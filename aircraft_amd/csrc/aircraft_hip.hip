@@ -27,6 +27,7 @@
 #include "ac_trim.hpp"
 #include "ac_mppi.hpp"
 #include "ac_lqr.hpp"
+#include "ac_eig.hpp"
 #include "ac_ekf.hpp"
 #include "ac_rts.hpp"
 #include "ac_wgrad.hpp"
@@ -2425,6 +2426,84 @@ int ac_ekf_smooth_f32(ac_handle* h, const float* X0, const float* P0, const floa
     int grid = 0, lds = 0;
     AC_HIP(rts_launch_smooth(io, (hipStream_t)stream, &grid, &lds));
     note_launch(h, "k_ekf_smooth", grid, kRtsGroups * kEkfLanes, lds);
+    return AC_OK;
+}
+
+// ---- flight modes: batched eigenvalues of the trim linearisation (ac_eig.hpp, modes_inst.hip) ---------------------------------------
+namespace {
+constexpr size_t kModesWsPad = 5 * 64;  // the five workspace buffers each start on a 256-byte boundary
+size_t modes_ws_floats(long n) { return (size_t)n * (size_t)kModesWsFloats + kModesWsPad; }
+const char* const kModesFixedWing = "the flight modes about a trim are defined for the fixed-wing models only";
+bool modes_overlap(const RtsSpan* out, int n_out, const RtsSpan* in, int n_in) {
+    for (int a = 0; a < n_out; ++a)
+        for (int b = 0; b < n_in; ++b)
+            if (rts_overlap(out[a], in[b])) return true;
+    return false;
+}
+}  // namespace
+
+int ac_eig_f32(ac_handle* h, const float* M, int m, int max_iters, long n, float* wr, float* wi, int* status, int* iters,
+               void* stream) {
+    AC_ENTER(h);
+    if (!h || n < 0) return AC_ERR_BAD_ARG;
+    if (m < 1 || m > kEigMaxM) return fail(AC_ERR_BAD_ARG, "eig: m must be 1 .. 13");
+    if (max_iters < 0) return fail(AC_ERR_BAD_ARG, "eig: max_iters must be >= 0 (0: 30)");
+    if (n == 0) return AC_OK;
+    if (!M || !wr || !wi || !status) return fail(AC_ERR_BAD_ARG, "eig: a required pointer is NULL");
+    const size_t N = (size_t)n, mm = (size_t)m;
+    const RtsSpan in[] = {{M, mm * mm * N}};
+    const RtsSpan out[] = {{wr, mm * N}, {wi, mm * N}, {(const float*)status, N}, {(const float*)iters, N}};
+    if (modes_overlap(out, 4, in, 1)) return fail(AC_ERR_BAD_ARG, "eig: an output overlaps an input");
+    int grid = 0, lds = 0;
+    AC_HIP(eig_launch(M, m, max_iters ? max_iters : kEigDefaultIters, n, wr, wi, status, iters, (hipStream_t)stream, &grid, &lds));
+    note_launch(h, "k_eig", grid, eig_lanes(m), lds);
+    return AC_OK;
+}
+
+int ac_modes_workspace_floats(const ac_handle* h, long n, size_t* floats) {
+    if (!h || !floats || n < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kModesFixedWing);
+    *floats = modes_ws_floats(n);
+    return AC_OK;
+}
+
+int ac_modes_f32(ac_handle* h, const ac_modes_opts* o, const float* X, const float* U, float dt, const float* K, long n, float* Axi,
+                 float* Bxi, float* wr, float* wi, float* sigma, float* omega, int* status, int* iters, float* ws, size_t ws_floats,
+                 void* stream) {
+    AC_ENTER(h);
+    if (!h || !o || n < 0) return AC_ERR_BAD_ARG;
+    if (!(dt > 0.f) || !(dt <= 3.0e38f)) return fail(AC_ERR_BAD_ARG, "modes: dt must be finite and > 0");
+    if (o->max_iters < 0) return fail(AC_ERR_BAD_ARG, "modes: max_iters must be >= 0 (0: 30)");
+    const unsigned coords = o->coords ? o->coords : kModesFlight;
+    if ((coords & kModesFlight) != kModesFlight || (coords >> 12) != 0u)
+        return fail(AC_ERR_BAD_ARG, "modes: coords must keep the chart coordinates 3-7 and 9-11 and set no bit >= 12");
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kModesFixedWing);
+    if (n == 0) return AC_OK;
+    if (!X || !U || !wr || !wi || !sigma || !omega || !status) return fail(AC_ERR_BAD_ARG, "modes: a required pointer is NULL");
+    int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    if (!ws || ws_floats < modes_ws_floats(n)) return fail(AC_ERR_WORKSPACE, "modes workspace too small: see ac_modes_workspace_floats");
+    const size_t N = (size_t)n;
+    const RtsSpan in[] = {{X, 13 * N}, {U, 7 * N}, {K, 84 * N}};
+    const RtsSpan out[] = {{Axi, 144 * N}, {Bxi, 84 * N}, {wr, 12 * N}, {wi, 12 * N}, {sigma, 12 * N}, {omega, 12 * N},
+                           {(const float*)status, N}, {(const float*)iters, N}, {ws, ws_floats}};
+    if (modes_overlap(out, 9, in, 3)) return fail(AC_ERR_BAD_ARG, "modes: an output overlaps an input");
+    float* const Xp = align256(ws);
+    float* const A = align256(Xp + 13 * N);
+    float* const Bm = align256(A + 169 * N);
+    float* const Aw = align256(Bm + 91 * N);
+    float* const Bw = align256(Aw + 144 * N);  // ends at most ws + 501 N + 5 * 63 floats
+    if (!Axi) Axi = Aw;
+    if (!Bxi) Bxi = Bw;
+    rc = sens_impl(h, X, U, dt, nullptr, n, n, Xp, A, Bm, nullptr, stream);
+    if (rc != AC_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int grid = 0, lds = 0, m = 0;
+    for (int i = 0; i < 12; ++i) m += (int)((coords >> i) & 1u);
+    AC_HIP(lqr_launch_project(X, U, Xp, A, Bm, n, Axi, Bxi, st, &grid));
+    AC_HIP(modes_launch_eig(Axi, Bxi, K, coords, m, o->max_iters ? o->max_iters : kEigDefaultIters, dt, n, wr, wi, sigma, omega,
+                            status, iters, st, &grid, &lds));
+    note_launch(h, "k_modes_eig", grid, eig_lanes(m), lds);
     return AC_OK;
 }
 

@@ -19,7 +19,7 @@ from ..utils import AircraftConfiguration
 from .base import SixDOF, SixDOFOpts
 from .coefficient_models import COEFF_MODEL_REGISTRY, CoefficientModel, DefaultModel
 
-__all__ = ["Aircraft", "AircraftOpts", "TrimResult", "LqrResult", "EKF", "EkfTrace", "EkfSmooth"]
+__all__ = ["Aircraft", "AircraftOpts", "TrimResult", "LqrResult", "ModesResult", "EKF", "EkfTrace", "EkfSmooth"]
 
 
 def _torch_mod():
@@ -90,6 +90,31 @@ class LqrResult:
         """Raw-state gains K_x,k = -K E(x_k) along a nominal Xnom (H+1, 13, n) -> (H, 7, 13, n): the feedback
         u = U_k + K_x,k (x - Xnom_k) of ac_rollout_policy_f32 / ILQR.closed_loop."""
         return self.system._lqr_gains(Xnom, self.K)
+
+
+@dataclass
+class ModesResult:
+    """Aircraft.modes' result for n instances (numpy in -> numpy out, float64 / complex128; tensors stay on the device,
+    complex64).  lam (m, n): the eigenvalues of the step linearised in the kept chart coordinates, in the canonical order
+    (descending |lam|, then descending imaginary part, then descending real part; include/aircraft_hip.h, ac_eig_f32);
+    s (m, n) = log(lam) / dt = sigma + i omega [1/s, rad/s]; wn = |s| [rad/s]; zeta = -sigma / |s| (NaN where s = 0);
+    rho (n,) = max |lam|; unstable (n,): the number of |lam| > 1; A (12, 12, n), B (12, 7, n): the step linearised in the
+    chart (what Aircraft.lqr returns); coords: the kept chart coordinates; status (n,): 0 all eigenvalues found, 1 the
+    iteration cap was reached, 3 non-finite input (lam, s NaN); converged (n,) = status == 0; iterations (n,): QR iterations
+    used; dt: the step length."""
+    lam: Any
+    s: Any
+    wn: Any
+    zeta: Any
+    rho: Any
+    unstable: Any
+    A: Any
+    B: Any
+    coords: Any
+    status: Any
+    converged: Any
+    iterations: Any
+    dt: float = 0.0
 
 
 @dataclass
@@ -650,6 +675,139 @@ class Aircraft(SixDOF):
         if npx:
             out = tuple(t.cpu().numpy().astype(np.float64) for t in out)
         return tuple(t[..., 0] for t in out) if vec else out
+
+    # ---- flight modes: eigenvalues of the linearised step (include/aircraft_hip.h, ac_modes_f32) -------
+    MODES_COORDS = {"flight": (3, 4, 5, 6, 7, 9, 10, 11), "path": (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11), "all": tuple(range(12))}
+
+    def modes_workspace(self, n: int):
+        """Device workspace of a modes call of n instances (ac_modes_workspace_floats); allocate it before capturing a graph."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_modes_workspace_floats(self._handle, int(n), C.byref(need)), "ac_modes_workspace_floats")
+        return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
+
+    @classmethod
+    def _modes_coords(cls, coords):
+        if isinstance(coords, str):
+            if coords not in cls.MODES_COORDS:
+                raise ValueError(f"modes: coords must be one of {sorted(cls.MODES_COORDS)} or a sequence of indices, got {coords!r}")
+            return cls.MODES_COORDS[coords]
+        try:
+            seq = list(coords)
+            idx = [int(c) for c in seq]
+            if any(isinstance(c, bool) or float(c) != i for c, i in zip(seq, idx)):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"modes: coords must be a name or a sequence of chart coordinate indices, got {coords!r}") from None
+        if len(set(idx)) != len(idx) or any(c < 0 or c > 11 for c in idx) or not set(cls.MODES_COORDS["flight"]) <= set(idx):
+            raise ValueError("modes: coords must be distinct indices 0 .. 11 that include the flight coordinates 3-7 and 9-11")
+        return tuple(sorted(idx))
+
+    def modes(self, trim_or_xu, dt, gains=None, coords="flight", max_iters=30, ws=None) -> ModesResult:
+        """Flight modes of n instances: the eigenvalues of the step of length dt linearised in the steady-flight chart
+        (steady_error) at `trim_or_xu`, a TrimResult or an (x (13, n), u (7, n)) pair; any state will do, at a trim the
+        linearisation is that of the whole trim helix.  gains: None (open loop), an LqrResult (its K; its dt must be this
+        dt) or a (7, 12, n) array K: the closed loop A - B K.  coords: "flight" (body velocity, tilt, body rates: 8), "path"
+        (without along-track: 11), "all" (12) or a sequence of chart coordinate indices that includes the flight eight.
+        max_iters: QR iterations per eigenvalue at most.  No host synchronisation (graph-capturable with a workspace from
+        modes_workspace(n))."""
+        torch = _torch_mod()
+        if isinstance(trim_or_xu, TrimResult):
+            x, u = trim_or_xu.x, trim_or_xu.u
+        elif isinstance(trim_or_xu, (tuple, list)) and len(trim_or_xu) == 2:
+            x, u = trim_or_xu
+        else:
+            raise ValueError("modes: pass a TrimResult or an (x, u) pair")
+        shp = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)  # noqa: E731
+        sx, su = shp(x), shp(u)
+        if len(sx) not in (1, 2) or sx[0] != 13 or len(su) != len(sx) or su[0] != _lib.NUM_CONTROLS or sx[1:] != su[1:]:
+            raise ValueError(f"modes: expected x (13, n) and u (7, n), got {sx} and {su}")
+        if isinstance(dt, bool) or np.ndim(dt) != 0 or not np.isfinite(float(dt)) or float(dt) <= 0:
+            raise ValueError(f"modes: dt must be a finite scalar > 0, got {dt!r}")
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 1:
+            raise ValueError(f"modes: max_iters must be an integer >= 1, got {max_iters!r}")
+        kept = self._modes_coords(coords)
+        Kin = None
+        if isinstance(gains, LqrResult):
+            if float(gains.dt) != float(dt):
+                raise ValueError(f"modes: the gains were designed for dt = {gains.dt!r}, not {dt!r}")
+            Kin = gains.K
+        elif gains is not None:
+            Kin = gains
+        if Kin is not None and shp(Kin) != (7, 12) + sx[1:]:
+            raise ValueError(f"modes: expected gains (7, 12, n) for x {sx}, got {shp(Kin)}")
+        if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.float32 or not ws.is_cuda
+                               or not ws.is_contiguous()):
+            raise ValueError("modes: ws must be a contiguous float32 device tensor (modes_workspace(n))")
+
+        # ---- device side ----
+        lib = self._sync()
+        X, npx, vec = self._in(x, self.num_states, "x")
+        U, _, _ = self._in(u, _lib.NUM_CONTROLS, "u")
+        n = X.shape[1]
+        dev = X.device
+        Kt = None
+        if Kin is not None:
+            Kt = Kin if isinstance(Kin, torch.Tensor) else torch.as_tensor(np.asarray(Kin, dtype=np.float32))
+            Kt = Kt.to(device=dev, dtype=torch.float32).reshape(7, 12, n).contiguous()
+        opts = _lib.ModesOpts()
+        opts.coords = sum(1 << c for c in kept)
+        opts.max_iters = int(max_iters)
+        if ws is None:
+            ws = self.modes_workspace(n)
+        f32 = dict(device=dev, dtype=torch.float32)
+        A, Bm = torch.empty((12, 12, n), **f32), torch.empty((12, 7, n), **f32)
+        out = torch.empty((4, 12, n), **f32)
+        S, it = torch.empty((n,), device=dev, dtype=torch.int32), torch.empty((n,), device=dev, dtype=torch.int32)
+        _lib.check(lib.ac_modes_f32(self._handle, C.byref(opts), X.data_ptr(), U.data_ptr(), C.c_float(float(dt)),
+                                    Kt.data_ptr() if Kt is not None else None, n, A.data_ptr(), Bm.data_ptr(), out[0].data_ptr(),
+                                    out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), S.data_ptr(), it.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), self._stream()), "ac_modes_f32")
+        m = len(kept)
+        lam = torch.complex(out[0, :m], out[1, :m])
+        s = torch.complex(out[2, :m], out[3, :m])
+        if npx:
+            lam, s = lam.cpu().numpy().astype(np.complex128), s.cpu().numpy().astype(np.complex128)
+            A, Bm = (t.cpu().numpy().astype(np.float64) for t in (A, Bm))
+            S, it = S.cpu().numpy(), it.cpu().numpy()
+            mag, wn = np.abs(lam), np.abs(s)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                zeta = -s.real / wn
+            rho, unstable = mag.max(axis=0), (mag > 1).sum(axis=0)
+        else:
+            mag, wn = lam.abs(), s.abs()
+            zeta = -s.real / wn
+            rho, unstable = mag.max(dim=0).values, (mag > 1).sum(dim=0)
+        res = [lam, s, wn, zeta, rho, unstable, A, Bm]
+        tail = [S, S == 0, it]
+        if vec:
+            res, tail = [t[..., 0] for t in res], [t[..., 0] for t in tail]
+        return ModesResult(*res, kept, *tail, float(dt))
+
+    def eig(self, M):
+        """Eigenvalues of n real m x m matrices M (m, m, n) or (m, m), 1 <= m <= 13, on the device (ac_eig_f32) ->
+        (lam (m, n) complex in the canonical order of ModesResult.lam, status (n,): 0 found, 1 iteration cap, 3 non-finite)."""
+        torch = _torch_mod()
+        from_np = not isinstance(M, torch.Tensor)
+        sm = np.shape(M) if from_np else tuple(M.shape)
+        if len(sm) not in (2, 3) or sm[0] != sm[1] or not 1 <= sm[0] <= _lib.EIG_MAX_M:
+            raise ValueError(f"eig: expected M (m, m, n) or (m, m) with 1 <= m <= {_lib.EIG_MAX_M}, got {sm}")
+        lib = self._sync()
+        dev = self._device_obj()
+        Mt = torch.as_tensor(np.asarray(M, dtype=np.float32) if from_np else M).to(device=dev, dtype=torch.float32)
+        vec = Mt.dim() == 2
+        if vec:
+            Mt = Mt.unsqueeze(-1)
+        Mt = Mt.contiguous()
+        m, n = Mt.shape[0], Mt.shape[2]
+        w = torch.empty((2, m, n), device=dev, dtype=torch.float32)
+        S = torch.empty((n,), device=dev, dtype=torch.int32)
+        _lib.check(lib.ac_eig_f32(self._handle, Mt.data_ptr(), m, 0, n, w[0].data_ptr(), w[1].data_ptr(), S.data_ptr(), None,
+                                  self._stream()), "ac_eig_f32")
+        lam = torch.complex(w[0], w[1])
+        if from_np:
+            lam, S = lam.cpu().numpy().astype(np.complex128), S.cpu().numpy()
+        return (lam[..., 0], S[..., 0]) if vec else (lam, S)
 
     # ---- extended Kalman filter (include/aircraft_hip.h, ac_ekf_step_f32; DESIGN.md §4.14) -------------------------------
     EKF_MAG_NED = (0.45, 0.03, 0.89)  # a northern mid-latitude field direction (north, east, down), the default of mag_ned

@@ -731,6 +731,43 @@ int ac_ekf_smooth_f32(ac_handle* h, const float* X0 /* [13][n] | NULL */, const 
                       float* Xs0, float* Ps0 /* with X0, P0; else NULL */, float* Cg /* [T][12][12][n] | NULL: C_k of link k */,
                       int* status /* [T][n] */, void* stream);
 
+/* ---- flight modes: eigenvalues of the trim linearisation ---------------------------------------------------------
+ * ac_eig_f32 (any handle): the eigenvalues of n real m x m matrices M [m][m][n], 1 <= m <= 13, float32 in and out with float64
+ * arithmetic between (the eigenvalues carry the rounding of the output, 6e-8, not the matrix's conditioning), one instance per
+ * lane (k_eig): balancing as LAPACK gebal does it (the permutation search that isolates every row or column whose off-diagonal
+ * part is exactly zero, then scaling by powers of two), Householder reduction to Hessenberg form, Francis double-shift QR
+ * (EISPACK hqr: deflation at 2^-52, exceptional shifts at the 10th and 20th iteration of an eigenvalue, at most max_iters
+ * iterations per eigenvalue, 0: 30).  wr, wi [m][n] in the CANONICAL ORDER: descending wr^2 + wi^2, then descending imaginary
+ * part (the + member of a pair first), then descending real part; a conjugate pair has the same real part bit for bit and
+ * imaginary parts +z, -z.  status [n]: 0 all m eigenvalues found; 1 the cap was reached: the instance's outputs are NaN; 3 a
+ * non-finite entry: outputs NaN, no iteration.  iters [n] or NULL: QR iterations used.  No workspace.
+ * ac_modes_f32 (fixed-wing models), per instance at (X, U), which need not be a trim:
+ *   1. the handle's own ac_step_sens_f32 launch writes x+ = F(x, u, dt), A, B into the workspace (every model and engine);
+ *   2. k_lqr_project: A_xi, B_xi in the steady-flight chart, bit for bit what ac_lqr_f32 exports (Axi, Bxi: optional outputs);
+ *   3. k_modes_eig: a copy of A_xi with the entries [rows 3-7, 9-11][columns 0, 1, 2, 8] set to exactly 0 (they are 0 by the
+ *      translation and yaw invariance of the dynamics; the projection leaves float32 noise there), minus B_xi K when K
+ *      [7][12][n] is given (u = u_b - K xi), restricted to the rows and columns of `coords` (m of them, 8 .. 12), its
+ *      eigenvalues as above, and s = log(lambda) / dt as sigma = log1p((wr - 1)(wr + 1) + wi^2) / (2 dt) [1/s] and
+ *      omega = atan2(wi, wr) / dt [rad/s].  wr, wi, sigma, omega [12][n]: rows >= m are 0.
+ * No instance affects another, and an instance's bits depend neither on n nor on its place in the batch.
+ * ws / ws_floats: caller-owned device scratch of at least ac_modes_workspace_floats(h, n) floats, else AC_ERR_WORKSPACE; after
+ * the call it holds x+ [13][n], A [13][13][n], B [13][7][n], A_xi [12][12][n], B_xi [12][7][n], each on a 256-byte boundary, in
+ * this order (A_xi, B_xi only when the outputs Axi, Bxi are NULL).
+ * AC_ERR_BAD_ARG for m outside 1 .. 13, max_iters < 0, n < 0, a NULL required pointer, a `coords` that lacks one of the bits
+ * 3-7, 9-11 or sets a bit >= 12, a dt that is not finite and > 0, or an output that overlaps an input; AC_ERR_UNSUPPORTED from
+ * ac_modes_f32 for the quadrotor; n == 0 is AC_OK.  Asynchronous, no allocation, no synchronisation, hipGraph-capturable. */
+int ac_eig_f32(ac_handle* h, const float* M /* [m][m][n] */, int m, int max_iters /* 0: 30 */, long n, float* wr, float* wi /* [m][n] */,
+               int* status /* [n] */, int* iters /* [n] | NULL */, void* stream);
+typedef struct ac_modes_opts {
+    unsigned coords; /* bit i: chart coordinate i is kept; bits 3-7 and 9-11 are required; 0 = the eight flight coordinates (0xEF8) */
+    int max_iters;   /* 0: 30 */
+} ac_modes_opts;
+int ac_modes_workspace_floats(const ac_handle* h, long n, size_t* floats);
+int ac_modes_f32(ac_handle* h, const ac_modes_opts* o, const float* X /* [13][n] */, const float* U /* [7][n] */, float dt,
+                 const float* K /* [7][12][n] | NULL: open loop */, long n, float* Axi /* [12][12][n] | NULL */,
+                 float* Bxi /* [12][7][n] | NULL */, float* wr, float* wi, float* sigma, float* omega /* each [12][n] */,
+                 int* status /* [n] */, int* iters /* [n] | NULL */, float* ws, size_t ws_floats, void* stream);
+
 /* ---- sampling-based MPC: MPPI (every model kind) ---------------------------------------------------------------
  * One MPPI iteration draws K perturbed control sequences per instance (ac_mppi_sample_f32), rolls them out and costs them with
  * the calls above (candidate k of instance b is column o = k*B + b, the layout ac_rollout_policy_f32 writes), and blends them by
