@@ -27,6 +27,8 @@ LQR_STATUS = {0: "converged", 1: "max_iter", 2: "breakdown", 3: "non_finite"}  #
 EKF_ROWS = 15                                         # ac_ekf_*: GPS p, GPS v, gyro, air data, magnetometer (3 rows each)
 EKF_REJECTED, EKF_NONFINITE = 1, 2                    # ac_ekf_step_f32 status bits per instance
 RTS_NOT_PD, RTS_NONFINITE = 1, 2                      # ac_ekf_smooth_f32 status bits per link and instance
+EM_NOT_PD, EM_NONFINITE = 1, 2                        # ac_ekf_em_f32 status values per node and instance
+EM_CHUNK = 32                                         # ac_ekf_em_f32: nodes per float64 partial sum (kEmChunk)
 EIG_STATUS = {0: "converged", 1: "max_iter", 3: "non_finite"}  # ac_eig_f32 / ac_modes_f32 status per instance
 EIG_MAX_M = 13                                        # ac_eig_f32: 1 <= m <= 13
 MODES_FLIGHT = 0xEF8                                  # ac_modes_opts.coords: chart coordinates 3-7 and 9-11
@@ -83,6 +85,11 @@ class ModesOpts(C.Structure):
 class EkfOpts(C.Structure):
     """struct ac_ekf_opts (include/aircraft_hip.h)."""
     _fields_ = [("mag_ned", C.c_float * 3), ("predict", C.c_int)]
+
+
+class EkfEmOpts(C.Structure):
+    """struct ac_ekf_em_opts (include/aircraft_hip.h)."""
+    _fields_ = [("mag_ned", C.c_float * 3), ("floor_rel", C.c_float)]
 
 
 class MppiOpts(C.Structure):
@@ -220,6 +227,9 @@ PROTOTYPES = {
     "ac_ekf_filter_rec_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
                                         _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_ekf_smooth_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ac_ekf_em_workspace_floats": (C.c_int, [_VP, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_ekf_em_f32": (C.c_int, [_VP, C.POINTER(EkfEmOpts), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP,
+                                _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_eig_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP]),
     "ac_modes_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_modes_f32": (C.c_int, [_VP, C.POINTER(ModesOpts), _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,

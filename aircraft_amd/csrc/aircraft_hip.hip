@@ -30,6 +30,7 @@
 #include "ac_eig.hpp"
 #include "ac_ekf.hpp"
 #include "ac_rts.hpp"
+#include "ac_em.hpp"
 #include "ac_wgrad.hpp"
 #include "ac_cgrad.hpp"
 #include "ac_agrad.hpp"
@@ -2504,6 +2505,50 @@ int ac_modes_f32(ac_handle* h, const ac_modes_opts* o, const float* X, const flo
     AC_HIP(modes_launch_eig(Axi, Bxi, K, coords, m, o->max_iters ? o->max_iters : kEigDefaultIters, dt, n, wr, wi, sigma, omega,
                             status, iters, st, &grid, &lds));
     note_launch(h, "k_modes_eig", grid, eig_lanes(m), lds);
+    return AC_OK;
+}
+
+// ---- EM statistics for the noise variances of the EKF (ac_em.hpp, em_inst.hip) --------------------------------------------------------
+namespace {
+constexpr size_t kEmWsPad = 2 * 64;  // the two workspace buffers each start on a 256-byte boundary
+// [chunks][27][n] float64, then [chunks][16][n] int32
+size_t em_ws_floats(long n, long T) { return (size_t)em_chunks(T) * (size_t)n * (size_t)(2 * kEmRows + kEmCounts) + kEmWsPad; }
+}  // namespace
+
+int ac_ekf_em_workspace_floats(const ac_handle* h, long n, long T, size_t* floats) {
+    if (!h || !floats || n < 0 || T < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    *floats = em_ws_floats(n, T);
+    return AC_OK;
+}
+
+int ac_ekf_em_f32(ac_handle* h, const ac_ekf_em_opts* o, const float* Xpred, const float* Ppred, const float* Xs, const float* Ps,
+                  const float* Z, const int* used, const float* Qd, const float* Rd, long n, long T, float* Qsum, float* Rsum,
+                  int* nq, int* nr, int* status, float* Qn, float* Rn, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !o || n < 0 || T < 0) return AC_ERR_BAD_ARG;
+    if (!(o->floor_rel >= 0.f) || !(o->floor_rel <= 3.0e38f)) return fail(AC_ERR_BAD_ARG, "ekf em: floor_rel must be finite and >= 0 (0: 1e-4)");
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    if (n == 0) return AC_OK;
+    if (!Qd || !Rd || !Qsum || !Rsum || !nq || !nr || (T > 0 && (!Xpred || !Ppred || !Xs || !Ps || !Z || !used || !status)))
+        return fail(AC_ERR_BAD_ARG, "ekf em: a required pointer is NULL");
+    const size_t N = (size_t)n, K = (size_t)T;
+    const long gb = (n + kEmGroups - 1) / kEmGroups;
+    if (em_chunks(T) > 2147483647L / gb || (long)kEmRows * n / kEmBlock >= 2147483647L)
+        return fail(AC_ERR_BAD_ARG, "ekf em: n * T exceeds the launch dimension");
+    if (!ws || ws_floats < em_ws_floats(n, T)) return fail(AC_ERR_WORKSPACE, "ekf em workspace too small: see ac_ekf_em_workspace_floats");
+    const RtsSpan in[] = {{Xpred, K * 13 * N}, {Ppred, K * 144 * N}, {Xs, K * 13 * N}, {Ps, K * 144 * N}, {Z, K * 15 * N},
+                          {(const float*)used, K * N}, {Qd, 12 * N}, {Rd, 15 * N}};
+    const RtsSpan out[] = {{Qsum, 12 * N}, {Rsum, 15 * N}, {(const float*)nq, N}, {(const float*)nr, 15 * N},
+                           {(const float*)status, K * N}, {Qn, 12 * N}, {Rn, 15 * N}, {ws, ws_floats}};
+    if (modes_overlap(out, 8, in, 8)) return fail(AC_ERR_BAD_ARG, "ekf em: an output overlaps an input");
+    double* const part = (double*)align256(ws);
+    int* const cnt = (int*)align256((float*)part + (size_t)em_chunks(T) * 2 * kEmRows * N);  // ends at most ws + 70 chunks N + 2 * 63 floats
+    EmIo io{Xpred, Ppred, Xs, Ps, Z, used, Qd, Rd, part, cnt, Qsum, Rsum, nq, nr, status, Qn, Rn, {o->mag_ned[0], o->mag_ned[1], o->mag_ned[2]},
+            h->dp.p.epsilon, o->floor_rel, n, T};
+    int grid = 0, lds = 0;
+    AC_HIP(em_launch(io, (hipStream_t)stream, &grid, &lds));
+    note_launch(h, T > 0 ? "k_ekf_em_nodes" : "k_ekf_em_reduce", grid, kEmGroups * kEkfLanes, lds);
     return AC_OK;
 }
 

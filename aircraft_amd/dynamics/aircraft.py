@@ -19,7 +19,8 @@ from ..utils import AircraftConfiguration
 from .base import SixDOF, SixDOFOpts
 from .coefficient_models import COEFF_MODEL_REGISTRY, CoefficientModel, DefaultModel
 
-__all__ = ["Aircraft", "AircraftOpts", "TrimResult", "LqrResult", "ModesResult", "EKF", "EkfTrace", "EkfSmooth"]
+__all__ = ["Aircraft", "AircraftOpts", "TrimResult", "LqrResult", "ModesResult", "EKF", "EkfTrace", "EkfSmooth", "EkfNoiseStats",
+           "EkfNoiseFit"]
 
 
 def _torch_mod():
@@ -163,6 +164,36 @@ class EkfSmooth:
     status: Any
 
 
+@dataclass
+class EkfNoiseStats:
+    """What EKF.noise_stats returns for a recorded filter run and its smoothed trace (numpy in -> numpy out; tensors stay on
+    the device): the M-step of an EM estimate of the diagonal Q and R (include/aircraft_hip.h, ac_ekf_em_f32).
+    Qsum (12, n), nq (n,): the sum over the counted nodes of E[w_kj^2 | all data] and their number; Rsum, nr (15, n): the sum of
+    (z_i - h_i(x^s_k))^2 + h_i P^s_k h_i' over the nodes at which row i was used, and their number.  q (12, n), r (15, n): the new
+    variances max(sum / count, floor x the bank's), the bank's own where nothing was counted.  status (T, n) per node: 0, 1 the
+    predicted covariance was not positive definite (the node is out of Q, its R terms count), 2 an operand was not finite (the
+    node adds nothing)."""
+    Qsum: Any
+    Rsum: Any
+    nq: Any
+    nr: Any
+    q: Any
+    r: Any
+    status: Any
+
+
+@dataclass
+class EkfNoiseFit:
+    """What EKF.fit_noise returns: q (12, n), r (15, n) the fitted variances (the bank holds them); ll (iters + 1, n): the
+    filter's log-likelihood before each update and after the last one; nq, nr, status: EkfNoiseStats' of the last iteration."""
+    q: Any
+    r: Any
+    ll: Any
+    nq: Any
+    nr: Any
+    status: Any
+
+
 class EKF:
     """A bank of n extended Kalman filters over one Aircraft's step sensitivities (Aircraft.ekf).  `x`
     (13, n) and `P` (12, 12, n) are the current estimate; step / update / filter advance it and return an EkfTrace.
@@ -170,7 +201,8 @@ class EKF:
     a row is used when its mask bit is set (mask (n,) integers, bit i = row i; None: all) and its z is finite, so a sensor
     that did not report is a NaN or a cleared bit.  No host synchronisation: with `ws` from Aircraft.ekf_workspace(n) the
     calls can be captured in a graph.  For a recorded flight, filter(..., record=True) keeps what smooth(trace) reads: the
-    fixed-interval (RTS) estimate of every step given the whole run."""
+    fixed-interval (RTS) estimate of every step given the whole run, and noise_stats(trace, smooth, Z) /
+    fit_noise(U, dt, Z) estimate the variances q, r from it by EM."""
 
     def __init__(self, system, X, P, Qd, Rd, mag_ned, ws, from_np, vec):
         self.system, self._X, self._P, self._Qd, self._Rd, self._ws = system, X, P, Qd, Rd, ws
@@ -194,6 +226,33 @@ class EKF:
     @property
     def P(self):
         return self._give(self._P)
+
+    @property
+    def q(self):
+        return self._give(self._Qd)
+
+    @property
+    def r(self):
+        return self._give(self._Rd)
+
+    def set_noise(self, q=None, r=None):
+        """Replace the process-noise variances q ((12,) or (12, n); >= 0) and / or the measurement variances r ((15,) or (15, n);
+        > 0).  Values on the host are checked (those of tensors already on a device are not read)."""
+        torch = _torch_mod()
+        new = {}
+        for a, rows, name in ((q, 12, "q"), (r, _lib.EKF_ROWS, "r")):
+            if a is None:
+                continue
+            shp = tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+            if shp not in ((rows,), (rows, self.n)):
+                raise ValueError(f"ekf: {name} must have shape ({rows},) or ({rows}, {self.n}), got {shp}")
+            if not (isinstance(a, torch.Tensor) and a.is_cuda):
+                v = a.detach().cpu().numpy().astype(np.float64) if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64)
+                if not np.isfinite(v).all() or (v < 0).any() or (name == "r" and (v <= 0).any()):
+                    raise ValueError("ekf: q must be finite and >= 0" if name == "q" else "ekf: r must be finite and > 0")
+            t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float32))
+            new[name] = t.to(device=self._X.device, dtype=torch.float32).reshape(rows, -1).expand(rows, self.n).contiguous().clone()
+        self._Qd, self._Rd = new.get("q", self._Qd), new.get("r", self._Rd)
 
     def _opts(self, predict):
         o = _lib.EkfOpts()
@@ -261,6 +320,10 @@ class EKF:
     def filter(self, U, dt, Z, mask=None, record=False) -> EkfTrace:
         """T steps: U (T, 7, n), Z (T, 15, n), mask (T, n) or None -> the per-step EkfTrace (leading axis T; ll (n,) summed).
         record=True: the trace also carries Xpred, Ppred, Abar of every step and the starting X0, P0 (what smooth reads)."""
+        dt, T, Zt, Ut, M = self._filter_args(U, dt, Z, mask)
+        return EkfTrace(*(self._give(t) for t in self._filter(Ut, dt, Zt, M, T, record)))
+
+    def _filter_args(self, U, dt, Z, mask):
         torch = _torch_mod()
         dt = self._dt(dt, True)
         shape = tuple(Z.shape) if isinstance(Z, torch.Tensor) else np.shape(Z)
@@ -270,6 +333,11 @@ class EKF:
         Zt = self._rows(Z, (T,), _lib.EKF_ROWS, "Z")
         Ut = self._rows(U, (T,), _lib.NUM_CONTROLS, "U")
         M = None if mask is None else self._rows(mask, (T,), None, "mask", torch.int32)
+        return dt, T, Zt, Ut, M
+
+    def _filter(self, Ut, dt, Zt, M, T, record):
+        """the device tensors of EkfTrace's fields, in order"""
+        torch = _torch_mod()
         sysm, n, dev = self.system, self.n, self._X.device
         lib = sysm._sync()
         f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
@@ -290,7 +358,7 @@ class EKF:
             _lib.check(lib.ac_ekf_filter_f32(*head, *tail), "ac_ekf_filter_f32")
         if T:
             self._X, self._P = Xo, Po
-        return EkfTrace(*(self._give(t) for t in (Xs, Ps, nu, S, nis, ll, used, st) + rec))
+        return (Xs, Ps, nu, S, nis, ll, used, st) + rec
 
     def smooth(self, trace, initial=True, gains=False) -> EkfSmooth:
         """The fixed-interval (RTS) smoother over a recorded run, trace = filter(..., record=True): every node's estimate given
@@ -311,6 +379,12 @@ class EKF:
         Pf, Pp, Ab = (self._rows(getattr(trace, k), (T, 12), 12, f"trace.{k}") for k in ("P", "Ppred", "Abar"))
         X0 = self._rows(trace.X0, (), 13, "trace.X0") if initial else None
         P0 = self._rows(trace.P0, (12,), 12, "trace.P0") if initial else None
+        return EkfSmooth(*(None if t is None else self._give(t) for t in self._smooth(X0, P0, Xf, Pf, Xp, Pp, Ab, T, gains)))
+
+    def _smooth(self, X0, P0, Xf, Pf, Xp, Pp, Ab, T, gains):
+        """the device tensors of EkfSmooth's fields, in order"""
+        torch = _torch_mod()
+        initial = X0 is not None
         sysm, n, dev = self.system, self.n, self._X.device
         lib = sysm._sync()
         f32 = dict(device=dev, dtype=torch.float32)
@@ -322,7 +396,95 @@ class EKF:
         _lib.check(lib.ac_ekf_smooth_f32(sysm._handle, ptr(X0), ptr(P0), Xf.data_ptr(), Pf.data_ptr(), Xp.data_ptr(), Pp.data_ptr(),
                                          Ab.data_ptr(), n, T, Xs.data_ptr(), Ps.data_ptr(), ptr(Xs0), ptr(Ps0), ptr(Cg), st.data_ptr(),
                                          sysm._stream()), "ac_ekf_smooth_f32")
-        return EkfSmooth(*(None if t is None else self._give(t) for t in (Xs, Ps, Xs0, Ps0, Cg, st)))
+        return Xs, Ps, Xs0, Ps0, Cg, st
+
+    # ---- EM estimate of q and r (include/aircraft_hip.h, ac_ekf_em_f32) ---------------------------------
+    @staticmethod
+    def _floor(floor):
+        if isinstance(floor, bool) or np.ndim(floor) != 0 or not np.isfinite(float(floor)) or float(floor) < 0:
+            raise ValueError(f"ekf: floor must be a finite scalar >= 0, got {floor!r}")
+        return float(floor)
+
+    def noise_stats(self, trace, smooth, Z, floor=1e-4) -> EkfNoiseStats:
+        """The M-step of an EM estimate of q and r from trace = filter(U, dt, Z, mask, record=True), made with the bank's present
+        q, r, and smooth = smooth(trace): one launch pair over (instances) x (chunks of 32 nodes).  floor: the new variances are
+        at least floor x the present ones (0 means 1e-4).  -> EkfNoiseStats; the bank's q, r are not changed (set_noise)."""
+        torch = _torch_mod()
+        floor = self._floor(floor)
+        if not isinstance(trace, EkfTrace) or not isinstance(smooth, EkfSmooth):
+            raise ValueError("ekf noise_stats: expected the EkfTrace of filter(..., record=True) and the EkfSmooth of smooth(trace)")
+        missing = [f"trace.{k}" for k in ("Xpred", "Ppred", "used") if getattr(trace, k) is None]
+        missing += [f"smooth.{k}" for k in ("X", "P") if getattr(smooth, k) is None]
+        if missing:
+            raise ValueError(f"ekf noise_stats: {', '.join(missing)} missing: run filter(..., record=True) and smooth(trace)")
+        shape = tuple(Z.shape) if isinstance(Z, torch.Tensor) else np.shape(Z)
+        if len(shape) != (2 if self._vec else 3):
+            raise ValueError(f"ekf noise_stats: Z must have shape (T, 15, n), got {shape}")
+        T = shape[0]
+        Zt = self._rows(Z, (T,), _lib.EKF_ROWS, "Z")
+        Xp, Xs = self._rows(trace.Xpred, (T,), 13, "trace.Xpred"), self._rows(smooth.X, (T,), 13, "smooth.X")
+        Pp, Ps = self._rows(trace.Ppred, (T, 12), 12, "trace.Ppred"), self._rows(smooth.P, (T, 12), 12, "smooth.P")
+        used = self._rows(trace.used, (T,), None, "trace.used", torch.int32)
+        return EkfNoiseStats(*(self._give(t) for t in self._noise_stats(Xp, Pp, Xs, Ps, Zt, used, T, floor)))
+
+    def _noise_stats(self, Xp, Pp, Xs, Ps, Zt, used, T, floor, ws=None):
+        """the device tensors of EkfNoiseStats' fields, in order"""
+        torch = _torch_mod()
+        sysm, n, dev = self.system, self.n, self._X.device
+        lib = sysm._sync()
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        if ws is None:
+            ws = sysm.ekf_em_workspace(n, T)
+        Qsum, Rsum, Qn, Rn = (torch.empty((rows, n), **f32) for rows in (12, _lib.EKF_ROWS, 12, _lib.EKF_ROWS))
+        nq, nr, st = torch.empty((n,), **i32), torch.empty((_lib.EKF_ROWS, n), **i32), torch.empty((T, n), **i32)
+        o = _lib.EkfEmOpts()
+        o.mag_ned[:] = self.mag_ned
+        o.floor_rel = floor
+        _lib.check(lib.ac_ekf_em_f32(sysm._handle, C.byref(o), Xp.data_ptr(), Pp.data_ptr(), Xs.data_ptr(), Ps.data_ptr(), Zt.data_ptr(),
+                                     used.data_ptr(), self._Qd.data_ptr(), self._Rd.data_ptr(), n, T, Qsum.data_ptr(), Rsum.data_ptr(),
+                                     nq.data_ptr(), nr.data_ptr(), st.data_ptr(), Qn.data_ptr(), Rn.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     sysm._stream()), "ac_ekf_em_f32")
+        return Qsum, Rsum, nq, nr, Qn, Rn, st
+
+    def fit_noise(self, U, dt, Z, mask=None, iters=10, update=("q", "r"), share=False, floor=1e-4) -> EkfNoiseFit:
+        """EM for the variances over a recorded flight U (T, 7, n), Z (T, 15, n), mask (T, n) or None.  Each of the `iters`
+        iterations starts from the estimate the bank holds now: filter(record=True), smooth(initial=False), noise_stats,
+        set_noise of the rows named in `update`.  share=True: one airframe, many logs: sums and counts are pooled over the
+        instances (a float64 sum) before dividing, so every instance gets the same q, r (the floor is then floor x the mean of the
+        present variances).  On return x, P are what they were, q, r are the fitted ones.  No host synchronisation before
+        the result is handed out.  -> EkfNoiseFit."""
+        torch = _torch_mod()
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 1:
+            raise ValueError(f"ekf fit_noise: iters must be an integer >= 1, got {iters!r}")
+        if isinstance(update, str) or not set(update) <= {"q", "r"}:
+            raise ValueError(f"ekf fit_noise: update names 'q' and / or 'r', got {update!r}")
+        floor = self._floor(floor)
+        dt, T, Zt, Ut, M = self._filter_args(U, dt, Z, mask)
+        X0, P0 = self._X, self._P
+        ws = self.system.ekf_em_workspace(self.n, T)
+        lls, st = [], None
+        for _ in range(int(iters)):
+            self._X, self._P = X0, P0
+            tr = self._filter(Ut, dt, Zt, M, T, True)
+            lls.append(tr[5])
+            sm = self._smooth(None, None, tr[0], tr[1], tr[8], tr[9], tr[10], T, False)
+            st = self._noise_stats(tr[8], tr[9], sm[0], sm[1], Zt, tr[6], T, floor, ws)
+            qn, rn = st[4], st[5]
+            if share:
+                lo = (floor if floor > 0 else 1e-4)
+                pool = lambda s, c, old: torch.where(c.sum(-1, keepdim=True) > 0, torch.maximum(  # noqa: E731
+                    s.double().sum(-1, keepdim=True) / c.sum(-1, keepdim=True).clamp(min=1), lo * old.double().mean(-1, keepdim=True)),
+                    old.double()).float().expand(-1, self.n).contiguous()
+                qn = pool(st[0], st[2].reshape(1, -1).expand(12, -1), self._Qd)
+                rn = pool(st[1], st[3], self._Rd)
+            if "q" in update:
+                self._Qd = qn
+            if "r" in update:
+                self._Rd = rn
+        self._X, self._P = X0, P0
+        lls.append(self._filter(Ut, dt, Zt, M, T, False)[5])
+        self._X, self._P = X0, P0
+        return EkfNoiseFit(*(self._give(t) for t in (self._Qd, self._Rd, torch.stack(lls), st[2], st[3], st[6])))
 
 
 def inertia_about_com(cfg_Ixx, cfg_Iyy, cfg_Izz, cfg_Ixz, mass, com):
@@ -817,6 +979,13 @@ class Aircraft(SixDOF):
         lib = self._sync()
         need = C.c_size_t()
         _lib.check(lib.ac_ekf_workspace_floats(self._handle, int(n), C.byref(need)), "ac_ekf_workspace_floats")
+        return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
+
+    def ekf_em_workspace(self, n: int, T: int):
+        """Device workspace of EKF.noise_stats over n instances and T nodes (ac_ekf_em_workspace_floats)."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_ekf_em_workspace_floats(self._handle, int(n), int(T), C.byref(need)), "ac_ekf_em_workspace_floats")
         return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
 
     def ekf(self, x0, P0, *, q, r, mag_ned=EKF_MAG_NED, ws=None) -> EKF:

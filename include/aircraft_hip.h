@@ -731,6 +731,37 @@ int ac_ekf_smooth_f32(ac_handle* h, const float* X0 /* [13][n] | NULL */, const 
                       float* Xs0, float* Ps0 /* with X0, P0; else NULL */, float* Cg /* [T][12][12][n] | NULL: C_k of link k */,
                       int* status /* [T][n] */, void* stream);
 
+/* ---- EM statistics for the noise variances of the extended Kalman filter (fixed-wing models) -----------------------
+ * The M-step of an EM estimate of the diagonal Q and R from a recorded filter run (ac_ekf_filter_rec_f32: Xpred, Ppred, used) and
+ * its smoothed trace (ac_ekf_smooth_f32: Xs, Ps), per instance over the nodes k = 0 .. T-1.  Qd, Rd must be the variances THE
+ * RECORDS WERE MADE WITH; mag_ned the filter's.
+ *   Process noise, innovations form: with e = x^s_k [-] x-_k, y = (P-_k)^-1 e, W = (P-_k)^-1 (P-_k - P^s_k) (P-_k)^-1 (plain Cholesky
+ *   of P-_k),  t_kj = Q_j + Q_j^2 (y_j^2 - W_jj) = E[w_kj^2 | all data];  Qsum [12][n] = sum_k t_kj over the counted nodes, nq [n] their
+ *   number.  Node 0 counts like any other (its P-_0 contains Q); the initial node is not read.
+ *   Sensor noise, relinearised at the smoothed state: for every node and row i whose `used` bit is set and whose z is finite,
+ *   Rsum_i += (z_i - h_i(x^s_k))^2 + h_i P^s_k h_i',  nr_i += 1;  Rsum, nr [15][n]  (h, H: the filter's, evaluated at x^s_k).
+ * status [T][n] per node: 0; value 2: an operand of the node (x-_k, P-_k, x^s_k, P^s_k, Qd) is not finite, the node adds nothing;
+ * else value 1: a pivot of the Cholesky was <= 0 or not finite, the node adds nothing to Q and its R terms count.  A link the
+ * smoother reported does not exclude a node.
+ * Qn [12][n], Rn [15][n] (each may be NULL): the new variances max(sum / count, floor_rel * input); the input bit for bit where
+ * the count is 0.  floor_rel must be finite and >= 0; 0 means 1e-4.
+ * Two launches: k_ekf_em_nodes over (groups of 16 instances) x (chunks of 32 consecutive nodes), per-node terms in float32,
+ * float64 sums in node order into the workspace; k_ekf_em_reduce sums the chunks in chunk order and rounds to float32 once.  No
+ * atomics, every sum in a fixed order: an instance's bits depend neither on n nor on its place in the batch (they do depend
+ * on the chunk length 32, which is part of the contract).
+ * ws / ws_floats: caller-owned device scratch of at least ac_ekf_em_workspace_floats(h, n, T) floats, else AC_ERR_WORKSPACE.
+ * AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG for n < 0, T < 0, a NULL required pointer, a floor_rel that is not finite
+ * and >= 0, or an output that overlaps an input; n == 0 is AC_OK and launches nothing; T == 0 writes zero sums and counts and
+ * Qn, Rn = Qd, Rd.  Asynchronous, no allocation, no synchronisation, hipGraph-capturable. */
+typedef struct ac_ekf_em_opts { float mag_ned[3]; float floor_rel; } ac_ekf_em_opts;
+int ac_ekf_em_workspace_floats(const ac_handle* h, long n, long T, size_t* floats);
+int ac_ekf_em_f32(ac_handle* h, const ac_ekf_em_opts* o, const float* Xpred /* [T][13][n] */, const float* Ppred /* [T][12][12][n] */,
+                  const float* Xs /* [T][13][n] */, const float* Ps /* [T][12][12][n] */, const float* Z /* [T][15][n] */,
+                  const int* used /* [T][n] */, const float* Qd /* [12][n] */, const float* Rd /* [15][n] */, long n, long T,
+                  float* Qsum /* [12][n] */, float* Rsum /* [15][n] */, int* nq /* [n] */, int* nr /* [15][n] */,
+                  int* status /* [T][n] */, float* Qn /* [12][n] | NULL */, float* Rn /* [15][n] | NULL */, float* ws,
+                  size_t ws_floats, void* stream);
+
 /* ---- flight modes: eigenvalues of the trim linearisation ---------------------------------------------------------
  * ac_eig_f32 (any handle): the eigenvalues of n real m x m matrices M [m][m][n], 1 <= m <= 13, float32 in and out with float64
  * arithmetic between (the eigenvalues carry the rounding of the output, 6e-8, not the matrix's conditioning), one instance per
