@@ -87,6 +87,11 @@ class EkfOpts(C.Structure):
     _fields_ = [("mag_ned", C.c_float * 3), ("predict", C.c_int)]
 
 
+class UkfOpts(C.Structure):
+    """struct ac_ukf_opts (include/aircraft_hip.h)."""
+    _fields_ = [("mag_ned", C.c_float * 3), ("predict", C.c_int), ("kappa", C.c_float)]
+
+
 class EkfEmOpts(C.Structure):
     """struct ac_ekf_em_opts (include/aircraft_hip.h)."""
     _fields_ = [("mag_ned", C.c_float * 3), ("floor_rel", C.c_float)]
@@ -225,6 +230,13 @@ PROTOTYPES = {
     "ac_ekf_filter_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_ekf_filter_rec_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
+                                        _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_ukf_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_ukf_step_f32": (C.c_int, [_VP, C.POINTER(UkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, _VP, _VP, _VP, _VP,
+                                  _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_ukf_filter_f32": (C.c_int, [_VP, C.POINTER(UkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
+                                    _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_ukf_filter_rec_f32": (C.c_int, [_VP, C.POINTER(UkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
                                         _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_ekf_smooth_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ac_ekf_em_workspace_floats": (C.c_int, [_VP, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),

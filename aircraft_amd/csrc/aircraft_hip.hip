@@ -31,6 +31,7 @@
 #include "ac_ekf.hpp"
 #include "ac_rts.hpp"
 #include "ac_em.hpp"
+#include "ac_ukf.hpp"
 #include "ac_wgrad.hpp"
 #include "ac_cgrad.hpp"
 #include "ac_agrad.hpp"
@@ -2401,6 +2402,138 @@ int ac_ekf_filter_rec_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, co
                           float* Ppreds, float* Abars, float* ws, size_t ws_floats, void* stream) {
     AC_ENTER(h);
     return ekf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, Xpreds, Ppreds,
+                           Abars, ws, ws_floats, stream);
+}
+
+// ---- unscented Kalman filter beside the EKF bank (ac_ukf.hpp, ukf_inst.hip) ---------------------------------------------------------
+namespace {
+constexpr size_t kUkfWsPad = 9 * 64;  // the nine workspace buffers each start on a 256-byte boundary
+size_t ukf_ws_floats(long n) { return (size_t)n * (size_t)(kUkfInstFloats + kEkfChainFloats) + kUkfWsPad; }
+
+// the workspace: points [13][25 n] | U [7][25 n] | images [13][25 n] | L [144][n] | flag [n] | the filter's two (x, P) pairs
+struct UkfWs {
+    float *Xw, *Uw, *Fw, *Lw;
+    int* flag;
+    float* buf[4];
+    UkfWs(float* ws, size_t N) {
+        Xw = align256(ws);
+        Uw = align256(Xw + 13 * kUkfPts * N);
+        Fw = align256(Uw + 7 * kUkfPts * N);
+        Lw = align256(Fw + 13 * kUkfPts * N);
+        flag = (int*)align256(Lw + 144 * N);
+        buf[0] = align256((float*)flag + N);
+        buf[1] = align256(buf[0] + 13 * N);
+        buf[2] = align256(buf[1] + 144 * N);
+        buf[3] = align256(buf[2] + 13 * N);  // ends at most ws + 1284 N + 9 * 63 floats
+    }
+};
+
+// one step: k_ukf_sigma, the handle's forward step over the 25 n units, k_ukf_update.  ll_in: added to this step's ll (or NULL).
+int ukf_step_impl(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                  const int* mask, const float* Qd, const float* Rd, long n, const float* ll_in, float* Xo, float* Po, float* nu,
+                  float* S, float* nis, float* ll, int* used, int* status, float* Xpred, float* Ppred, float* Abar, float* ws,
+                  void* stream) {
+    const UkfWs w(ws, (size_t)n);
+    const UkfWeights wt = ukf_weights(o->kappa);
+    int grid = 0, lds = 0;
+    if (o->predict) {
+        const UkfSigIo sio{X, P, U, w.Xw, w.Uw, w.Lw, w.flag, n};
+        AC_HIP(ukf_launch_sigma(wt, sio, (hipStream_t)stream, &grid, &lds));
+        note_launch(h, "k_ukf_sigma", grid, kUkfGroups * kEkfLanes, lds);
+        const int rc = step_impl(h, w.Xw, w.Uw, dt, nullptr, kUkfPts * n, kUkfPts * n, w.Fw, stream);
+        if (rc != AC_OK) return rc;
+    }
+    const UkfIo io{X, P, w.Fw, w.Lw, w.flag, Z, Qd, Rd, mask, ll_in, Xo, Po, nu, S, nis, ll, used, status, Xpred, Ppred, Abar, n};
+    AC_HIP(ukf_launch_update(*o, wt, h->dp.p.epsilon, io, (hipStream_t)stream, &grid, &lds));
+    note_launch(h, "k_ukf_update", grid, kUkfGroups * kEkfLanes, lds);
+    return AC_OK;
+}
+
+// the checks the entry points share; *go = false: nothing to do (AC_OK)
+int ukf_check(ac_handle* h, const ac_ukf_opts* o, float dt, long n, long T, const float* ws, size_t ws_floats, bool* go) {
+    *go = false;
+    if (!h || !o || n < 0 || T < 0) return AC_ERR_BAD_ARG;
+    if (o->predict && (!(dt > 0.f) || !(dt <= 3.0e38f))) return fail(AC_ERR_BAD_ARG, "ukf: dt must be finite and > 0");
+    if (!(o->kappa >= 0.f) || !(o->kappa <= 3.0e38f)) return fail(AC_ERR_BAD_ARG, "ukf: kappa must be finite and >= 0");
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    if (n == 0 || T == 0) return AC_OK;
+    if (n > 0x7fffffffL / (kUkfPts * 13)) return fail(AC_ERR_BAD_ARG, "ukf: 25 n exceeds the step launch");
+    const int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    if (!ws || ws_floats < ukf_ws_floats(n)) return fail(AC_ERR_WORKSPACE, "ukf workspace too small: see ac_ukf_workspace_floats");
+    *go = true;
+    return AC_OK;
+}
+
+// T steps as a host loop over the step (ekf_filter_impl's)
+int ukf_filter_impl(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                    const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
+                    float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds, float* Ppreds, float* Abars,
+                    float* ws, size_t ws_floats, void* stream) {
+    bool go = false;
+    int rc = ukf_check(h, o, dt, n, T, ws, ws_floats, &go);
+    if (rc != AC_OK || !go) return rc;
+    if (!X || !P || !Z || !Rd || !Xo || !Po || !ll) return fail(AC_ERR_BAD_ARG, "ukf filter: a required pointer is NULL");
+    if (o->predict && (!U || !Qd)) return fail(AC_ERR_BAD_ARG, "ukf filter: U and Qd are required when predict is set");
+    const size_t N = (size_t)n;
+    const UkfWs w(ws, N);
+    const float *xin = X, *pin = P;
+    for (long t = 0; t < T; ++t) {
+        const bool last = t == T - 1;
+        float* const xo = last ? Xo : w.buf[2 * (t & 1)];
+        float* const po = last ? Po : w.buf[2 * (t & 1) + 1];
+        const size_t k = (size_t)t;
+        rc = ukf_step_impl(h, o, xin, pin, U ? U + k * 7 * N : nullptr, dt, Z + k * 15 * N, mask ? mask + k * N : nullptr, Qd, Rd, n,
+                           t ? ll : nullptr, xo, po, nu ? nu + k * 15 * N : nullptr, S ? S + k * 15 * N : nullptr,
+                           nis ? nis + k * N : nullptr, ll, used ? used + k * N : nullptr, status ? status + k * N : nullptr,
+                           Xpreds ? Xpreds + k * 13 * N : nullptr, Ppreds ? Ppreds + k * 144 * N : nullptr,
+                           Abars ? Abars + k * 144 * N : nullptr, ws, stream);
+        if (rc != AC_OK) return rc;
+        if (Xs) AC_HIP(hipMemcpyAsync(Xs + k * 13 * N, xo, 13 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        if (Ps) AC_HIP(hipMemcpyAsync(Ps + k * 144 * N, po, 144 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        xin = xo;
+        pin = po;
+    }
+    return AC_OK;
+}
+}  // namespace
+
+int ac_ukf_workspace_floats(const ac_handle* h, long n, size_t* floats) {
+    if (!h || !floats || n < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    *floats = ukf_ws_floats(n);
+    return AC_OK;
+}
+
+int ac_ukf_step_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                    const int* mask, const float* Qd, const float* Rd, long n, float* Xo, float* Po, float* nu, float* S, float* nis,
+                    float* ll, int* used, int* status, float* Xpred, float* Ppred, float* Abar, float* ws, size_t ws_floats,
+                    void* stream) {
+    AC_ENTER(h);
+    bool go = false;
+    const int rc = ukf_check(h, o, dt, n, 1, ws, ws_floats, &go);
+    if (rc != AC_OK || !go) return rc;
+    if (!X || !P || !Z || !Rd || !Xo || !Po || !nu || !S || !nis || !ll || !used || !status)
+        return fail(AC_ERR_BAD_ARG, "ukf step: a required pointer is NULL");
+    if (o->predict && (!U || !Qd)) return fail(AC_ERR_BAD_ARG, "ukf step: U and Qd are required when predict is set");
+    return ukf_step_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, nullptr, Xo, Po, nu, S, nis, ll, used, status, Xpred, Ppred, Abar, ws,
+                         stream);
+}
+
+int ac_ukf_filter_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
+                      const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
+                      float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    return ukf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, nullptr, nullptr,
+                           nullptr, ws, ws_floats, stream);
+}
+
+int ac_ukf_filter_rec_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt,
+                          const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po,
+                          float* ll, float* Xs, float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds,
+                          float* Ppreds, float* Abars, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    return ukf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, Xpreds, Ppreds,
                            Abars, ws, ws_floats, stream);
 }
 

@@ -204,6 +204,8 @@ class EKF:
     fixed-interval (RTS) estimate of every step given the whole run, and noise_stats(trace, smooth, Z) /
     fit_noise(U, dt, Z) estimate the variances q, r from it by EM."""
 
+    _STEP, _FILTER, _FILTER_REC = "ac_ekf_step_f32", "ac_ekf_filter_f32", "ac_ekf_filter_rec_f32"  # the entry points of the bank
+
     def __init__(self, system, X, P, Qd, Rd, mag_ned, ws, from_np, vec):
         self.system, self._X, self._P, self._Qd, self._Rd, self._ws = system, X, P, Qd, Rd, ws
         self.mag_ned = tuple(float(v) for v in mag_ned)
@@ -302,10 +304,10 @@ class EKF:
         used, st = torch.empty((n,), **i32), torch.empty((n,), **i32)
         o = self._opts(predict)
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        _lib.check(lib.ac_ekf_step_f32(sysm._handle, C.byref(o), self._X.data_ptr(), self._P.data_ptr(), ptr(U), C.c_float(dt),
-                                       Z.data_ptr(), ptr(M), self._Qd.data_ptr(), self._Rd.data_ptr(), n, Xo.data_ptr(), Po.data_ptr(),
-                                       nu.data_ptr(), S.data_ptr(), nis.data_ptr(), ll.data_ptr(), used.data_ptr(), st.data_ptr(),
-                                       None, None, None, self._ws.data_ptr(), self._ws.numel(), sysm._stream()), "ac_ekf_step_f32")
+        _lib.check(getattr(lib, self._STEP)(sysm._handle, C.byref(o), self._X.data_ptr(), self._P.data_ptr(), ptr(U), C.c_float(dt),
+                                            Z.data_ptr(), ptr(M), self._Qd.data_ptr(), self._Rd.data_ptr(), n, Xo.data_ptr(), Po.data_ptr(),
+                                            nu.data_ptr(), S.data_ptr(), nis.data_ptr(), ll.data_ptr(), used.data_ptr(), st.data_ptr(),
+                                            None, None, None, self._ws.data_ptr(), self._ws.numel(), sysm._stream()), self._STEP)
         self._X, self._P = Xo, Po
         return EkfTrace(*(self._give(t) for t in (Xo, Po, nu, S, nis, ll, used, st)))
 
@@ -353,9 +355,9 @@ class EKF:
         rec = ()
         if record:
             rec = (torch.empty((T, 13, n), **f32), torch.empty((T, 12, 12, n), **f32), torch.empty((T, 12, 12, n), **f32), self._X, self._P)
-            _lib.check(lib.ac_ekf_filter_rec_f32(*head, *(t.data_ptr() for t in rec[:3]), *tail), "ac_ekf_filter_rec_f32")
+            _lib.check(getattr(lib, self._FILTER_REC)(*head, *(t.data_ptr() for t in rec[:3]), *tail), self._FILTER_REC)
         else:
-            _lib.check(lib.ac_ekf_filter_f32(*head, *tail), "ac_ekf_filter_f32")
+            _lib.check(getattr(lib, self._FILTER)(*head, *tail), self._FILTER)
         if T:
             self._X, self._P = Xo, Po
         return (Xs, Ps, nu, S, nis, ll, used, st) + rec
@@ -485,6 +487,33 @@ class EKF:
         lls.append(self._filter(Ut, dt, Zt, M, T, False)[5])
         self._X, self._P = X0, P0
         return EkfNoiseFit(*(self._give(t) for t in (self._Qd, self._Rd, torch.stack(lls), st[2], st[3], st[6])))
+
+
+class UKF(EKF):
+    """A bank of n unscented Kalman filters (Aircraft.ukf): EKF's interface over sigma points in place of
+    Jacobians (include/aircraft_hip.h, ac_ukf_step_f32).  step / update / filter return an EkfTrace whose status may also carry
+    bit 3 (value 4): the covariance or its prediction had no Cholesky factor.  filter(..., record=True) records the statistical
+    linearisation as Abar, so smooth(trace) is the unscented RTS smoother.  noise_stats / fit_noise are not defined here: the
+    EM statistic's innovations form assumes P- = Abar P Abar' + Q exactly, which the sigma-point P- does not satisfy."""
+
+    _STEP, _FILTER, _FILTER_REC = "ac_ukf_step_f32", "ac_ukf_filter_f32", "ac_ukf_filter_rec_f32"
+
+    def __init__(self, *args, kappa=0.0):
+        super().__init__(*args)
+        self.kappa = float(kappa)
+
+    def _opts(self, predict):
+        o = _lib.UkfOpts()
+        o.mag_ned[:] = self.mag_ned
+        o.predict = int(predict)
+        o.kappa = self.kappa
+        return o
+
+    def noise_stats(self, *args, **kwargs):
+        raise NotImplementedError("ukf: the EM noise statistics assume the EKF's P- = Abar P Abar' + Q; use Aircraft.ekf for them")
+
+    def fit_noise(self, *args, **kwargs):
+        raise NotImplementedError("ukf: the EM noise fit assumes the EKF's P- = Abar P Abar' + Q; use Aircraft.ekf for it")
 
 
 def inertia_about_com(cfg_Ixx, cfg_Iyy, cfg_Izz, cfg_Ixz, mass, com):
@@ -988,7 +1017,21 @@ class Aircraft(SixDOF):
         _lib.check(lib.ac_ekf_em_workspace_floats(self._handle, int(n), int(T), C.byref(need)), "ac_ekf_em_workspace_floats")
         return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
 
-    def ekf(self, x0, P0, *, q, r, mag_ned=EKF_MAG_NED, ws=None) -> EKF:
+    def ukf_workspace(self, n: int):
+        """Device workspace of a bank of n unscented filters (ac_ukf_workspace_floats); allocate it before capturing a graph."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_ukf_workspace_floats(self._handle, int(n), C.byref(need)), "ac_ukf_workspace_floats")
+        return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
+
+    def ukf(self, x0, P0, *, q, r, kappa=0.0, mag_ned=EKF_MAG_NED, ws=None) -> UKF:
+        """A bank of n unscented Kalman filters: Aircraft.ekf's arguments and checks, plus kappa >= 0 (the centre point's weight
+        is kappa / (12 + kappa); 0, the default, leaves it out of the means).  ws: ukf_workspace(n)."""
+        if isinstance(kappa, bool) or np.ndim(kappa) != 0 or not np.isfinite(float(kappa)) or float(kappa) < 0:
+            raise ValueError(f"ukf: kappa must be a finite scalar >= 0, got {kappa!r}")
+        return self.ekf(x0, P0, q=q, r=r, mag_ned=mag_ned, ws=ws, _bank=lambda *a: UKF(*a, kappa=float(kappa)))
+
+    def ekf(self, x0, P0, *, q, r, mag_ned=EKF_MAG_NED, ws=None, _bank=None) -> EKF:
         """A bank of n extended Kalman filters started at x0 (13, n) with covariance P0 (12, 12, n) in the error coordinates
         (dp NED, dv NED, dtheta body-frame rotation vector, dw).  q: process-noise variances per step, (12,) for every
         instance or (12, n); r: measurement variances > 0 of the 15 rows, (15,) or (15, n); mag_ned: the magnetic field in NED
@@ -1031,8 +1074,8 @@ class Aircraft(SixDOF):
         Qd = to(q).reshape(12, -1).expand(12, n).contiguous()
         Rd = to(r).reshape(_lib.EKF_ROWS, -1).expand(_lib.EKF_ROWS, n).contiguous()
         if ws is None:
-            ws = self.ekf_workspace(n)
-        return EKF(self, X.clone(), P, Qd, Rd, mg, ws, npx, vec)
+            ws = self.ekf_workspace(n) if _bank is None else self.ukf_workspace(n)
+        return (_bank or EKF)(self, X.clone(), P, Qd, Rd, mg, ws, npx, vec)
 
     def measure(self, x, mag_ned=EKF_MAG_NED):
         """z (15, n) = h(x): what the filter's sensors read at the state x (13, n) without noise: GPS position, GPS velocity

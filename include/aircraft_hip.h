@@ -706,6 +706,55 @@ int ac_ekf_filter_rec_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, co
                           float* Xpreds, float* Ppreds, float* Abars /* per step, each may be NULL */, float* ws, size_t ws_floats,
                           void* stream);
 
+/* ---- unscented Kalman filter beside the EKF bank (fixed-wing models) ------------------------------------------------
+ * The EKF's error state, chart, measurement rows h(x) [15], diagonal Qd, Rd and mask / NaN rule, with sigma points in place of
+ * Jacobians: the second-order terms of f and h that one linearisation per step leaves out are carried.  kappa >= 0 (default 0):
+ * gamma = sqrt(12 + kappa), weights w0 = kappa / (12 + kappa) for the centre and 1 / (2 (12 + kappa)) for the 24 other points.
+ * One step, per instance:
+ *   1. k_ukf_sigma: L L' = P (plain Cholesky), the points x and x [+] (+-gamma L.j) and the replicated U into the workspace;
+ *   2. the handle's own ac_step_f32 launch over the 25 n units (every model and engine);
+ *   3. k_ukf_update: e_j = F(chi_j) [-] F(chi_0), dbar = sum w_j e_j, x- = F(chi_0) [+] dbar, P- = sum w_j (e_j - dbar)(e_j - dbar)'
+ *      + diag(Qd); L- L-' = P-, z_j = h(x- [+] (+-gamma L-.j)), zbar = sum w_j z_j, Pzz = sum w_j (z_j - zbar)(z_j - zbar)' + diag(Rd),
+ *      Pxz = L- Y' with Y.j = (z_+j - z_-j) / (2 gamma); a Cholesky of Pzz in row order over the USED rows (an unused row is a
+ *      unit row), L_S; w = L_S^-1 (z - zbar), Yx = Pxz L_S^-', d = Yx w, P = P- - Yx Yx', x+ = x- [+] d (x- itself, bit for bit,
+ *      when no row was applied).
+ * Outputs have ac_ekf_step_f32's shapes and meaning: S_i = (L_S)_ii^2, the innovation variance of row i given the rows before
+ * it; nu_i = (L_S)_ii w_i; nis = sum w_i^2; ll = -1/2 sum (log 2 pi S_i + w_i^2); used; unused rows give 0.  Po, Ppred are
+ * symmetric bit for bit.  Abar (optional) = D L^-1 with D.j = (e_+j - e_-j) / (2 gamma): the statistical linearisation
+ * Cov(d+, d) P^-1, with which ac_ekf_smooth_f32 on these records is the unscented RTS smoother (its gain P Abar' (P-)^-1 is
+ * the sigma-point cross covariance times (P-)^-1).
+ * status [n]: 0, or bit 1 (value 1): a used row's pivot was <= 0 or not finite, the row is skipped as if unused; bit 2
+ * (value 2): the prediction is not finite (ac_ekf_step_f32's rule); bit 3 (value 4): a pivot of the factor of P or of P- was
+ * <= 0 or not finite.  For P: the instance's 25 units are all x^, Xo = X and Po = P come back unchanged (Xpred = X, Ppred = P,
+ * Abar = I), nu = S = nis = ll = used = 0.  For P-: Xo, Po are the prediction and no row is applied.
+ * predict == 0: the measurement update alone at (X, P) (Abar = I; U, dt, Qd ignored; neither k_ukf_sigma nor a step launch).
+ * ws / ws_floats: caller-owned device scratch of at least ac_ukf_workspace_floats floats, else AC_ERR_WORKSPACE.  After a
+ * predicting step it holds, each on a 256-byte boundary and in this order: the sigma points [13][25 n] (unit j n + i is point j
+ * of instance i: 0 the centre, 1 + j and 13 + j the points +-gamma L.j; position rows RELATIVE to the instance's p^), the
+ * replicated U [7][25 n], their images [13][25 n] (positions still relative), L [12][12][n], the flag of P's factor [n] (int).
+ * ac_ukf_filter_f32, ac_ukf_filter_rec_f32: ac_ekf_filter_f32's and ac_ekf_filter_rec_f32's host loop over the step, bit-equal
+ * to T step calls.  AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG for n < 0, T < 0, a NULL required pointer, (predict
+ * set) a dt that is not finite and > 0, or a kappa that is not finite and >= 0; n == 0 or T == 0 is AC_OK.  Asynchronous, no
+ * allocation, no synchronisation, hipGraph-capturable.  No atomics: an instance's bits depend neither on n nor on its place. */
+typedef struct ac_ukf_opts { float mag_ned[3]; int predict; float kappa; } ac_ukf_opts;
+int ac_ukf_workspace_floats(const ac_handle* h, long n, size_t* floats);
+int ac_ukf_step_f32(ac_handle* h, const ac_ukf_opts* o, const float* X /* [13][n] */, const float* P /* [12][12][n] */,
+                    const float* U /* [7][n] */, float dt, const float* Z /* [15][n] */, const int* mask /* [n] bits 0-14 | NULL */,
+                    const float* Qd /* [12][n] */, const float* Rd /* [15][n] */, long n, float* Xo, float* Po,
+                    float* nu /* [15][n] */, float* S /* [15][n] */, float* nis, float* ll /* [n] */, int* used /* [n] */,
+                    int* status /* [n] */, float* Xpred, float* Ppred, float* Abar /* optional, may be NULL */, float* ws,
+                    size_t ws_floats, void* stream);
+int ac_ukf_filter_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U /* [T][7][n] */, float dt,
+                      const float* Z /* [T][15][n] */, const int* mask /* [T][n] | NULL */, const float* Qd, const float* Rd,
+                      long n, long T, float* Xo, float* Po, float* ll /* [n] */, float* Xs, float* Ps, float* nu, float* S,
+                      float* nis, int* used, int* status /* per step, each may be NULL */, float* ws, size_t ws_floats,
+                      void* stream);
+int ac_ukf_filter_rec_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt,
+                          const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po,
+                          float* ll, float* Xs, float* Ps, float* nu, float* S, float* nis, int* used, int* status,
+                          float* Xpreds, float* Ppreds, float* Abars /* per step, each may be NULL */, float* ws, size_t ws_floats,
+                          void* stream);
+
 /* ---- RTS smoother over the trace of the extended Kalman filter (fixed-wing models) --------------------------------
  * The fixed-interval Rauch-Tung-Striebel estimate of every node of a recorded filter run, given the whole run: one launch
  * (k_ekf_smooth) sweeps backward in time, one instance per 16-lane group.  Nodes k = 0 .. T-1 are the filter's steps: Xf, Pf
