@@ -26,6 +26,9 @@ TRIM_STATUS = {0: "converged", 1: "max_iter", 2: "bound", 3: "non_finite"}  # ac
 LQR_STATUS = {0: "converged", 1: "max_iter", 2: "breakdown", 3: "non_finite"}  # ac_lqr_f32 status per instance
 EKF_ROWS = 15                                         # ac_ekf_*: GPS p, GPS v, gyro, air data, magnetometer (3 rows each)
 EKF_REJECTED, EKF_NONFINITE = 1, 2                    # ac_ekf_step_f32 status bits per instance
+LQG_ESTIMATORS = {"ekf": 0, "ukf": 1}                 # ac_lqg_opts.estimator (AC_EST_*)
+LQG_FEEDBACK = {"estimate": 0, "truth": 1}            # ac_lqg_opts.feedback (AC_FB_*)
+LQG_GROUPS = 5                                        # ac_sense_opts: GPS p, GPS v, gyro, air data, magnetometer
 RTS_NOT_PD, RTS_NONFINITE = 1, 2                      # ac_ekf_smooth_f32 status bits per link and instance
 EM_NOT_PD, EM_NONFINITE = 1, 2                        # ac_ekf_em_f32 status values per node and instance
 EM_CHUNK = 32                                         # ac_ekf_em_f32: nodes per float64 partial sum (kEmChunk)
@@ -90,6 +93,17 @@ class EkfOpts(C.Structure):
 class UkfOpts(C.Structure):
     """struct ac_ukf_opts (include/aircraft_hip.h)."""
     _fields_ = [("mag_ned", C.c_float * 3), ("predict", C.c_int), ("kappa", C.c_float)]
+
+
+class SenseOpts(C.Structure):
+    """struct ac_sense_opts (include/aircraft_hip.h)."""
+    _fields_ = [("mag_ned", C.c_float * 3), ("seed_lo", C.c_uint), ("seed_hi", C.c_uint), ("instance_offset", C.c_long),
+                ("period", C.c_int * 5), ("phase", C.c_int * 5), ("dropout", C.c_float * 5)]
+
+
+class LqgOpts(C.Structure):
+    """struct ac_lqg_opts (include/aircraft_hip.h)."""
+    _fields_ = [("estimator", C.c_int), ("feedback", C.c_int), ("kappa", C.c_float), ("step0", C.c_int)]
 
 
 class EkfEmOpts(C.Structure):
@@ -238,6 +252,13 @@ PROTOTYPES = {
                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "ac_ukf_filter_rec_f32": (C.c_int, [_VP, C.POINTER(UkfOpts), _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP,
                                         _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_sense_f32": (C.c_int, [_VP, C.POINTER(SenseOpts), C.c_int, _VP, _VP, _VP, C.c_long, _VP, _VP, _VP]),
+    "ac_disturb_f32": (C.c_int, [_VP, C.POINTER(SenseOpts), C.c_int, _VP, _VP, _VP, C.c_long, _VP, _VP]),
+    "ac_policy_f32": (C.c_int, [_VP, C.POINTER(IlqrCost), _VP, _VP, _VP, _VP, C.c_long, _VP, _VP]),
+    "ac_estimate_score_f32": (C.c_int, [_VP, _VP, _VP, _VP, C.c_long, _VP, _VP, _VP, _VP]),
+    "ac_lqg_workspace_floats": (C.c_int, [_VP, C.c_int, C.c_long, C.POINTER(C.c_size_t)]),
+    "ac_lqg_rollout_f32": (C.c_int, [_VP, C.POINTER(LqgOpts), C.POINTER(SenseOpts), C.POINTER(IlqrCost)] + [_VP] * 10
+                           + [C.c_float, C.c_long, C.c_long] + [_VP] * 15 + [C.c_size_t, _VP]),
     "ac_ekf_smooth_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ac_ekf_em_workspace_floats": (C.c_int, [_VP, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_ekf_em_f32": (C.c_int, [_VP, C.POINTER(EkfEmOpts), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP,

@@ -32,6 +32,7 @@
 #include "ac_rts.hpp"
 #include "ac_em.hpp"
 #include "ac_ukf.hpp"
+#include "ac_lqg.hpp"
 #include "ac_wgrad.hpp"
 #include "ac_cgrad.hpp"
 #include "ac_agrad.hpp"
@@ -2535,6 +2536,200 @@ int ac_ukf_filter_rec_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, co
     AC_ENTER(h);
     return ukf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, Xpreds, Ppreds,
                            Abars, ws, ws_floats, stream);
+}
+
+// ---- the loop closed through the estimator (ac_lqg.hpp, lqg_inst.hip) ---------------------------------------------------------------
+namespace {
+constexpr long kLqgLoopFloats = 2 * 13 + 2 * 13 + 2 * 144 + 7 + 15 + 1;  // truth x2 | x^ x2 | P x2 | u | z | mask per instance
+constexpr size_t kLqgWsPad = 10 * 64;  // the loop's nine buffers and the estimator's workspace each start on a 256-byte boundary
+size_t lqg_est_floats(int estimator, long n) { return estimator == AC_EST_UKF ? ukf_ws_floats(n) : ekf_ws_floats(n); }
+size_t lqg_ws_floats(int estimator, long n) { return lqg_est_floats(estimator, n) + (size_t)n * (size_t)kLqgLoopFloats + kLqgWsPad; }
+
+bool lqg_sense_opts_ok(const ac_sense_opts* o) {
+    for (int j = 0; j < kLqgGroups; ++j)
+        if (o->period[j] < 1 || !(o->dropout[j] >= 0.f) || !(o->dropout[j] < 1.f)) return false;
+    return true;
+}
+bool lqg_limits_ok(const ac_ilqr_cost* c) {
+    for (int i = 0; i < 7; ++i)
+        if (!(c->u_min[i] <= c->u_max[i])) return false;  // (false for a NaN bound)
+    return true;
+}
+LqgLimits lqg_limits(const ac_ilqr_cost* c) {
+    LqgLimits l;
+    memcpy(l.u_min, c->u_min, sizeof(l.u_min));
+    memcpy(l.u_max, c->u_max, sizeof(l.u_max));
+    return l;
+}
+// the checks every entry point here shares; *go = false: nothing to do (AC_OK)
+int lqg_check(ac_handle* h, long n, bool* go) {
+    *go = false;
+    if (!h) return AC_ERR_BAD_ARG;
+    if (n < 0) return fail(AC_ERR_BAD_ARG, "lqg: n must be >= 0");
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    *go = n > 0;
+    return AC_OK;
+}
+}  // namespace
+
+int ac_sense_f32(ac_handle* h, const ac_sense_opts* o, int step, const int* step_dev, const float* X, const float* sigma_r, long n,
+                 float* Z, int* mask, void* stream) {
+    AC_ENTER(h);
+    bool go = false;
+    const int rc = lqg_check(h, n, &go);
+    if (rc != AC_OK) return rc;
+    if (!o || !lqg_sense_opts_ok(o)) return fail(AC_ERR_BAD_ARG, "sense: period must be >= 1 and dropout in [0, 1)");
+    if (!go) return AC_OK;
+    if (!X || !sigma_r || !Z || !mask) return fail(AC_ERR_BAD_ARG, "sense: a required pointer is NULL");
+    int grid = 0;
+    AC_HIP(lqg_launch_sense(*o, h->dp.p.epsilon, step, step_dev, X, sigma_r, n, Z, mask, (hipStream_t)stream, &grid));
+    note_launch(h, "k_lqg_sense", grid, kLqgBlock, 0);
+    return AC_OK;
+}
+
+int ac_disturb_f32(ac_handle* h, const ac_sense_opts* o, int step, const int* step_dev, const float* X, const float* sigma_q, long n,
+                   float* Xo, void* stream) {
+    AC_ENTER(h);
+    bool go = false;
+    const int rc = lqg_check(h, n, &go);
+    if (rc != AC_OK) return rc;
+    if (!o) return fail(AC_ERR_BAD_ARG, "disturb: the options are NULL");
+    if (!go) return AC_OK;
+    if (!X || !sigma_q || !Xo) return fail(AC_ERR_BAD_ARG, "disturb: a required pointer is NULL");
+    int grid = 0;
+    AC_HIP(lqg_launch_disturb(*o, step, step_dev, X, sigma_q, n, Xo, (hipStream_t)stream, &grid));
+    note_launch(h, "k_lqg_sense", grid, kLqgBlock, 0);
+    return AC_OK;
+}
+
+int ac_policy_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* Fb, const float* Xnom, const float* Unom, const float* Kx,
+                  long n, float* U, void* stream) {
+    AC_ENTER(h);
+    bool go = false;
+    const int rc = lqg_check(h, n, &go);
+    if (rc != AC_OK) return rc;
+    if (!limits || !lqg_limits_ok(limits)) return fail(AC_ERR_BAD_ARG, "policy: limits with u_min <= u_max are required");
+    if (!go) return AC_OK;
+    if (!Fb || !Xnom || !Unom || !Kx || !U) return fail(AC_ERR_BAD_ARG, "policy: a required pointer is NULL");
+    int grid = 0;
+    AC_HIP(lqg_launch_control(lqg_limits(limits), Fb, Xnom, Unom, Kx, n, U, (hipStream_t)stream, &grid));
+    note_launch(h, "k_lqg_control", grid, kLqgBlock, 0);
+    return AC_OK;
+}
+
+int ac_estimate_score_f32(ac_handle* h, const float* X, const float* Xhat, const float* P, long n, float* e, float* nees, int* status,
+                          void* stream) {
+    AC_ENTER(h);
+    bool go = false;
+    const int rc = lqg_check(h, n, &go);
+    if (rc != AC_OK || !go) return rc;
+    if (!X || !Xhat || !P || !e || !nees || !status) return fail(AC_ERR_BAD_ARG, "estimate score: a required pointer is NULL");
+    int grid = 0;
+    AC_HIP(lqg_launch_score(X, Xhat, P, n, e, nees, status, (hipStream_t)stream, &grid));
+    note_launch(h, "k_lqg_score", grid, kLqgBlock, 0);
+    return AC_OK;
+}
+
+int ac_lqg_workspace_floats(const ac_handle* h, int estimator, long n, size_t* floats) {
+    if (!h || !floats || n < 0 || (estimator != AC_EST_EKF && estimator != AC_EST_UKF)) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kEkfFixedWing);
+    *floats = lqg_ws_floats(estimator, n);
+    return AC_OK;
+}
+
+int ac_lqg_rollout_f32(ac_handle* h, const ac_lqg_opts* o, const ac_sense_opts* s, const ac_ilqr_cost* limits, const float* X0,
+                       const float* Xhat0, const float* P0, const float* Xnom, const float* Unom, const float* Kx, const float* Qd,
+                       const float* Rd, const float* sigma_q, const float* sigma_r, float dt, long n, long T, float* Xo, float* Po,
+                       float* Xtrue, float* Xhat, float* U, float* Ps, float* Z, int* mask, float* nis, float* nees, int* used,
+                       int* est_status, int* score_status, float* err, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h) return AC_ERR_BAD_ARG;
+    if (!o || !s || !limits || n < 0 || T < 0) return fail(AC_ERR_BAD_ARG, "lqg: NULL options or limits, n < 0 or T < 0");
+    if ((long long)o->step0 + (long long)T > 0x7fffffffLL) return fail(AC_ERR_BAD_ARG, "lqg: step0 + T exceeds the 32-bit step index");
+    if (o->estimator != AC_EST_EKF && o->estimator != AC_EST_UKF) return fail(AC_ERR_BAD_ARG, "lqg: unknown estimator");
+    if (o->feedback != AC_FB_ESTIMATE && o->feedback != AC_FB_TRUTH) return fail(AC_ERR_BAD_ARG, "lqg: unknown feedback");
+    if (!lqg_sense_opts_ok(s)) return fail(AC_ERR_BAD_ARG, "lqg: period must be >= 1 and dropout in [0, 1)");
+    if (!lqg_limits_ok(limits)) return fail(AC_ERR_BAD_ARG, "lqg: limits need u_min <= u_max");
+    const bool ukf = o->estimator == AC_EST_UKF;
+    const ac_ekf_opts eo{{s->mag_ned[0], s->mag_ned[1], s->mag_ned[2]}, 1};
+    const ac_ukf_opts uo{{s->mag_ned[0], s->mag_ned[1], s->mag_ned[2]}, 1, ukf ? o->kappa : 0.f};
+    // the estimator's own checks (dt, kappa, the quadrotor, the model, n == 0 or T == 0), against its part of the workspace
+    bool go = false;
+    const size_t est_floats = lqg_est_floats(o->estimator, n);
+    const bool ws_ok = ws && ws_floats >= lqg_ws_floats(o->estimator, n);
+    int rc = ukf ? ukf_check(h, &uo, dt, n, T, ws_ok ? ws : nullptr, est_floats, &go) : ekf_check(h, &eo, dt, n, T, ws_ok ? ws : nullptr, est_floats, &go);
+    if (rc == AC_ERR_WORKSPACE) return fail(AC_ERR_WORKSPACE, "lqg workspace too small: see ac_lqg_workspace_floats");
+    if (rc != AC_OK || !go) return rc;
+    if (!X0 || !Xhat0 || !P0 || !Xnom || !Unom || !Kx || !Qd || !Rd || !sigma_r || !Xo || !Po)
+        return fail(AC_ERR_BAD_ARG, "lqg: a required pointer is NULL");
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    // the loop's buffers behind the estimator's workspace
+    float* xt[2];
+    float* xh[2];
+    float* pp[2];
+    xt[0] = align256(ws + est_floats);
+    xt[1] = align256(xt[0] + 13 * N);
+    xh[0] = align256(xt[1] + 13 * N);
+    xh[1] = align256(xh[0] + 13 * N);
+    pp[0] = align256(xh[1] + 13 * N);
+    pp[1] = align256(pp[0] + 144 * N);
+    float* const ub = align256(pp[1] + 144 * N);
+    float* const zb = align256(ub + 7 * N);
+    int* const mb = (int*)align256(zb + 15 * N);  // ends at most ws + est_floats + 363 N + 9 * 63 floats
+    const LqgLimits lim = lqg_limits(limits);
+    const bool score = err || nees || score_status;
+    auto copy = [&](void* dst, const void* src, size_t floats) { return hipMemcpyAsync(dst, src, floats * sizeof(float), hipMemcpyDeviceToDevice, st); };
+    if (Xtrue) AC_HIP(copy(Xtrue, X0, 13 * N));
+    if (Xhat) AC_HIP(copy(Xhat, Xhat0, 13 * N));
+    const float *xt_in = X0, *xh_in = Xhat0, *p_in = P0;
+    int grid = 0;
+    for (long t = 0; t < T; ++t) {
+        const size_t k = (size_t)t;
+        const bool last = t == T - 1;
+        float* const xt_o = xt[t & 1];
+        float* const xh_o = last ? Xo : xh[t & 1];
+        float* const p_o = last ? Po : pp[t & 1];
+        float* const u_k = U ? U + k * 7 * N : ub;
+        float* const z_k = Z ? Z + k * 15 * N : zb;
+        int* const m_k = mask ? mask + k * N : mb;
+        // 1. the control law on the estimate (or the truth)
+        AC_HIP(lqg_launch_control(lim, o->feedback == AC_FB_TRUTH ? xt_in : xh_in, Xnom + k * 13 * N, Unom + k * 7 * N, Kx + k * 91 * N, n,
+                                  u_k, st, &grid));
+        note_launch(h, "k_lqg_control", grid, kLqgBlock, 0);
+        // 2. the truth: the handle's forward step, then the process noise of step step0 + k
+        rc = step_impl(h, xt_in, u_k, dt, nullptr, n, n, xt_o, stream);
+        if (rc != AC_OK) return rc;
+        if (sigma_q) {
+            AC_HIP(lqg_launch_disturb(*s, o->step0 + (int)t, nullptr, xt_o, sigma_q, n, xt_o, st, &grid));
+            note_launch(h, "k_lqg_sense", grid, kLqgBlock, 0);
+        }
+        if (Xtrue) AC_HIP(copy(Xtrue + (k + 1) * 13 * N, xt_o, 13 * N));
+        // 3. the sensors at step step0 + k + 1
+        AC_HIP(lqg_launch_sense(*s, h->dp.p.epsilon, o->step0 + (int)t + 1, nullptr, xt_o, sigma_r, n, z_k, m_k, st, &grid));
+        note_launch(h, "k_lqg_sense", grid, kLqgBlock, 0);
+        // 4. the estimator's own step
+        float* const nis_k = nis ? nis + k * N : nullptr;
+        int* const used_k = used ? used + k * N : nullptr;
+        int* const st_k = est_status ? est_status + k * N : nullptr;
+        rc = ukf ? ukf_step_impl(h, &uo, xh_in, p_in, u_k, dt, z_k, m_k, Qd, Rd, n, nullptr, xh_o, p_o, nullptr, nullptr, nis_k, nullptr,
+                                 used_k, st_k, nullptr, nullptr, nullptr, ws, stream)
+                 : ekf_step_impl(h, &eo, xh_in, p_in, u_k, dt, z_k, m_k, Qd, Rd, n, nullptr, xh_o, p_o, nullptr, nullptr, nis_k, nullptr,
+                                 used_k, st_k, nullptr, nullptr, nullptr, ws, stream);
+        if (rc != AC_OK) return rc;
+        if (Xhat) AC_HIP(copy(Xhat + (k + 1) * 13 * N, xh_o, 13 * N));
+        if (Ps) AC_HIP(copy(Ps + k * 144 * N, p_o, 144 * N));
+        // 5. the estimate against the truth
+        if (score) {
+            AC_HIP(lqg_launch_score(xt_o, xh_o, p_o, n, err ? err + k * 12 * N : nullptr, nees ? nees + k * N : nullptr,
+                                    score_status ? score_status + k * N : nullptr, st, &grid));
+            note_launch(h, "k_lqg_score", grid, kLqgBlock, 0);
+        }
+        xt_in = xt_o;
+        xh_in = xh_o;
+        p_in = p_o;
+    }
+    return AC_OK;
 }
 
 // ---- RTS smoother over the EKF trace (ac_rts.hpp, rts_inst.hip) ---------------------------------------------------------------------

@@ -20,7 +20,7 @@ from .base import SixDOF, SixDOFOpts
 from .coefficient_models import COEFF_MODEL_REGISTRY, CoefficientModel, DefaultModel
 
 __all__ = ["Aircraft", "AircraftOpts", "TrimResult", "LqrResult", "ModesResult", "EKF", "EkfTrace", "EkfSmooth", "EkfNoiseStats",
-           "EkfNoiseFit"]
+           "EkfNoiseFit", "UKF", "SensorModel", "LqgResult"]
 
 
 def _torch_mod():
@@ -516,6 +516,96 @@ class UKF(EKF):
         raise NotImplementedError("ukf: the EM noise fit assumes the EKF's P- = Abar P Abar' + Q; use Aircraft.ekf for it")
 
 
+EKF_MAG_NED = (0.45, 0.03, 0.89)  # a northern mid-latitude field direction (north, east, down), the default of mag_ned
+
+
+@dataclass
+class SensorModel:
+    """The simulated sensors of Aircraft.sense and the output-feedback rollouts (include/aircraft_hip.h, ac_sense_f32; DESIGN.md
+    §4.19).  sigma (15,) or (15, n): the standard deviation of every measurement row (finite, >= 0; checked for values on the
+    host, those of a tensor already on a device are not read, as in Aircraft.ekf).  The five sensor groups (GPS
+    position, GPS velocity, gyro, air data, magnetometer; three rows each) report at the steps with (step - phase[j]) % period[j]
+    == 0 and are then dropped with probability dropout[j] in [0, 1).  seed: a 64-bit integer; the draw of a row depends on (seed,
+    step, instance_offset + i, row) alone, so a sharded batch draws what the whole batch would."""
+    sigma: Any
+    period: Any = (1, 1, 1, 1, 1)
+    phase: Any = (0, 0, 0, 0, 0)
+    dropout: Any = (0.0, 0.0, 0.0, 0.0, 0.0)
+    seed: int = 0
+    mag_ned: Any = EKF_MAG_NED
+    instance_offset: int = 0
+
+    def __post_init__(self):
+        torch = _torch_mod()
+        g = _lib.LQG_GROUPS
+        if isinstance(self.sigma, torch.Tensor):
+            shp = tuple(self.sigma.shape)
+            sv = None if self.sigma.is_cuda else self.sigma.detach().numpy().astype(np.float64)
+        else:
+            sv = self.sigma = np.asarray(self.sigma, dtype=np.float64)
+            shp = self.sigma.shape
+        if sv is not None and (not np.isfinite(sv).all() or (sv < 0).any()):
+            raise ValueError("sensors: sigma must be finite and >= 0")
+        if len(shp) not in (1, 2) or shp[0] != _lib.EKF_ROWS:
+            raise ValueError(f"sensors: sigma must have shape (15,) or (15, n), got {shp}")
+        for name in ("period", "phase"):
+            v = np.asarray(getattr(self, name))
+            if v.shape != (g,) or v.dtype.kind not in "iu" or np.abs(v).max() >= 2 ** 31:
+                raise ValueError(f"sensors: {name} must be {g} integers, got {getattr(self, name)!r}")
+            setattr(self, name, tuple(int(x) for x in v))
+        if min(self.period) < 1:
+            raise ValueError("sensors: every period must be >= 1")
+        d = np.asarray(self.dropout, dtype=np.float64)
+        if d.shape != (g,) or not ((d >= 0) & (d < 1)).all():
+            raise ValueError("sensors: dropout must be 5 probabilities in [0, 1)")
+        self.dropout = tuple(float(x) for x in d)
+        if isinstance(self.seed, bool) or not isinstance(self.seed, (int, np.integer)) or not 0 <= int(self.seed) < 2 ** 64:
+            raise ValueError(f"sensors: seed must be an integer in [0, 2^64), got {self.seed!r}")
+        if isinstance(self.instance_offset, bool) or not isinstance(self.instance_offset, (int, np.integer)) or not 0 <= int(self.instance_offset) < 2 ** 63:
+            raise ValueError(f"sensors: instance_offset must be an integer >= 0, got {self.instance_offset!r}")
+        mg = np.asarray(self.mag_ned, dtype=np.float64)
+        if mg.shape != (3,) or not np.isfinite(mg).all():
+            raise ValueError("sensors: mag_ned must be 3 finite numbers")
+        self.mag_ned = tuple(float(x) for x in mg)
+
+    def _opts(self):
+        o = _lib.SenseOpts()
+        o.mag_ned[:] = self.mag_ned
+        o.seed_lo, o.seed_hi = int(self.seed) & 0xFFFFFFFF, int(self.seed) >> 32
+        o.instance_offset = int(self.instance_offset)
+        o.period[:], o.phase[:], o.dropout[:] = self.period, self.phase, self.dropout
+        return o
+
+    def _sigma(self, n, dev):
+        torch = _torch_mod()
+        s = self.sigma if isinstance(self.sigma, torch.Tensor) else torch.as_tensor(np.asarray(self.sigma, dtype=np.float32))
+        if s.dim() == 2 and s.shape[1] != n:
+            raise ValueError(f"sensors: sigma must have shape (15,) or (15, {n}), got {tuple(s.shape)}")
+        return s.to(device=dev, dtype=torch.float32).reshape(_lib.EKF_ROWS, -1).expand(_lib.EKF_ROWS, n).contiguous()
+
+
+@dataclass
+class LqgResult:
+    """What the output-feedback rollouts return for n instances and T steps (numpy in -> numpy out; tensors stay on the device;
+    include/aircraft_hip.h, ac_lqg_rollout_f32).  X, Xhat (T+1, 13, n): the truth and the estimate, node 0 the
+    starting ones; U (T, 7, n): the controls applied; Z (T, 15, n), mask (T, n): what the sensors reported after each step (NaN
+    and a cleared bit for a row that did not report); nis (T, n), used (T, n), status (T, n): the estimator's own (EkfTrace);
+    nees (T, n) = e' P^-1 e and err (T, 12, n) = x [-] x^ in the error coordinates, NaN nees where P had no Cholesky factor; P
+    (T, 12, 12, n) when recorded (record=("P",)), else None; Xnom (T+1, 13, n): the nominal the law tracked."""
+    X: Any
+    Xhat: Any
+    U: Any
+    Z: Any
+    mask: Any
+    nis: Any
+    nees: Any
+    err: Any
+    used: Any
+    status: Any
+    Xnom: Any
+    P: Any = None
+
+
 def inertia_about_com(cfg_Ixx, cfg_Iyy, cfg_Izz, cfg_Ixz, mass, com):
     """I = I0 + m K(com)   (reference dynamics/aircraft.py:137-141, 168-187), float64."""
     x, y, z = (float(c) for c in com)
@@ -1001,7 +1091,7 @@ class Aircraft(SixDOF):
         return (lam[..., 0], S[..., 0]) if vec else (lam, S)
 
     # ---- extended Kalman filter (include/aircraft_hip.h, ac_ekf_step_f32) -------------------------------
-    EKF_MAG_NED = (0.45, 0.03, 0.89)  # a northern mid-latitude field direction (north, east, down), the default of mag_ned
+    EKF_MAG_NED = EKF_MAG_NED  # (the module's: SensorModel's default too)
 
     def ekf_workspace(self, n: int):
         """Device workspace of a bank of n filters (ac_ekf_workspace_floats); allocate it before capturing a graph."""
@@ -1092,6 +1182,196 @@ class Aircraft(SixDOF):
         o.mag_ned[:] = [float(v) for v in mg]
         _lib.check(lib.ac_ekf_measure_f32(self._handle, C.byref(o), X.data_ptr(), n, Z.data_ptr(), self._stream()), "ac_ekf_measure_f32")
         return self._out(Z, npx, vec)
+
+    # ---- the loop closed through the estimator (include/aircraft_hip.h, ac_lqg_rollout_f32) ----------------
+    @staticmethod
+    def _step_index(step, name):
+        if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not -2 ** 31 <= int(step) < 2 ** 31:
+            raise ValueError(f"{name}: step must be a 32-bit integer, got {step!r}")
+        return int(step)
+
+    def sense(self, x, sensors: SensorModel, step, step_dev=None):
+        """(z (15, n), mask (n,)): what the simulated sensors report at the state x (13, n) at step `step`: h(x) plus the seeded
+        noise of `sensors`, NaN and a cleared mask bit for a group that does not report.  step_dev: an int32 device tensor of one
+        element that is added to `step` on the device (a captured call draws fresh noise when the caller increments it)."""
+        torch = _torch_mod()
+        if not isinstance(sensors, SensorModel):
+            raise ValueError("sense: sensors must be a SensorModel")
+        step = self._step_index(step, "sense")
+        if step_dev is not None and (not isinstance(step_dev, torch.Tensor) or step_dev.dtype != torch.int32 or step_dev.numel() != 1
+                                     or not step_dev.is_cuda):
+            raise ValueError("sense: step_dev must be an int32 device tensor of one element")
+        shp = tuple(x.shape) if isinstance(x, torch.Tensor) else np.shape(x)
+        if len(shp) not in (1, 2) or shp[0] != 13:
+            raise ValueError(f"sense: expected x (13, n), got {shp}")
+        n = shp[1] if len(shp) == 2 else 1
+        sg = sensors.sigma
+        if len(sg.shape) == 2 and sg.shape[1] != n:
+            raise ValueError(f"sensors: sigma must have shape (15,) or (15, {n}), got {tuple(sg.shape)}")
+        lib = self._sync()
+        X, npx, vec = self._in(x, self.num_states, "x")
+        S = sensors._sigma(n, X.device)
+        Z = torch.empty((_lib.EKF_ROWS, n), device=X.device, dtype=torch.float32)
+        M = torch.empty((n,), device=X.device, dtype=torch.int32)
+        o = sensors._opts()
+        _lib.check(lib.ac_sense_f32(self._handle, C.byref(o), step, None if step_dev is None else step_dev.data_ptr(), X.data_ptr(),
+                                    S.data_ptr(), n, Z.data_ptr(), M.data_ptr(), self._stream()), "ac_sense_f32")
+        Z = self._out(Z, npx, vec)
+        M = M.cpu().numpy() if npx else M
+        return Z, (M[0] if vec else M)
+
+    def lqg_workspace(self, est, n: int):
+        """Device workspace of an output-feedback rollout of n instances with the estimator `est` (an EKF or UKF bank, or
+        "ekf" / "ukf") (ac_lqg_workspace_floats); allocate it before capturing a graph."""
+        kind = est if isinstance(est, str) else ("ukf" if isinstance(est, UKF) else "ekf")
+        if kind not in _lib.LQG_ESTIMATORS:
+            raise ValueError(f"lqg_workspace: expected 'ekf' or 'ukf', got {est!r}")
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_lqg_workspace_floats(self._handle, _lib.LQG_ESTIMATORS[kind], int(n), C.byref(need)), "ac_lqg_workspace_floats")
+        return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
+
+    def rollout_output_feedback(self, est, x0, Xnom, Unom, Kx, dt, sensors: SensorModel, process_sigma=None, limits=None,
+                                feedback="estimate", record=(), step0=0, ws=None) -> LqgResult:
+        """Fly T steps of the closed loop in which the controller sees only what the estimator gives it.  est: an EKF or UKF bank
+        of this aircraft (Aircraft.ekf / Aircraft.ukf): it supplies x^0, P0, q, r and holds the final estimate afterwards, as
+        est.filter leaves it.  x0 (13, n): the true starting state; Xnom (T+1, 13, n), Unom (T, 7, n), Kx (T, 7, 13, n): the
+        nominal and the raw-state gains of u_k = clip(Unom_k + Kx_k (fb_k - Xnom_k)) (LqrResult.gains, ILQR), fb the estimate
+        (feedback="estimate") or the truth ("truth").  After every step the truth gets process noise of standard deviation
+        process_sigma ((12,) or (12, n) in the error coordinates, finite and >= 0, checked for host values; None: none), is
+        measured by `sensors` at step step0 + k + 1 and the estimator takes its own step.  step0 + T must stay below 2^31.  limits = (u_min (7,), u_max (7,)) (default: none); record=("P",) also returns the
+        covariances; ws: lqg_workspace(est, n).  The bank's mag_ned must be the sensors'.  Shapes and host values are checked
+        before any device is touched."""
+        torch = _torch_mod()
+        name = "rollout_output_feedback"
+        dt, lo, hi, record, step0 = self._lqg_args(name, est, sensors, dt, process_sigma, limits, feedback, record, step0, ws)
+        shp = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)  # noqa: E731
+        n, vec = est.n, est._vec
+        tail = () if vec else (n,)
+        sx, sn = shp(x0), shp(Xnom)
+        if sx != (13,) + tail:
+            raise ValueError(f"{name}: x0 must have shape {(13,) + tail}, got {sx}")
+        if len(sn) != 2 + len(tail) or sn[0] < 1 or sn[1:] != (13,) + tail:
+            raise ValueError(f"{name}: Xnom must have shape (T+1, 13{', n' if tail else ''}), got {sn}")
+        T = sn[0] - 1
+        if shp(Unom) != (T, 7) + tail or shp(Kx) != (T, 7, 13) + tail:
+            raise ValueError(f"{name}: expected Unom {(T, 7) + tail} and Kx {(T, 7, 13) + tail}, got {shp(Unom)} and {shp(Kx)}")
+        if step0 + T > 2 ** 31 - 1:
+            raise ValueError(f"{name}: step0 + T must stay below 2^31, got {step0} + {T}")
+        # ---- device side ----
+        self._sync()
+        dev = est._X.device
+        to = lambda a: (torch.as_tensor(np.asarray(a, dtype=np.float32)) if not isinstance(a, torch.Tensor) else a).to(device=dev, dtype=torch.float32)  # noqa: E731
+        X0 = to(x0).reshape(13, n).contiguous()
+        Xn, Un, Kt = to(Xnom).reshape(T + 1, 13, n).contiguous(), to(Unom).reshape(T, 7, n).contiguous(), to(Kx).reshape(T, 7, 13, n).contiguous()
+        out = self._lqg_run(est, X0, Xn, Un, Kt, dt, sensors, process_sigma, lo, hi, feedback, record, step0, ws)
+        return LqgResult(*(None if t is None else est._give(t) for t in out))
+
+    def _lqg_args(self, name, est, sensors, dt, process_sigma, limits, feedback, record, step0, ws):
+        """the checks the output-feedback rollouts share (no device is touched) -> dt, u_min, u_max, record, step0"""
+        torch = _torch_mod()
+        if not isinstance(est, EKF) or est.system is not self:
+            raise ValueError(f"{name}: est must be an EKF or UKF bank of this aircraft (Aircraft.ekf / Aircraft.ukf)")
+        if not isinstance(sensors, SensorModel):
+            raise ValueError(f"{name}: sensors must be a SensorModel")
+        if tuple(est.mag_ned) != tuple(sensors.mag_ned):  # (the loop hands the filter the sensors' field: one model, not two)
+            raise ValueError(f"{name}: the bank's mag_ned {est.mag_ned} differs from the sensors' {sensors.mag_ned}")
+        if feedback not in _lib.LQG_FEEDBACK:
+            raise ValueError(f"{name}: feedback must be 'estimate' or 'truth', got {feedback!r}")
+        record = (record,) if isinstance(record, str) else tuple(record)
+        if any(r != "P" for r in record):
+            raise ValueError(f"{name}: record may hold 'P' only, got {record!r}")
+        dt = EKF._dt(dt, True)
+        step0 = self._step_index(step0, name)
+        lo, hi = (np.full(7, -np.inf), np.full(7, np.inf)) if limits is None else (np.asarray(b, dtype=np.float64) for b in limits)
+        if lo.shape != (7,) or hi.shape != (7,) or np.isnan(lo).any() or np.isnan(hi).any() or (lo > hi).any():
+            raise ValueError(f"{name}: limits must be (u_min (7,), u_max (7,)) with u_min <= u_max")
+        n = est.n
+        sg = sensors.sigma
+        if len(sg.shape) == 2 and sg.shape[1] != n:
+            raise ValueError(f"sensors: sigma must have shape (15,) or (15, {n}), got {tuple(sg.shape)}")
+        if process_sigma is not None:
+            ps = tuple(process_sigma.shape) if isinstance(process_sigma, torch.Tensor) else np.shape(process_sigma)
+            if ps not in ((12,), (12, n)):
+                raise ValueError(f"{name}: process_sigma must have shape (12,) or (12, {n}), got {ps}")
+            if not (isinstance(process_sigma, torch.Tensor) and process_sigma.is_cuda):  # (device values are not read)
+                pv = process_sigma.detach().numpy() if isinstance(process_sigma, torch.Tensor) else process_sigma
+                pv = np.asarray(pv, dtype=np.float64)
+                if not np.isfinite(pv).all() or (pv < 0).any():
+                    raise ValueError(f"{name}: process_sigma must be finite and >= 0")
+        if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous()):
+            raise ValueError(f"{name}: ws must be a contiguous float32 device tensor (lqg_workspace(est, n))")
+        return dt, lo, hi, record, step0
+
+    def _lqg_run(self, est, X0, Xn, Un, Kt, dt, sensors, process_sigma, lo, hi, feedback, record, step0, ws):
+        """the device tensors of LqgResult's fields, in order, from checked device operands"""
+        torch = _torch_mod()
+        lib = self._sync()
+        dev, n, T = est._X.device, est.n, Un.shape[0]
+        to = lambda a: (torch.as_tensor(np.asarray(a, dtype=np.float32)) if not isinstance(a, torch.Tensor) else a).to(device=dev, dtype=torch.float32)  # noqa: E731
+        Sr = sensors._sigma(n, dev)
+        Sq = None if process_sigma is None else to(process_sigma).reshape(12, -1).expand(12, n).contiguous()
+        ukf = isinstance(est, UKF)
+        if ws is None:
+            ws = self.lqg_workspace(est, n)
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        Xo, Po = torch.empty((13, n), **f32), torch.empty((12, 12, n), **f32)
+        Xt, Xh, U = torch.empty((T + 1, 13, n), **f32), torch.empty((T + 1, 13, n), **f32), torch.empty((T, 7, n), **f32)
+        Ps = torch.empty((T, 12, 12, n), **f32) if "P" in record else None
+        Z, M = torch.empty((T, _lib.EKF_ROWS, n), **f32), torch.empty((T, n), **i32)
+        nis, nees, err = torch.empty((T, n), **f32), torch.empty((T, n), **f32), torch.empty((T, 12, n), **f32)
+        used, st, sst = torch.empty((T, n), **i32), torch.empty((T, n), **i32), torch.empty((T, n), **i32)
+        o = _lib.LqgOpts()
+        o.estimator, o.feedback = _lib.LQG_ESTIMATORS["ukf" if ukf else "ekf"], _lib.LQG_FEEDBACK[feedback]
+        o.kappa, o.step0 = (est.kappa if ukf else 0.0), step0
+        so = sensors._opts()
+        lim = _lib.IlqrCost()
+        lim.u_min[:] = [float(v) for v in lo]
+        lim.u_max[:] = [float(v) for v in hi]
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        _lib.check(lib.ac_lqg_rollout_f32(self._handle, C.byref(o), C.byref(so), C.byref(lim), X0.data_ptr(), est._X.data_ptr(),
+                                          est._P.data_ptr(), Xn.data_ptr(), Un.data_ptr(), Kt.data_ptr(), est._Qd.data_ptr(),
+                                          est._Rd.data_ptr(), ptr(Sq), Sr.data_ptr(), C.c_float(dt), n, T, Xo.data_ptr(), Po.data_ptr(),
+                                          Xt.data_ptr(), Xh.data_ptr(), U.data_ptr(), ptr(Ps), Z.data_ptr(), M.data_ptr(), nis.data_ptr(),
+                                          nees.data_ptr(), used.data_ptr(), st.data_ptr(), sst.data_ptr(), err.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), self._stream()), "ac_lqg_rollout_f32")
+        if T:
+            est._X, est._P = Xo, Po
+        else:
+            Xt[0], Xh[0] = X0, est._X
+        return (Xt, Xh, U, Z, M, nis, nees, err, used, st, Xn, Ps)
+
+    def rollout_lqg(self, res: LqrResult, est, x0, T, sensors: SensorModel, dt=None, process_sigma=None, limits=None,
+                    feedback="estimate", record=(), step0=0, ws=None) -> LqgResult:
+        """rollout_lqr flown on the estimate: Xnom is this handle's rollout of the design's nominal (res.x, res.u), the gains are
+        res.gains(Xnom) (exactly what rollout_lqr builds), and the loop is rollout_output_feedback's (see there for the other
+        arguments).  dt defaults to the design's."""
+        torch = _torch_mod()
+        if not isinstance(res, LqrResult):
+            raise ValueError("rollout_lqg: res must be an LqrResult (Aircraft.lqr)")
+        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 1:
+            raise ValueError(f"rollout_lqg: T must be an integer >= 1, got {T!r}")
+        dt, lo, hi, record, step0 = self._lqg_args("rollout_lqg", est, sensors, res.dt if dt is None else dt, process_sigma, limits,
+                                                   feedback, record, step0, ws)
+        if step0 + int(T) > 2 ** 31 - 1:
+            raise ValueError(f"rollout_lqg: step0 + T must stay below 2^31, got {step0} + {T}")
+        shp = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)  # noqa: E731
+        tail = () if est._vec else (est.n,)
+        if shp(x0) != (13,) + tail or shp(res.x) != (13,) + tail or shp(res.u) != (7,) + tail:
+            raise ValueError(f"rollout_lqg: x0 and the design's nominal must have shapes {(13,) + tail} and {(7,) + tail}, got {shp(x0)}, "
+                             f"{shp(res.x)}, {shp(res.u)}")
+        Xb, _, _ = self._in(res.x, self.num_states, "res.x")
+        Ub, _, _ = self._in(res.u, _lib.NUM_CONTROLS, "res.u")
+        n = est.n
+        Un = Ub.unsqueeze(0).expand(int(T), -1, -1).contiguous()
+        Xnom = self.rollout(Xb, Un, dt)
+        K = res.K if isinstance(res.K, torch.Tensor) else torch.as_tensor(np.asarray(res.K, dtype=np.float32))
+        K = K.to(device=Xb.device, dtype=torch.float32).reshape(7, 12, n)
+        Kx = self._lqr_gains(Xnom, K)
+        X0 = (torch.as_tensor(np.asarray(x0, dtype=np.float32)) if not isinstance(x0, torch.Tensor) else x0)
+        X0 = X0.to(device=Xb.device, dtype=torch.float32).reshape(13, n).contiguous()
+        out = self._lqg_run(est, X0, Xnom, Un, Kx, dt, sensors, process_sigma, lo, hi, feedback, record, step0, ws)
+        return LqgResult(*(None if t is None else est._give(t) for t in out))
 
     # what the test oracle needs to rebuild the same airframe (tests only)
     def airframe_dict(self) -> dict:

@@ -755,6 +755,77 @@ int ac_ukf_filter_rec_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, co
                           float* Xpreds, float* Ppreds, float* Abars /* per step, each may be NULL */, float* ws, size_t ws_floats,
                           void* stream);
 
+/* ---- the loop closed through the estimator: simulated sensors and the LQG rollout (fixed-wing models) ---------------
+ * Noise: Philox4x32-10 with key (seed_lo, seed_hi) and counter (g low word, g high word, step, purpose), g = instance_offset + i
+ * the GLOBAL instance; Box-Muller as ac_mppi_sample_f32 forms it.  Purposes 0-3: the four normals of measurement rows 4p .. 4p+3
+ * (the sixteenth is dropped); 4: word j is the uniform (x >> 8) 2^-24 of sensor group j = 0 .. 3; 5: word 0 is group 4's; 6-8: the
+ * twelve process-noise normals.  A draw depends on (seed, step, g, row) alone.  Sensor groups, three rows each: 0 GPS position,
+ * 1 GPS velocity, 2 gyro, 3 air data, 4 magnetometer (ac_ekf_step_f32's rows).
+ *   ac_sense_f32     at step s = step + (step_dev ? *step_dev : 0) (step_dev: a DEVICE int the caller increments, so that a captured
+ *                    call draws fresh noise on every replay; the sum wraps): group j reports when (s - phase[j]) % period[j] == 0
+ *                    (taken in 64-bit, so any int step and phase are allowed) and its uniform
+ *                    is not below dropout[j].  A reporting row is Z = fmaf(sigma_r, normal, h(X)), h being ac_ekf_measure_f32's
+ *                    values (so Z is that call's output bit for bit where sigma_r = 0); a group that does not report has its three
+ *                    mask bits cleared and NaN in its rows.  sigma_r [15][n] must be finite and >= 0 (not checked on the device).
+ *   ac_disturb_f32   Xo = X [+] (sigma_q . normals) in the EKF's chart, sigma_q [12][n]; Xo may be X.
+ *   ac_policy_f32    U_r = clip(Unom_r + sum_c Kx[r][c] (Fb_c - Xnom_c), u_min_r, u_max_r), the sum as one fmaf per c = 0 .. 12 in
+ *                    that order: ac_rollout_policy_f32's law with kff = 0 on whatever state Fb [13][n] it is handed.  Kx [7][13][n]
+ *                    (ac_lqr_gains_f32, ILQR), Xnom [13][n], Unom [7][n]; `limits`: only u_min, u_max are read (infinite bounds
+ *                    are allowed).
+ *   ac_estimate_score_f32   e [12][n] = X [-] Xhat in the chart, nees [n] = e' P^-1 e by a plain Cholesky of P [12][12][n] (its lower
+ *                    triangle is read) and one forward solve; status [n]: 1 when a pivot is <= 0 or not finite (nees = NaN), else 0.
+ *   ac_lqg_rollout_f32      a host loop of launches; for k = 0 .. T-1:
+ *                      1. u_k = policy(fb_k; Xnom_k, Unom_k, Kx_k), fb the estimate (AC_FB_ESTIMATE) or the truth (AC_FB_TRUTH);
+ *                      2. x_{k+1} = F(x_k, u_k, dt) (the handle's ac_step_f32 launch, any engine), then, sigma_q given, [+] noise at
+ *                         step step0 + k (sigma_q NULL: the step's output bit for bit);
+ *                      3. (z, mask) = sense(x_{k+1}) at step step0 + k + 1;
+ *                      4. ac_ekf_step_f32 / ac_ukf_step_f32 (predict set) with (x^_k, P_k, u_k, dt, z, mask, Qd, Rd);
+ *                      5. the score of x_{k+1} against (x^_{k+1}, P_{k+1}).
+ *                    The estimator's magnetometer model is the sensors' (s->mag_ned).
+ *                    Every output equals, bit for bit, what these single calls give in that order.  Inputs X0, Xhat0 [13][n], P0
+ *                    [12][12][n], Xnom [T+1][13][n] (node T is not read), Unom [T][7][n], Kx [T][7][13][n], Qd [12][n], Rd [15][n],
+ *                    sigma_q [12][n] | NULL, sigma_r [15][n].  Outputs: the final estimate Xo, Po (required); per step, each may be
+ *                    NULL: Xtrue, Xhat [T+1][13][n] (node 0 the inputs), U [T][7][n], Ps [T][12][12][n], Z [T][15][n], mask, used,
+ *                    est_status, score_status [T][n] (int), nis, nees [T][n], err [T][12][n].
+ * ws / ws_floats (the rollout only): caller-owned device scratch of at least ac_lqg_workspace_floats floats, else
+ * AC_ERR_WORKSPACE: the estimator's own workspace followed by the loop's buffers, every region on a 256-byte boundary.
+ * AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG (before any launch) for a NULL required pointer, n < 0, T < 0, a dt that is
+ * not finite and > 0, a period < 1, a dropout outside [0, 1), u_min > u_max or a NaN bound, an unknown estimator or feedback, a
+ * kappa that is not finite and >= 0, step0 + T > 2^31 - 1; n == 0 or T == 0 is AC_OK.  NaNs propagate (a non-finite truth gives NaN measurements, hence
+ * unused rows); nothing is trapped.  Asynchronous, no allocation, no synchronisation, hipGraph-capturable.  No atomics: an
+ * instance's bits depend neither on n nor on its place in the batch. */
+typedef struct ac_sense_opts {
+    float mag_ned[3];
+    unsigned seed_lo, seed_hi;
+    long instance_offset;
+    int period[5], phase[5];   /* group j reports at steps with (step - phase[j]) % period[j] == 0, period >= 1 */
+    float dropout[5];          /* probability in [0, 1) that a due group does not report */
+} ac_sense_opts;
+enum { AC_EST_EKF = 0, AC_EST_UKF = 1 };
+enum { AC_FB_ESTIMATE = 0, AC_FB_TRUTH = 1 };
+typedef struct ac_lqg_opts {
+    int estimator;   /* AC_EST_EKF | AC_EST_UKF */
+    int feedback;    /* AC_FB_ESTIMATE | AC_FB_TRUTH */
+    float kappa;     /* AC_EST_UKF only (ac_ukf_opts) */
+    int step0;       /* the step index of X0: node k + 1 is measured at step step0 + k + 1 */
+} ac_lqg_opts;
+int ac_sense_f32(ac_handle* h, const ac_sense_opts* o, int step, const int* step_dev /* device, may be NULL */,
+                 const float* X /* [13][n] */, const float* sigma_r /* [15][n] */, long n, float* Z /* [15][n] */,
+                 int* mask /* [n] */, void* stream);
+int ac_disturb_f32(ac_handle* h, const ac_sense_opts* o, int step, const int* step_dev, const float* X /* [13][n] */,
+                   const float* sigma_q /* [12][n] */, long n, float* Xo /* [13][n], may be X */, void* stream);
+int ac_policy_f32(ac_handle* h, const ac_ilqr_cost* limits, const float* Fb /* [13][n] */, const float* Xnom /* [13][n] */,
+                  const float* Unom /* [7][n] */, const float* Kx /* [7][13][n] */, long n, float* U /* [7][n] */, void* stream);
+int ac_estimate_score_f32(ac_handle* h, const float* X /* [13][n] */, const float* Xhat /* [13][n] */,
+                          const float* P /* [12][12][n] */, long n, float* e /* [12][n] */, float* nees /* [n] */,
+                          int* status /* [n] */, void* stream);
+int ac_lqg_workspace_floats(const ac_handle* h, int estimator, long n, size_t* floats);
+int ac_lqg_rollout_f32(ac_handle* h, const ac_lqg_opts* o, const ac_sense_opts* s, const ac_ilqr_cost* limits, const float* X0,
+                       const float* Xhat0, const float* P0, const float* Xnom, const float* Unom, const float* Kx, const float* Qd,
+                       const float* Rd, const float* sigma_q, const float* sigma_r, float dt, long n, long T, float* Xo, float* Po,
+                       float* Xtrue, float* Xhat, float* U, float* Ps, float* Z, int* mask, float* nis, float* nees, int* used,
+                       int* est_status, int* score_status, float* err, float* ws, size_t ws_floats, void* stream);
+
 /* ---- RTS smoother over the trace of the extended Kalman filter (fixed-wing models) --------------------------------
  * The fixed-interval Rauch-Tung-Striebel estimate of every node of a recorded filter run, given the whole run: one launch
  * (k_ekf_smooth) sweeps backward in time, one instance per 16-lane group.  Nodes k = 0 .. T-1 are the filter's steps: Xf, Pf
