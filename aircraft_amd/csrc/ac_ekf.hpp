@@ -30,27 +30,16 @@
 // after the other, phase by phase: a phase reads from the mirrors only what an EARLIER phase wrote.
 #pragma once
 #include "ac_dynamics.hpp"
-
-// AC_EKF_FP opens every function body of this header: no contraction of a * b + c into one FMA beyond the fmaf calls that are
-// written out, so that the device rounds where the host build (-ffp-contract=off) rounds.  The two then differ by the
-// library functions alone (atan2f, asinf, logf), and the host build's error against float64 is the device's.
-#ifdef AC_HOST_CHECK
-#define AC_EKF_INLINE
-#define AC_EKF_FP
-#else
-#define AC_EKF_INLINE __attribute__((always_inline))
-#define AC_EKF_FP _Pragma("clang fp contract(off)")
-#endif
+#include "ac_group.hpp"  // the group, AC_EKF_FP (it opens every function body of this header), kEkfFltMax
 
 namespace ac {
 
-constexpr int kEkfN = 12;        // error-state coordinates
-constexpr int kEkfZ = 15;        // measurement rows
-constexpr int kEkfLanes = 16;    // lanes of one instance's group (rows 12-15 idle)
-constexpr int kEkfLd = 13;       // row stride of the LDS mirrors
-constexpr int kEkfGroups = 16;   // instances per workgroup of k_ekf_step (four waves)
-constexpr int kEkfBlock = 256;   // lanes per workgroup of k_ekf_measure
-constexpr float kEkfFltMax = 3.0e38f;
+constexpr int kEkfN = 12;               // error-state coordinates
+constexpr int kEkfZ = 15;               // measurement rows
+constexpr int kEkfLanes = kGrpLanes;    // lanes of one instance's group (rows 12-15 idle)
+constexpr int kEkfLd = kGrpLd;          // row stride of the LDS mirrors
+constexpr int kEkfGroups = 16;          // instances per workgroup of k_ekf_step (four waves)
+constexpr int kEkfBlock = 256;          // lanes per workgroup of k_ekf_measure
 constexpr float kEkfLog2Pi = 1.8378770664093453f;
 constexpr long kEkfSensFloats = 13 + 169 + 91;      // x- | A | B per instance (the sensitivity launch's outputs)
 constexpr long kEkfChainFloats = 2 * (13 + 144);    // two (x, P) pairs per instance: ac_ekf_filter_f32's ping-pong

@@ -140,7 +140,7 @@ AC_DI void em_nodes_group(G& grp, EmShared& s, const EmIo& io, long i, long c, b
             s.xm[r] = L.cur.xm;
             L.pivbad = false;
         });
-        // ---- L L' = P-_k, column by column: lane r forms L_rj, every lane the pivot --------------------------------------------
+        // ---- L L' = P-_k, column by column (ac_group.hpp) ------------------------------------------------------------------------
 #pragma unroll
         for (int j = 0; j < 12; ++j) {
             grp.each([&](EmLane& L, int r) AC_EKF_INLINE {
@@ -150,21 +150,7 @@ AC_DI void em_nodes_group(G& grp, EmShared& s, const EmIo& io, long i, long c, b
                     for (int q = 0; q < kEkfLanes; ++q) ok = ok && s.red[q] == 0.f;
                     L.opsok = ok;
                 }
-                float t = s.m[0][r][j], d = s.m[0][j][j];  // (row r is overwritten from column j on only after this read)
-#pragma unroll
-                for (int q = 0; q < j; ++q) {
-                    const float lj = s.m[0][j][q];
-                    t = fmaf(-L.l[q], lj, t);
-                    d = fmaf(-lj, lj, d);
-                }
-                if (!(d > 0.f && d <= kEkfFltMax)) {
-                    L.pivbad = true;
-                    d = 1.0f;
-                }
-                const float w = 1.0f / sqrtf(d);
-                L.inv[j] = w;
-                L.l[j] = t * w;
-                if (r > j) s.m[0][r][j] = L.l[j];
+                grp_chol_column(s.m[0], L.l, r, j, L.inv[j], L.pivbad);
             });
         }
         // ---- lane j: row j of (P-_k)^-1 by two triangular solves, y_j, W_jj, t_kj; lane i: h_i(x^s), h_i, h_i P^s h_i' ---------------

@@ -26,7 +26,7 @@
 // The per-lane code is shared with the host build (tests/host_lqr, -DAC_HOST_CHECK), which runs the 16 lanes of a group one
 // after the other, phase by phase: a phase reads from the mirrors only what an EARLIER phase wrote.
 #pragma once
-#include "ac_math.hpp"
+#include "ac_group.hpp"
 #include "../../include/aircraft_hip.h"
 
 #ifdef AC_HOST_CHECK
@@ -39,7 +39,7 @@ namespace ac {
 
 constexpr int kLqrN = 12;       // chart coordinates
 constexpr int kLqrM = 7;        // controls
-constexpr int kLqrLanes = 16;   // lanes of one instance's group (rows 12-15 idle)
+constexpr int kLqrLanes = kGrpLanes;  // lanes of one instance's group (rows 12-15 idle)
 constexpr int kLqrLd = 13;      // row stride of the LDS mirrors
 constexpr int kLqrGroups = 4;   // instances per workgroup of k_lqr_dare (one wave)
 constexpr int kLqrBlock = 256;  // lanes per workgroup of the one-lane-per-instance kernels

@@ -169,7 +169,7 @@ AC_DI void rts_sweep_group(G& grp, RtsShared& s, const RtsIo& io, long i, bool s
             s.xm[r] = L.cur.xm;
             L.pivbad = false;
         });
-        // ---- L L' = P-_k, column by column: lane r forms L_rj, every lane the pivot; with column 0, row r of P_{k-1} Abar_k' ----
+        // ---- L L' = P-_k, column by column (ac_group.hpp); with column 0, row r of P_{k-1} Abar_k' -------------------------------------
 #pragma unroll
         for (int j = 0; j < 12; ++j) {
             grp.each([&](RtsLane& L, int r) AC_EKF_INLINE {
@@ -186,21 +186,7 @@ AC_DI void rts_sweep_group(G& grp, RtsShared& s, const RtsIo& io, long i, bool s
                         L.mr[q] = acc;
                     }
                 }
-                float t = s.m[0][r][j], d = s.m[0][j][j];  // (row r is overwritten from column j on only after this read)
-#pragma unroll
-                for (int c = 0; c < j; ++c) {
-                    const float lj = s.m[0][j][c];
-                    t = fmaf(-L.l[c], lj, t);
-                    d = fmaf(-lj, lj, d);
-                }
-                if (!(d > 0.f && d <= kEkfFltMax)) {
-                    L.pivbad = true;
-                    d = 1.0f;
-                }
-                const float w = 1.0f / sqrtf(d);
-                L.inv[j] = w;
-                L.l[j] = t * w;
-                if (r > j) s.m[0][r][j] = L.l[j];
+                grp_chol_column(s.m[0], L.l, r, j, L.inv[j], L.pivbad);
             });
         }
         // ---- row r of C_k by two triangular solves; e = x^s_k [-] x-_k; element r of C_k e -----------------------------------------

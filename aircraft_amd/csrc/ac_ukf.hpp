@@ -73,27 +73,6 @@ struct UkfSigLane {
     bool pivbad;
 };
 
-// One column of the plain Cholesky of the matrix in m (RtsShared's scheme): lane r forms L_rj, every lane the pivot.
-// -> false when the pivot is <= 0 or not finite (the column is then formed with pivot 1).
-AC_DI bool ukf_chol_column(float (&m)[kEkfLanes][kEkfLd], float (&l)[12], int r, int j) {
-    AC_EKF_FP
-    float t = m[r][j], d = m[j][j];  // (row r is overwritten from column j on only after this read)
-#pragma unroll
-    for (int c = 0; c < 12; ++c) {
-        if (c < j) {
-            const float lj = m[j][c];
-            t = fmaf(-l[c], lj, t);
-            d = fmaf(-lj, lj, d);
-        }
-    }
-    const bool ok = d > 0.f && d <= kEkfFltMax;
-    if (!ok) d = 1.0f;
-    const float w = 1.0f / sqrtf(d);
-    l[j] = t * w;
-    if (r > j) m[r][j] = l[j];
-    return ok;
-}
-
 // gamma times column c of the factor whose strict lower triangle is in m and whose diagonal entry of row c is dg (c < 12)
 AC_DI void ukf_column(const float (&m)[kEkfLanes][kEkfLd], float dg, float gamma, int c, float dl[12]) {
     AC_EKF_FP
@@ -111,10 +90,12 @@ AC_DI void ukf_sigma_group(G& grp, UkfSigShared& s, const UkfWeights& w, const U
         for (int j = 0; j < 12; ++j) s.m[r][j] = io.P[(rr * 12 + j) * n + i];
         L.pivbad = false;
     });
+    // ---- L L' = P, column by column (ac_group.hpp; 1 / L_jj is not kept) ----------------------------------------------------------
 #pragma unroll
     for (int j = 0; j < 12; ++j) {
         grp.each([&](UkfSigLane& L, int r) AC_EKF_INLINE {
-            if (!ukf_chol_column(s.m, L.l, r, j)) L.pivbad = true;
+            float iv;
+            grp_chol_column(s.m, L.l, r, j, iv, L.pivbad);
         });
     }
     grp.each([&](UkfSigLane& L, int r) AC_EKF_INLINE {
@@ -318,7 +299,7 @@ AC_DI void ukf_update_group(G& grp, UkfShared& s, const ac_ukf_opts& o, const Uk
         L.pmbad = false;
         L.rd = io.Rd[(r < kEkfZ ? r : 0) * n + i];
     });
-    // ---- L- L-' = P-, column by column -------------------------------------------------------------------------------------------
+    // ---- L- L-' = P-, column by column (ac_group.hpp) ---------------------------------------------------------------------------------
 #pragma unroll
     for (int j = 0; j < 12; ++j) {
         grp.each([&](UkfLane& L, int r) AC_EKF_INLINE {
@@ -328,7 +309,8 @@ AC_DI void ukf_update_group(G& grp, UkfShared& s, const ac_ukf_opts& o, const Uk
                 for (int k = 0; k < kEkfN; ++k) ok = ok && s.red[k] == 0.f;
                 L.predok = ok;
             }
-            if (!ukf_chol_column(s.b.m, L.l, r, j)) L.pmbad = true;
+            float iv;
+            grp_chol_column(s.b.m, L.l, r, j, iv, L.pmbad);
             if (r == j) s.dg[j] = L.l[j];
         });
     }

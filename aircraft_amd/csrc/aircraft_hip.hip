@@ -276,6 +276,43 @@ int instance(int rc, const char* missing) { return rc == kNoInstance ? fail(AC_E
 // engines: plan.)
 const MlpPlan& engine_plan(const ac_handle* h) { return h->use_mfma ? h->plan_sens : h->plan; }
 
+// T steps as a host loop over an estimator's step, for a caller that has run the estimator's *_check.  step: its *_step_impl
+// on the handle, the options and the workspace; buf: the two (x, P) pairs of the ping-pong in that workspace; name: what the
+// messages call it.  Xpreds, Ppreds, Abars: the per-step records a smoother reads (each may be NULL).
+template <class Step>
+int filter_loop(const char* name, bool predict, Step step, float* const buf[4], const float* X, const float* P, const float* U,
+                float dt, const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po,
+                float* ll, float* Xs, float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds,
+                float* Ppreds, float* Abars, void* stream) {
+    if (!X || !P || !Z || !Rd || !Xo || !Po || !ll) {
+        snprintf(g_err, sizeof(g_err), "%s filter: a required pointer is NULL", name);
+        return AC_ERR_BAD_ARG;
+    }
+    if (predict && (!U || !Qd)) {
+        snprintf(g_err, sizeof(g_err), "%s filter: U and Qd are required when predict is set", name);
+        return AC_ERR_BAD_ARG;
+    }
+    const size_t N = (size_t)n;
+    const float *xin = X, *pin = P;
+    for (long t = 0; t < T; ++t) {
+        const bool last = t == T - 1;
+        float* const xo = last ? Xo : buf[2 * (t & 1)];
+        float* const po = last ? Po : buf[2 * (t & 1) + 1];
+        const size_t k = (size_t)t;
+        const int rc = step(xin, pin, U ? U + k * 7 * N : nullptr, dt, Z + k * 15 * N, mask ? mask + k * N : nullptr, Qd, Rd, n,
+                            t ? ll : nullptr, xo, po, nu ? nu + k * 15 * N : nullptr, S ? S + k * 15 * N : nullptr,
+                            nis ? nis + k * N : nullptr, ll, used ? used + k * N : nullptr, status ? status + k * N : nullptr,
+                            Xpreds ? Xpreds + k * 13 * N : nullptr, Ppreds ? Ppreds + k * 144 * N : nullptr,
+                            Abars ? Abars + k * 144 * N : nullptr);
+        if (rc != AC_OK) return rc;
+        if (Xs) AC_HIP(hipMemcpyAsync(Xs + k * 13 * N, xo, 13 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        if (Ps) AC_HIP(hipMemcpyAsync(Ps + k * 144 * N, po, 144 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        xin = xo;
+        pin = po;
+    }
+    return AC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2345,42 +2382,6 @@ int ac_ekf_step_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const fl
 }
 
 namespace {
-// T steps as a host loop over the step; Xpreds, Ppreds, Abars: the per-step records a smoother reads (each may be NULL)
-int ekf_filter_impl(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
-                    const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
-                    float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds, float* Ppreds, float* Abars,
-                    float* ws, size_t ws_floats, void* stream) {
-    bool go = false;
-    int rc = ekf_check(h, o, dt, n, T, ws, ws_floats, &go);
-    if (rc != AC_OK || !go) return rc;
-    if (!X || !P || !Z || !Rd || !Xo || !Po || !ll) return fail(AC_ERR_BAD_ARG, "ekf filter: a required pointer is NULL");
-    if (o->predict && (!U || !Qd)) return fail(AC_ERR_BAD_ARG, "ekf filter: U and Qd are required when predict is set");
-    const size_t N = (size_t)n;
-    float* buf[4];  // x, P | x, P behind the sensitivity outputs
-    buf[0] = align256(align256(align256(align256(ws) + 13 * N) + 169 * N) + 91 * N);
-    buf[1] = align256(buf[0] + 13 * N);
-    buf[2] = align256(buf[1] + 144 * N);
-    buf[3] = align256(buf[2] + 13 * N);  // ends at most ws + 587 N + 7 * 63 floats
-    const float *xin = X, *pin = P;
-    for (long t = 0; t < T; ++t) {
-        const bool last = t == T - 1;
-        float* const xo = last ? Xo : buf[2 * (t & 1)];
-        float* const po = last ? Po : buf[2 * (t & 1) + 1];
-        const size_t k = (size_t)t;
-        rc = ekf_step_impl(h, o, xin, pin, U ? U + k * 7 * N : nullptr, dt, Z + k * 15 * N, mask ? mask + k * N : nullptr, Qd, Rd, n,
-                           t ? ll : nullptr, xo, po, nu ? nu + k * 15 * N : nullptr, S ? S + k * 15 * N : nullptr,
-                           nis ? nis + k * N : nullptr, ll, used ? used + k * N : nullptr, status ? status + k * N : nullptr,
-                           Xpreds ? Xpreds + k * 13 * N : nullptr, Ppreds ? Ppreds + k * 144 * N : nullptr,
-                           Abars ? Abars + k * 144 * N : nullptr, ws, stream);
-        if (rc != AC_OK) return rc;
-        if (Xs) AC_HIP(hipMemcpyAsync(Xs + k * 13 * N, xo, 13 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        if (Ps) AC_HIP(hipMemcpyAsync(Ps + k * 144 * N, po, 144 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        xin = xo;
-        pin = po;
-    }
-    return AC_OK;
-}
-
 // do two spans of floats share an element? (a NULL span shares none)
 struct RtsSpan { const float* p; size_t floats; };
 bool rts_overlap(const RtsSpan& a, const RtsSpan& b) {
@@ -2392,9 +2393,8 @@ bool rts_overlap(const RtsSpan& a, const RtsSpan& b) {
 int ac_ekf_filter_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
                       const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
                       float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* ws, size_t ws_floats, void* stream) {
-    AC_ENTER(h);
-    return ekf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, nullptr, nullptr,
-                           nullptr, ws, ws_floats, stream);
+    return ac_ekf_filter_rec_f32(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, nullptr,
+                                 nullptr, nullptr, ws, ws_floats, stream);
 }
 
 int ac_ekf_filter_rec_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, const float* P, const float* U, float dt,
@@ -2402,8 +2402,18 @@ int ac_ekf_filter_rec_f32(ac_handle* h, const ac_ekf_opts* o, const float* X, co
                           float* ll, float* Xs, float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds,
                           float* Ppreds, float* Abars, float* ws, size_t ws_floats, void* stream) {
     AC_ENTER(h);
-    return ekf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, Xpreds, Ppreds,
-                           Abars, ws, ws_floats, stream);
+    bool go = false;
+    const int rc = ekf_check(h, o, dt, n, T, ws, ws_floats, &go);
+    if (rc != AC_OK || !go) return rc;
+    const size_t N = (size_t)n;
+    float* buf[4];  // x, P | x, P behind the sensitivity outputs
+    buf[0] = align256(align256(align256(align256(ws) + 13 * N) + 169 * N) + 91 * N);
+    buf[1] = align256(buf[0] + 13 * N);
+    buf[2] = align256(buf[1] + 144 * N);
+    buf[3] = align256(buf[2] + 13 * N);  // ends at most ws + 587 N + 7 * 63 floats
+    const auto step = [&](auto... a) { return ekf_step_impl(h, o, a..., ws, stream); };
+    return filter_loop("ekf", o->predict, step, buf, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status,
+                       Xpreds, Ppreds, Abars, stream);
 }
 
 // ---- unscented Kalman filter beside the EKF bank (ac_ukf.hpp, ukf_inst.hip) ---------------------------------------------------------
@@ -2465,38 +2475,6 @@ int ukf_check(ac_handle* h, const ac_ukf_opts* o, float dt, long n, long T, cons
     *go = true;
     return AC_OK;
 }
-
-// T steps as a host loop over the step (ekf_filter_impl's)
-int ukf_filter_impl(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
-                    const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
-                    float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds, float* Ppreds, float* Abars,
-                    float* ws, size_t ws_floats, void* stream) {
-    bool go = false;
-    int rc = ukf_check(h, o, dt, n, T, ws, ws_floats, &go);
-    if (rc != AC_OK || !go) return rc;
-    if (!X || !P || !Z || !Rd || !Xo || !Po || !ll) return fail(AC_ERR_BAD_ARG, "ukf filter: a required pointer is NULL");
-    if (o->predict && (!U || !Qd)) return fail(AC_ERR_BAD_ARG, "ukf filter: U and Qd are required when predict is set");
-    const size_t N = (size_t)n;
-    const UkfWs w(ws, N);
-    const float *xin = X, *pin = P;
-    for (long t = 0; t < T; ++t) {
-        const bool last = t == T - 1;
-        float* const xo = last ? Xo : w.buf[2 * (t & 1)];
-        float* const po = last ? Po : w.buf[2 * (t & 1) + 1];
-        const size_t k = (size_t)t;
-        rc = ukf_step_impl(h, o, xin, pin, U ? U + k * 7 * N : nullptr, dt, Z + k * 15 * N, mask ? mask + k * N : nullptr, Qd, Rd, n,
-                           t ? ll : nullptr, xo, po, nu ? nu + k * 15 * N : nullptr, S ? S + k * 15 * N : nullptr,
-                           nis ? nis + k * N : nullptr, ll, used ? used + k * N : nullptr, status ? status + k * N : nullptr,
-                           Xpreds ? Xpreds + k * 13 * N : nullptr, Ppreds ? Ppreds + k * 144 * N : nullptr,
-                           Abars ? Abars + k * 144 * N : nullptr, ws, stream);
-        if (rc != AC_OK) return rc;
-        if (Xs) AC_HIP(hipMemcpyAsync(Xs + k * 13 * N, xo, 13 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        if (Ps) AC_HIP(hipMemcpyAsync(Ps + k * 144 * N, po, 144 * N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        xin = xo;
-        pin = po;
-    }
-    return AC_OK;
-}
 }  // namespace
 
 int ac_ukf_workspace_floats(const ac_handle* h, long n, size_t* floats) {
@@ -2524,9 +2502,8 @@ int ac_ukf_step_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, const fl
 int ac_ukf_filter_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt, const float* Z,
                       const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xo, float* Po, float* ll, float* Xs,
                       float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* ws, size_t ws_floats, void* stream) {
-    AC_ENTER(h);
-    return ukf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, nullptr, nullptr,
-                           nullptr, ws, ws_floats, stream);
+    return ac_ukf_filter_rec_f32(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, nullptr,
+                                 nullptr, nullptr, ws, ws_floats, stream);
 }
 
 int ac_ukf_filter_rec_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, const float* P, const float* U, float dt,
@@ -2534,8 +2511,13 @@ int ac_ukf_filter_rec_f32(ac_handle* h, const ac_ukf_opts* o, const float* X, co
                           float* ll, float* Xs, float* Ps, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds,
                           float* Ppreds, float* Abars, float* ws, size_t ws_floats, void* stream) {
     AC_ENTER(h);
-    return ukf_filter_impl(h, o, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status, Xpreds, Ppreds,
-                           Abars, ws, ws_floats, stream);
+    bool go = false;
+    const int rc = ukf_check(h, o, dt, n, T, ws, ws_floats, &go);
+    if (rc != AC_OK || !go) return rc;
+    const UkfWs w(ws, (size_t)n);
+    const auto step = [&](auto... a) { return ukf_step_impl(h, o, a..., ws, stream); };
+    return filter_loop("ukf", o->predict, step, w.buf, X, P, U, dt, Z, mask, Qd, Rd, n, T, Xo, Po, ll, Xs, Ps, nu, S, nis, used, status,
+                       Xpreds, Ppreds, Abars, stream);
 }
 
 // ---- the loop closed through the estimator (ac_lqg.hpp, lqg_inst.hip) ---------------------------------------------------------------

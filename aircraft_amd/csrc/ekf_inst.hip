@@ -2,32 +2,13 @@
 #include "ac_ekf.hpp"
 
 namespace ac {
-namespace {
 
-// One lane of a 16-lane group: a phase, then the workgroup's barrier (it orders the LDS traffic of the phase).
-struct EkfGroupDev {
-    EkfLane L;
-    int r;
-    template <class F>
-    __device__ __forceinline__ void each(F f) {
-        f(L, r);
-        __syncthreads();
-    }
-};
-
-}  // namespace
-
-// A group past the end of the batch filters the last instance again and stores nothing: every lane of the workgroup
-// reaches every barrier.
 template <bool PREDICT>
 __global__ __launch_bounds__(kEkfGroups* kEkfLanes) void k_ekf_step(const ac_ekf_opts o, float eps, const EkfIo io) {
     __shared__ EkfShared sh[kEkfGroups];
-    const int g = threadIdx.x / kEkfLanes;
-    long i = (long)blockIdx.x * kEkfGroups + g;
-    const bool store = i < io.n;
-    if (!store) i = io.n - 1;
-    EkfGroupDev grp;
-    grp.r = threadIdx.x % kEkfLanes;
+    AC_GROUP_SLOT(kEkfLanes, kEkfGroups, blockIdx.x, io.n);
+    GroupDev<EkfLane> grp;
+    grp.r = r;
     ekf_step_group<PREDICT>(grp, sh[g], o, eps, io, i, store);
 }
 

@@ -2,33 +2,16 @@
 #include "ac_em.hpp"
 
 namespace ac {
-namespace {
-
-// One lane of a 16-lane group: a phase, then the workgroup's barrier (it orders the LDS traffic of the phase).
-struct EmGroupDev {
-    EmLane L;
-    int r;
-    template <class F>
-    __device__ __forceinline__ void each(F f) {
-        f(L, r);
-        __syncthreads();
-    }
-};
-
-}  // namespace
 
 // Workgroup b works on chunk b / gb of the instances (b % gb) * 16 .. + 15 (gb: workgroups per chunk), so that neighbouring
-// workgroups read neighbouring columns of the same nodes.  A group past the end of the batch works on the last instance again
-// and stores nothing: every lane of the workgroup reaches every barrier (the chunk is the same for all).
+// workgroups read neighbouring columns of the same nodes (the chunk is the same for every group of the workgroup:
+// AC_GROUP_SLOT's rule holds).
 __global__ __launch_bounds__(kEmGroups* kEkfLanes) void k_ekf_em_nodes(const EmIo io, const long gb) {
     __shared__ EmShared sh[kEmGroups];
-    const int g = threadIdx.x / kEkfLanes;
+    AC_GROUP_SLOT(kEkfLanes, kEmGroups, (long)blockIdx.x % gb, io.n);
     const long c = (long)blockIdx.x / gb;
-    long i = ((long)blockIdx.x % gb) * kEmGroups + g;
-    const bool store = i < io.n;
-    if (!store) i = io.n - 1;
-    EmGroupDev grp;
-    grp.r = threadIdx.x % kEkfLanes;
+    GroupDev<EmLane> grp;
+    grp.r = r;
     em_nodes_group(grp, sh[g], io, i, c, store);
 }
 

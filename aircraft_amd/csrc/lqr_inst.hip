@@ -4,17 +4,6 @@
 namespace ac {
 namespace {
 
-// One lane of a 16-lane group: a phase, then a barrier (a workgroup is one wave: the barrier orders its LDS traffic).
-struct LqrGroupDev {
-    LqrLane L;
-    int r;
-    template <class F>
-    __device__ __forceinline__ void each(F f) {
-        f(L, r);
-        __syncthreads();
-    }
-};
-
 int lane_grid(long n) { return (int)((n + kLqrBlock - 1) / kLqrBlock); }
 
 }  // namespace
@@ -29,19 +18,15 @@ __global__ __launch_bounds__(kLqrBlock) void k_lqr_project(const float* __restri
                      LqrCol{Axi + i, n}, LqrCol{Bxi + i, n});
 }
 
-// A group past the end of the batch solves the last instance again and stores nothing: every lane of the workgroup
-// reaches every barrier.
+// (a workgroup is one wave: the group's barrier orders its LDS traffic)
 __global__ __launch_bounds__(kLqrGroups* kLqrLanes) void k_lqr_dare(const ac_lqr_opts o, int iters, const float* __restrict__ Axi,
                                                                      const float* __restrict__ Bxi, long n, float* __restrict__ P,
                                                                      float* __restrict__ K, float* __restrict__ resid,
                                                                      int* __restrict__ status, int* __restrict__ used_iters) {
     __shared__ LqrShared sh[kLqrGroups];
-    const int g = threadIdx.x / kLqrLanes;
-    long i = (long)blockIdx.x * kLqrGroups + g;
-    const bool store = i < n;
-    if (!store) i = n - 1;
-    LqrGroupDev grp;
-    grp.r = threadIdx.x % kLqrLanes;
+    AC_GROUP_SLOT(kLqrLanes, kLqrGroups, blockIdx.x, n);
+    GroupDev<LqrLane> grp;
+    grp.r = r;
     lqr_dare_group(grp, sh[g], o, iters, LqrCCol{Axi + i, n}, LqrCCol{Bxi + i, n}, LqrCol{P + i, n}, LqrCol{K + i, n}, resid + i,
                    status + i, used_iters + i, store);
 }

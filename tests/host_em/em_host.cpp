@@ -1,7 +1,7 @@
 // em_host.cpp — the per-lane code of the EM statistics for the EKF's noise variances (aircraft_amd/csrc/ac_em.hpp) compiled for
 // the HOST (g++, -DAC_HOST_CHECK -ffp-contract=off) behind a small C API, so that `pytest -m "not gpu"` measures the float32
 // arithmetic of the Cholesky, the triangular solves and the per-node terms against float64 without a GPU.  The 16 lanes of an
-// instance's group run one after the other, phase by phase (EmGroupHost), on the same code the device runs; the chunks and
+// instance's group run one after the other, phase by phase (GroupHost, ac_group.hpp), on the same code the device runs; the chunks and
 // the reduction are the device's too.  AC_EM_HEADER names the header (the tests also build mutated copies of it).
 // TEST INFRASTRUCTURE: nothing in aircraft_amd loads this.
 #define AC_HOST_CHECK 1
@@ -13,18 +13,6 @@
 #include <vector>
 
 using namespace ac;
-
-namespace {
-
-struct EmGroupHost {
-    EmLane L[kEkfLanes];
-    template <class F>
-    void each(F f) {
-        for (int r = 0; r < kEkfLanes; ++r) f(L[r], r);
-    }
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -41,7 +29,7 @@ int host_em_stats(const float* mag, float floor_rel, float eps, const float* Xpr
                   {mag[0], mag[1], mag[2]}, eps, floor_rel, n, T};
     for (long c = 0; c < chunks; ++c)
         for (long i = 0; i < n; ++i) {
-            EmGroupHost grp{};
+            GroupHost<EmLane, kEkfLanes> grp{};
             EmShared s{};
             em_nodes_group(grp, s, io, i, c, true);
         }

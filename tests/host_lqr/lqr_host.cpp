@@ -1,7 +1,7 @@
 // lqr_host.cpp — the LQR's per-lane code (aircraft_amd/csrc/ac_lqr.hpp) compiled for the HOST (g++, -DAC_HOST_CHECK) behind a
 // small C API, so that `pytest -m "not gpu"` measures the float32 arithmetic of the projection, the Riccati solve, the gain
 // expansion and the chart against float64 without a GPU.  The 16 lanes of an instance's group run one after the other,
-// phase by phase (LqrGroupHost), on the same code the device runs.  AC_LQR_HEADER names the header (the tests also build
+// phase by phase (GroupHost, ac_group.hpp), on the same code the device runs.  AC_LQR_HEADER names the header (the tests also build
 // mutated copies of it).
 // TEST INFRASTRUCTURE: nothing in aircraft_amd loads this.
 #define AC_HOST_CHECK 1
@@ -11,18 +11,6 @@
 #include AC_LQR_HEADER
 
 using namespace ac;
-
-namespace {
-
-struct LqrGroupHost {
-    LqrLane L[kLqrLanes];
-    template <class F>
-    void each(F f) {
-        for (int r = 0; r < kLqrLanes; ++r) f(L[r], r);
-    }
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -37,7 +25,7 @@ int host_lqr_project(const float* X, const float* Xp, const float* A, const floa
 int host_lqr_dare(const ac_lqr_opts* o, const float* Axi, const float* Bxi, int iters, long n, float* P, float* K, float* resid,
                   int* status, int* used_iters) {
     for (long i = 0; i < n; ++i) {
-        LqrGroupHost grp{};
+        GroupHost<LqrLane, kLqrLanes> grp{};
         LqrShared s{};
         lqr_dare_group(grp, s, *o, iters, LqrCCol{Axi + i, n}, LqrCCol{Bxi + i, n}, LqrCol{P + i, n}, LqrCol{K + i, n}, resid + i,
                        status + i, used_iters + i, true);
@@ -59,7 +47,7 @@ int host_steady_error(const float* X, const float* Xnom, long n, float* xi) {
 
 // the group elimination alone: W [12][12], RHS [12][24] row-major -> X = W^-1 RHS [12][24]
 int host_lqr_gj(const float* W, const float* RHS, float* X, int* bad) {
-    LqrGroupHost grp{};
+    GroupHost<LqrLane, kLqrLanes> grp{};
     LqrShared s{};
     for (int r = 0; r < kLqrN; ++r) {
         for (int j = 0; j < 12; ++j) grp.L[r].w[j] = W[r * 12 + j];

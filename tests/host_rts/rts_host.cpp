@@ -1,7 +1,7 @@
 // rts_host.cpp — the RTS smoother's per-lane code (aircraft_amd/csrc/ac_rts.hpp) compiled for the HOST (g++, -DAC_HOST_CHECK
 // -ffp-contract=off) behind a small C API, so that `pytest -m "not gpu"` measures the float32 arithmetic of the Cholesky, the
 // triangular solves, the chart and the covariance recursion against float64 without a GPU.  The 16 lanes of an instance's
-// group run one after the other, phase by phase (RtsGroupHost), on the same code the device runs.  AC_RTS_HEADER names the
+// group run one after the other, phase by phase (GroupHost, ac_group.hpp), on the same code the device runs.  AC_RTS_HEADER names the
 // header (the tests also build mutated copies of it).
 // TEST INFRASTRUCTURE: nothing in aircraft_amd loads this.
 #define AC_HOST_CHECK 1
@@ -12,18 +12,6 @@
 
 using namespace ac;
 
-namespace {
-
-struct RtsGroupHost {
-    RtsLane L[kEkfLanes];
-    template <class F>
-    void each(F f) {
-        for (int r = 0; r < kEkfLanes; ++r) f(L[r], r);
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
 // the backward sweep of every instance; X0, P0, Xs0, Ps0 all given or all NULL; Cg may be NULL
@@ -31,7 +19,7 @@ int host_rts_smooth(const float* X0, const float* P0, const float* Xf, const flo
                     const float* Abar, long n, long T, float* Xs, float* Ps, float* Xs0, float* Ps0, float* Cg, int* status) {
     const RtsIo io{X0, P0, Xf, Pf, Xpred, Ppred, Abar, Xs, Ps, Xs0, Ps0, Cg, status, n, T};
     for (long i = 0; i < n; ++i) {
-        RtsGroupHost grp{};
+        GroupHost<RtsLane, kEkfLanes> grp{};
         RtsShared s{};
         rts_sweep_group(grp, s, io, i, true);
     }

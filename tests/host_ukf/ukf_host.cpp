@@ -1,6 +1,6 @@
 // ukf_host.cpp — the UKF's per-lane code (aircraft_amd/csrc/ac_ukf.hpp) compiled for the HOST (g++, -DAC_HOST_CHECK
 // -ffp-contract=off) behind a small C API, so that `pytest -m "not gpu"` measures the float32 arithmetic of the two kernels
-// against float64 without a GPU.  The 16 lanes of an instance's group run one after the other, phase by phase, on the same
+// against float64 without a GPU.  The 16 lanes of an instance's group run one after the other, phase by phase (GroupHost, ac_group.hpp), on the same
 // code the device runs.  AC_UKF_HEADER names the header (the tests also build mutated copies of it).
 // TEST INFRASTRUCTURE: nothing in aircraft_amd loads this.
 #define AC_HOST_CHECK 1
@@ -11,19 +11,6 @@
 
 using namespace ac;
 
-namespace {
-
-template <class Lane>
-struct UkfGroupHost {
-    Lane L[kEkfLanes];
-    template <class F>
-    void each(F f) {
-        for (int r = 0; r < kEkfLanes; ++r) f(L[r], r);
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
 // phase 1: the factor of P, the 25 n points (position rows relative to p^) and the replicated controls
@@ -32,7 +19,7 @@ int host_ukf_sigma(const ac_ukf_opts* o, const float* X, const float* P, const f
     const UkfWeights w = ukf_weights(o->kappa);
     const UkfSigIo io{X, P, U, Xw, Uw, Lw, flag, n};
     for (long i = 0; i < n; ++i) {
-        UkfGroupHost<UkfSigLane> grp{};
+        GroupHost<UkfSigLane, kEkfLanes> grp{};
         UkfSigShared s{};
         ukf_sigma_group(grp, s, w, io, i, true);
     }
@@ -48,7 +35,7 @@ int host_ukf_update(const ac_ukf_opts* o, float eps, const float* X, const float
     const UkfWeights w = ukf_weights(o->kappa);
     const UkfIo io{X, P, Fw, Lw, flag, Z, Qd, Rd, mask, ll_in, Xo, Po, nu, S, nis, ll, used, status, Xpred, Ppred, Abar, n};
     for (long i = 0; i < n; ++i) {
-        UkfGroupHost<UkfLane> grp{};
+        GroupHost<UkfLane, kEkfLanes> grp{};
         UkfShared s{};
         if (o->predict) ukf_update_group<true>(grp, s, *o, w, eps, io, i, true);
         else ukf_update_group<false>(grp, s, *o, w, eps, io, i, true);

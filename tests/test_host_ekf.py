@@ -30,7 +30,7 @@ def lib_host(header=None):
         return _LIBS[key]
     src = os.path.join(HERE, "ekf_host.cpp")
     so = os.path.join(HERE, "libekf_host.so") if header is None else os.path.splitext(header)[0] + ".so"
-    deps = [src, key] + [os.path.join(CSRC, f) for f in ("ac_math.hpp", "ac_dynamics.hpp")]
+    deps = [src, key] + [os.path.join(CSRC, f) for f in ("ac_math.hpp", "ac_group.hpp", "ac_dynamics.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC]
         if header is not None:
@@ -169,7 +169,8 @@ def test_mutated_header_fails(which, tmp_path):
     assert text.count(old) == 1, which
     path = str(tmp_path / f"ac_ekf_{which}.hpp")
     with open(path, "w") as f:
-        f.write(text.replace(old, new).replace('#include "ac_dynamics.hpp"', f'#include "{CSRC}/ac_dynamics.hpp"'))
+        f.write(text.replace(old, new).replace('#include "ac_dynamics.hpp"', f'#include "{CSRC}/ac_dynamics.hpp"')
+                .replace('#include "ac_group.hpp"', f'#include "{CSRC}/ac_group.hpp"'))
     with pytest.raises(AssertionError):
         check(measure("poly", path, cases=("all", "no_gps")))
 

@@ -32,7 +32,7 @@ def lib_host(header=None):
         return _LIBS[key]
     src = os.path.join(HERE, "rts_host.cpp")
     so = os.path.join(HERE, "librts_host.so") if header is None else os.path.splitext(header)[0] + ".so"
-    deps = [src, key] + [os.path.join(CSRC, f) for f in ("ac_math.hpp", "ac_dynamics.hpp", "ac_ekf.hpp")]
+    deps = [src, key] + [os.path.join(CSRC, f) for f in ("ac_math.hpp", "ac_group.hpp", "ac_dynamics.hpp", "ac_ekf.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC]
         if header is not None:
