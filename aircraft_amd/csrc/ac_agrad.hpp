@@ -12,7 +12,8 @@
 //   M = Ma + com x F                           com_bar         += F x M_bar
 // The accumulators, their reduction and the grid are those of the coefficient gradient (ac_cgrad.hpp): one LDS column of 22
 // words per lane in front of the VjpColumn words, columns added per workgroup in a fixed order (cgrad_store_partial), partials
-// added in workgroup order (k_wgrad_reduce).  No floating-point atomics.
+// added in workgroup order (k_wgrad_reduce).  No floating-point atomics.  This header holds the provider (RecAirframe) and the
+// kernels' instantiations; the sweeps themselves are cgrad_step_sweep / cgrad_rollout_sweep of ac_cgrad.hpp.
 #pragma once
 #include "ac_cgrad.hpp"
 
@@ -52,91 +53,23 @@ template <int MODEL, class Sink> struct RecAirframe : AdjAnalyticCoeffs<MODEL> {
 #ifndef AC_HOST_CHECK
 namespace ac {
 
-// Step: X, U, Lam [13|7|13][n] -> partial [gridDim.x][22] and, where the pointers are given, Xbar [13][n], Ubar [7][n],
-// dtbar [n] (k_step_cgrad's sweep with the airframe provider).  Dynamic LDS: cgrad_lane_words(22, ns) floats per lane.
+// The sweeps of ac_cgrad.hpp with the airframe provider: partial [gridDim.x][22]; Xbar / X0bar, Ubar, dtbar nullable.  Dynamic
+// LDS: cgrad_lane_words(22, ns) floats per lane.
 template <int MODEL>
 __global__ __launch_bounds__(kVjpBlock) void k_step_agrad(const DevParams P, const float* __restrict__ X, const float* __restrict__ U,
                                                           float dt, const float* __restrict__ dt_per_unit,
                                                           const float* __restrict__ Lam, long n, float* __restrict__ Xbar,
                                                           float* __restrict__ Ubar, float* __restrict__ dtbar,
                                                           float* __restrict__ partial) {
-    extern __shared__ float ag_lds[];  // [22][kVjpBlock] accumulators, [vjp_lane_words(ns)][kVjpBlock]
-    constexpr int PF = kAgradFloats;
-    float* acc = &ag_lds[threadIdx.x];
-    for (int r = 0; r < PF; ++r) acc[r * kVjpBlock] = 0.f;
-    const VjpColumn col{&ag_lds[PF * kVjpBlock + threadIdx.x], kVjpBlock};
-    RecAirframe<MODEL, CgradColumn> coeffs(CgradColumn{acc, kVjpBlock});
-    const long ntiles = (n + kVjpBlock - 1) / kVjpBlock;
-#pragma nounroll
-    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const long i = tile * kVjpBlock + threadIdx.x;
-        if (i < n) {  // (a mask, not a return: every lane takes part in the column sums below)
-            float x[13], u[7], lam[13], gx[13], gu[7], gdt;
-            load_rows<13>(X, n, i, x);
-            load_rows<7>(U, n, i, u);
-            load_rows<13>(Lam, n, i, lam);
-            const float h = dt_per_unit ? dt_per_unit[i] : dt;
-            step_vjp_unit(P, coeffs, x, u, h, lam, col, gx, gu, gdt);
-            if (Xbar) {
-#pragma unroll
-                for (int r = 0; r < 13; ++r) Xbar[(long)r * n + i] = gx[r];
-            }
-            if (Ubar) {
-#pragma unroll
-                for (int r = 0; r < 7; ++r) Ubar[(long)r * n + i] = gu[r];
-            }
-            if (dtbar) dtbar[i] = gdt;
-        }
-    }
-    cgrad_store_partial<PF>(ag_lds, partial + (long)blockIdx.x * PF);
+    cgrad_step_sweep<kAgradFloats, RecAirframe<MODEL, CgradColumn>>(P, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar, partial);
 }
-
-// Rollout: one lane per instance, lambda in registers across the horizon (k_rollout_cgrad's sweep with the airframe provider).
-// X0bar, Ubar, dtbar nullable.
 template <int MODEL>
 __global__ __launch_bounds__(kVjpBlock) void k_rollout_agrad(const DevParams P, const float* __restrict__ Xtraj,
                                                              const float* __restrict__ U, float dt, long B, long H,
                                                              const float* __restrict__ G, float* __restrict__ X0bar,
                                                              float* __restrict__ Ubar, float* __restrict__ dtbar,
                                                              float* __restrict__ partial) {
-    extern __shared__ float ag_lds[];
-    constexpr int PF = kAgradFloats;
-    float* acc = &ag_lds[threadIdx.x];
-    for (int r = 0; r < PF; ++r) acc[r * kVjpBlock] = 0.f;
-    const VjpColumn col{&ag_lds[PF * kVjpBlock + threadIdx.x], kVjpBlock};
-    RecAirframe<MODEL, CgradColumn> coeffs(CgradColumn{acc, kVjpBlock});
-    const long ntiles = (B + kVjpBlock - 1) / kVjpBlock;
-#pragma nounroll
-    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const long i = tile * kVjpBlock + threadIdx.x;
-        if (i < B) {
-            float lam[13];
-            load_rows<13>(G + H * 13 * B, B, i, lam);
-            float gdt_sum = 0.f;
-#pragma nounroll
-            for (long k = H - 1; k >= 0; --k) {
-                float x[13], u[7], g[13], gx[13], gu[7], gdt;
-                load_rows<13>(Xtraj + k * 13 * B, B, i, x);
-                load_rows<7>(U + k * 7 * B, B, i, u);
-                load_rows<13>(G + k * 13 * B, B, i, g);
-                step_vjp_unit(P, coeffs, x, u, dt, lam, col, gx, gu, gdt);
-                if (Ubar) {
-                    float* ub = Ubar + k * 7 * B;
-#pragma unroll
-                    for (int r = 0; r < 7; ++r) ub[(long)r * B + i] = gu[r];
-                }
-                gdt_sum += gdt;
-#pragma unroll
-                for (int r = 0; r < 13; ++r) lam[r] = g[r] + gx[r];
-            }
-            if (X0bar) {
-#pragma unroll
-                for (int r = 0; r < 13; ++r) X0bar[(long)r * B + i] = lam[r];
-            }
-            if (dtbar) dtbar[i] = gdt_sum;
-        }
-    }
-    cgrad_store_partial<PF>(ag_lds, partial + (long)blockIdx.x * PF);
+    cgrad_rollout_sweep<kAgradFloats, RecAirframe<MODEL, CgradColumn>>(P, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, partial);
 }
 
 // The kernels are compiled in a translation unit of their own (an_inst_agrad.hip); every other unit only refers to them.

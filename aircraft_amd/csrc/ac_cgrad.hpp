@@ -17,6 +17,10 @@
 // conflict-free); after its last tile a workgroup adds the 64 columns of every row in a fixed order into one partial [P] in
 // the caller's workspace, and k_wgrad_reduce adds the partials in workgroup order.  No floating-point atomics: the same
 // inputs on the same grid give the same bits.
+//
+// The persistent sweeps (cgrad_step_sweep, cgrad_rollout_sweep) are templates over the accumulator count and the recording
+// provider: the kernels here and those of the airframe gradient (ac_agrad.hpp) are one call each.  What a lane does per unit is
+// step_vjp_lane / rollout_vjp_lane of ac_vjp.hpp, shared with the plain VJP kernels and the host twins.
 #pragma once
 #include "ac_vjp.hpp"
 
@@ -118,92 +122,69 @@ template <int PF> AC_DI void cgrad_store_partial(const float* lds, float* __rest
     }
 }
 
-// Step: X, U, Lam [13|7|13][n] -> partial [gridDim.x][PF] and, where the pointers are given, Xbar [13][n], Ubar [7][n],
-// dtbar [n].  Persistent over tiles of 64 units (tile = blockIdx.x, + gridDim.x, ...).  Dynamic LDS:
-// cgrad_lane_words(PF, ns) floats per lane.
+// The recording sweeps of one workgroup, persistent over tiles of 64 lanes (tile = blockIdx.x, + gridDim.x, ...): zero this
+// lane's PF accumulators, run the lane body of ac_vjp.hpp with the recording provider Coeffs(CgradColumn) over every unit the
+// lane owns, store the workgroup's partial [PF].  Dynamic LDS: [PF][kVjpBlock] accumulators, then
+// [vjp_lane_words(ns)][kVjpBlock]: cgrad_lane_words(PF, ns) floats per lane.  Shared by the coefficient and the airframe
+// gradient (ac_agrad.hpp); every per-unit output pointer is nullable.
+//
+// Step: X, U, Lam [13|7|13][n] -> partial [gridDim.x][PF], Xbar [13][n], Ubar [7][n], dtbar [n]
+template <int PF, class Coeffs>
+AC_DI void cgrad_step_sweep(const DevParams P, const float* __restrict__ X, const float* __restrict__ U, float dt,
+                            const float* __restrict__ dt_per_unit, const float* __restrict__ Lam, long n,
+                            float* __restrict__ Xbar, float* __restrict__ Ubar, float* __restrict__ dtbar,
+                            float* __restrict__ partial) {
+    extern __shared__ float cg_lds[];
+    float* acc = &cg_lds[threadIdx.x];
+    for (int r = 0; r < PF; ++r) acc[r * kVjpBlock] = 0.f;
+    const VjpColumn col{&cg_lds[PF * kVjpBlock + threadIdx.x], kVjpBlock};
+    Coeffs coeffs(CgradColumn{acc, kVjpBlock});
+    const long ntiles = (n + kVjpBlock - 1) / kVjpBlock;
+#pragma nounroll
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long i = tile * kVjpBlock + threadIdx.x;
+        // (a mask, not a return: every lane takes part in the column sums below)
+        if (i < n) step_vjp_lane(P, coeffs, col, X, U, dt, dt_per_unit, Lam, n, i, Xbar, Ubar, dtbar);
+    }
+    cgrad_store_partial<PF>(cg_lds, partial + (long)blockIdx.x * PF);
+}
+
+// Rollout: one lane per instance (rollout_vjp_lane's layouts and recurrence) -> partial [gridDim.x][PF], X0bar, Ubar, dtbar
+template <int PF, class Coeffs>
+AC_DI void cgrad_rollout_sweep(const DevParams P, const float* __restrict__ Xtraj, const float* __restrict__ U, float dt, long B,
+                               long H, const float* __restrict__ G, float* __restrict__ X0bar, float* __restrict__ Ubar,
+                               float* __restrict__ dtbar, float* __restrict__ partial) {
+    extern __shared__ float cg_lds[];
+    float* acc = &cg_lds[threadIdx.x];
+    for (int r = 0; r < PF; ++r) acc[r * kVjpBlock] = 0.f;
+    const VjpColumn col{&cg_lds[PF * kVjpBlock + threadIdx.x], kVjpBlock};
+    Coeffs coeffs(CgradColumn{acc, kVjpBlock});
+    const long ntiles = (B + kVjpBlock - 1) / kVjpBlock;
+#pragma nounroll
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long i = tile * kVjpBlock + threadIdx.x;
+        if (i < B) rollout_vjp_lane(P, coeffs, col, Xtraj, U, dt, B, H, G, i, X0bar, Ubar, dtbar);
+    }
+    cgrad_store_partial<PF>(cg_lds, partial + (long)blockIdx.x * PF);
+}
+
 template <int MODEL>
 __global__ __launch_bounds__(kVjpBlock) void k_step_cgrad(const DevParams P, const float* __restrict__ X, const float* __restrict__ U,
                                                           float dt, const float* __restrict__ dt_per_unit,
                                                           const float* __restrict__ Lam, long n, float* __restrict__ Xbar,
                                                           float* __restrict__ Ubar, float* __restrict__ dtbar,
                                                           float* __restrict__ partial) {
-    extern __shared__ float cg_lds[];  // [PF][kVjpBlock] accumulators, [vjp_lane_words(ns)][kVjpBlock]
-    constexpr int PF = CgradFloats<MODEL>::value;
-    float* acc = &cg_lds[threadIdx.x];
-    for (int r = 0; r < PF; ++r) acc[r * kVjpBlock] = 0.f;
-    const VjpColumn col{&cg_lds[PF * kVjpBlock + threadIdx.x], kVjpBlock};
-    RecCoeffs<MODEL, CgradColumn> coeffs(CgradColumn{acc, kVjpBlock});
-    const long ntiles = (n + kVjpBlock - 1) / kVjpBlock;
-#pragma nounroll
-    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const long i = tile * kVjpBlock + threadIdx.x;
-        if (i < n) {  // (a mask, not a return: every lane takes part in the column sums below)
-            float x[13], u[7], lam[13], gx[13], gu[7], gdt;
-            load_rows<13>(X, n, i, x);
-            load_rows<7>(U, n, i, u);
-            load_rows<13>(Lam, n, i, lam);
-            const float h = dt_per_unit ? dt_per_unit[i] : dt;
-            step_vjp_unit(P, coeffs, x, u, h, lam, col, gx, gu, gdt);
-            if (Xbar) {
-#pragma unroll
-                for (int r = 0; r < 13; ++r) Xbar[(long)r * n + i] = gx[r];
-            }
-            if (Ubar) {
-#pragma unroll
-                for (int r = 0; r < 7; ++r) Ubar[(long)r * n + i] = gu[r];
-            }
-            if (dtbar) dtbar[i] = gdt;
-        }
-    }
-    cgrad_store_partial<PF>(cg_lds, partial + (long)blockIdx.x * PF);
+    cgrad_step_sweep<CgradFloats<MODEL>::value, RecCoeffs<MODEL, CgradColumn>>(P, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar,
+                                                                               partial);
 }
-
-// Rollout: one lane per instance, lambda in registers across the horizon (k_rollout_vjp's layout and recurrence), persistent
-// over tiles of 64 instances.  X0bar, Ubar, dtbar nullable.
 template <int MODEL>
 __global__ __launch_bounds__(kVjpBlock) void k_rollout_cgrad(const DevParams P, const float* __restrict__ Xtraj,
                                                              const float* __restrict__ U, float dt, long B, long H,
                                                              const float* __restrict__ G, float* __restrict__ X0bar,
                                                              float* __restrict__ Ubar, float* __restrict__ dtbar,
                                                              float* __restrict__ partial) {
-    extern __shared__ float cg_lds[];
-    constexpr int PF = CgradFloats<MODEL>::value;
-    float* acc = &cg_lds[threadIdx.x];
-    for (int r = 0; r < PF; ++r) acc[r * kVjpBlock] = 0.f;
-    const VjpColumn col{&cg_lds[PF * kVjpBlock + threadIdx.x], kVjpBlock};
-    RecCoeffs<MODEL, CgradColumn> coeffs(CgradColumn{acc, kVjpBlock});
-    const long ntiles = (B + kVjpBlock - 1) / kVjpBlock;
-#pragma nounroll
-    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const long i = tile * kVjpBlock + threadIdx.x;
-        if (i < B) {
-            float lam[13];
-            load_rows<13>(G + H * 13 * B, B, i, lam);
-            float gdt_sum = 0.f;
-#pragma nounroll
-            for (long k = H - 1; k >= 0; --k) {
-                float x[13], u[7], g[13], gx[13], gu[7], gdt;
-                load_rows<13>(Xtraj + k * 13 * B, B, i, x);
-                load_rows<7>(U + k * 7 * B, B, i, u);
-                load_rows<13>(G + k * 13 * B, B, i, g);
-                step_vjp_unit(P, coeffs, x, u, dt, lam, col, gx, gu, gdt);
-                if (Ubar) {
-                    float* ub = Ubar + k * 7 * B;
-#pragma unroll
-                    for (int r = 0; r < 7; ++r) ub[(long)r * B + i] = gu[r];
-                }
-                gdt_sum += gdt;
-#pragma unroll
-                for (int r = 0; r < 13; ++r) lam[r] = g[r] + gx[r];
-            }
-            if (X0bar) {
-#pragma unroll
-                for (int r = 0; r < 13; ++r) X0bar[(long)r * B + i] = lam[r];
-            }
-            if (dtbar) dtbar[i] = gdt_sum;
-        }
-    }
-    cgrad_store_partial<PF>(cg_lds, partial + (long)blockIdx.x * PF);
+    cgrad_rollout_sweep<CgradFloats<MODEL>::value, RecCoeffs<MODEL, CgradColumn>>(P, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar,
+                                                                                  partial);
 }
 
 // out[i] = partial[0][i] + partial[1][i] + ... in that order (defined with the weight gradient, ac_wgrad.hpp)

@@ -1281,4 +1281,14 @@ AC_DI void rk4_step_seeded(const DevParams& P, Coeffs& coeffs, int g, const floa
     rk4_step_seeded<N>(P, coeffs, g, xv, uv, hv, dh_ddt, xo, acc);
 }
 
+// Unit i of a component-major array [ROWS][n] (the kernels' layout; host-compilable for the lane bodies of ac_vjp.hpp)
+template <int ROWS> AC_DI void load_rows(const float* __restrict__ src, long n, long i, float out[ROWS]) {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) out[r] = src[(long)r * n + i];
+}
+template <int ROWS> AC_DI void store_rows(float* __restrict__ dst, long n, long i, const float v[ROWS]) {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) dst[(long)r * n + i] = v[r];
+}
+
 }  // namespace ac

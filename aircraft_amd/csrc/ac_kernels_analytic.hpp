@@ -66,11 +66,7 @@ AC_DI void store_state_rows(const DevParams& P, const float* __restrict__ X, flo
     }
     store_rows<13>(out, ua, r);
 }
-// flat [ROWS][n] helper used by the rollout kernels
-template <int ROWS> AC_DI void load_rows(const float* __restrict__ src, long n, long i, float out[ROWS]) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) out[r] = src[(long)r * n + i];
-}
+// (the flat [ROWS][n] load_rows / store_rows of the rollout kernels: ac_dynamics.hpp)
 
 // ---- forward kernels: one lane per unit ------------------------------------------------------
 template <int MODEL>

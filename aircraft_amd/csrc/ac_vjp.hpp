@@ -14,6 +14,11 @@
 // each from the fp32 rounding of the carry, and normalises the quaternion ONCE after the last one.  The reverse sweep re-runs
 // that forward pass, keeps the ns sub-step inputs (this lane's column of an LDS array, 13 ns floats) and pulls lambda back
 // through them in reverse order; the normalisation adjoint enters the last sub-step only (rk4_vjp's norm_adj).
+//
+// What is shared, and where: step_vjp_unit is the sweep of one unit; step_vjp_lane / rollout_vjp_lane (below, host-compilable)
+// are what one lane does around it (load x, u, lambda; sweep; store; the rollout's recurrence).  k_step_vjp / k_rollout_vjp,
+// the coefficient gradient (ac_cgrad.hpp) and the airframe gradient (ac_agrad.hpp) all call the lane bodies with their own
+// coefficient provider, and so do the host twins under tests/host_{vjp,cgrad,agrad}.
 #pragma once
 #include "ac_adjoint.hpp"
 
@@ -108,11 +113,63 @@ AC_DI void step_vjp_unit(const DevParams& P, Coeffs& coeffs, const float x[13], 
     }
     gdt = (ns == 1) ? gh : gh * (1.0f / (float)ns);  // h = dt / ns
 }
+// ... with the plain provider of an analytic model
 template <int MODEL>
 AC_DI void step_vjp_unit(const DevParams& P, const float x[13], const float u[7], float dt, const float lam[13],
                          const VjpColumn& col, float gx[13], float gu[7], float& gdt) {
     AdjAnalyticCoeffs<MODEL> coeffs;
     step_vjp_unit(P, coeffs, x, u, dt, lam, col, gx, gu, gdt);
+}
+
+// ---- lane bodies: what one lane of the fused kernels does, in plain pointers and an index ----------------------------------
+// (no threadIdx: the kernels below, ac_cgrad.hpp and ac_agrad.hpp pass their lane's unit and LDS column, the host twins under
+// tests/ pass n-strided arrays and a stride-1 column, so `pytest -m "not gpu"` runs this very code)
+// Every output pointer is nullable: an output that is not asked for is not written; OUT_ALL: the caller guarantees Xbar / X0bar
+// and Ubar (the plain VJP kernels: no null tests inside the horizon loop).  P by value: with a reference hipcc takes
+// k_step_vjp from 239 to 256 VGPRs (linear) and to 256 + 5 AGPRs (default), 2 -> 1 waves per SIMD, for the same work.
+//
+// Step, unit i of X, U, Lam [13|7|13][n] -> Xbar [13][n], Ubar [7][n], dtbar [n]
+template <bool OUT_ALL = false, class Coeffs>
+AC_DI void step_vjp_lane(const DevParams P, Coeffs& coeffs, const VjpColumn& col, const float* __restrict__ X,
+                         const float* __restrict__ U, float dt, const float* __restrict__ dt_per_unit,
+                         const float* __restrict__ Lam, long n, long i, float* __restrict__ Xbar, float* __restrict__ Ubar,
+                         float* __restrict__ dtbar) {
+    float x[13], u[7], lam[13], gx[13], gu[7], gdt;
+    load_rows<13>(X, n, i, x);
+    load_rows<7>(U, n, i, u);
+    load_rows<13>(Lam, n, i, lam);
+    const float h = dt_per_unit ? dt_per_unit[i] : dt;
+    step_vjp_unit(P, coeffs, x, u, h, lam, col, gx, gu, gdt);
+    if (OUT_ALL || Xbar) store_rows<13>(Xbar, n, i, gx);
+    if (OUT_ALL || Ubar) store_rows<7>(Ubar, n, i, gu);
+    if (dtbar) dtbar[i] = gdt;
+}
+
+// Rollout, instance i, lambda in registers across the horizon:
+//   lambda_H = G_H;  lambda_k = G_k + A_k' lambda_{k+1},  Ubar_k = B_k' lambda_{k+1},  dtbar = sum_k c_k . lambda_{k+1}
+//   Xtraj [H+1][13][B] (the forward trajectory, ac_rollout_f32's layout), U [H][7][B], G [H+1][13][B] (dLoss/dX[k])
+//   -> X0bar [13][B], Ubar [H][7][B], dtbar [B]
+template <bool OUT_ALL = false, class Coeffs>
+AC_DI void rollout_vjp_lane(const DevParams P, Coeffs& coeffs, const VjpColumn& col, const float* __restrict__ Xtraj,
+                            const float* __restrict__ U, float dt, long B, long H, const float* __restrict__ G, long i,
+                            float* __restrict__ X0bar, float* __restrict__ Ubar, float* __restrict__ dtbar) {
+    float lam[13];
+    load_rows<13>(G + H * 13 * B, B, i, lam);
+    float gdt_sum = 0.f;
+#pragma nounroll
+    for (long k = H - 1; k >= 0; --k) {
+        float x[13], u[7], g[13], gx[13], gu[7], gdt;
+        load_rows<13>(Xtraj + k * 13 * B, B, i, x);
+        load_rows<7>(U + k * 7 * B, B, i, u);
+        load_rows<13>(G + k * 13 * B, B, i, g);
+        step_vjp_unit(P, coeffs, x, u, dt, lam, col, gx, gu, gdt);
+        if (OUT_ALL || Ubar) store_rows<7>(Ubar + k * 7 * B, B, i, gu);
+        gdt_sum += gdt;
+#pragma unroll
+        for (int r = 0; r < 13; ++r) lam[r] = g[r] + gx[r];
+    }
+    if (OUT_ALL || X0bar) store_rows<13>(X0bar, B, i, lam);
+    if (dtbar) dtbar[i] = gdt_sum;
 }
 
 // f itself pulled back:  gx = (df/dx)' w,  gu = (df/du)' w
@@ -145,23 +202,11 @@ __global__ __launch_bounds__(kVjpBlock) void k_step_vjp(const DevParams P, const
     extern __shared__ float vjp_lds[];  // [vjp_lane_words(ns)][kVjpBlock]
     const long i = (long)blockIdx.x * kVjpBlock + threadIdx.x;
     if (i >= n) return;  // (no barrier below: every lane owns its LDS column)
-    float x[13], u[7], lam[13], gx[13], gu[7], gdt;
-    load_rows<13>(X, n, i, x);
-    load_rows<7>(U, n, i, u);
-    load_rows<13>(Lam, n, i, lam);
-    const float h = dt_per_unit ? dt_per_unit[i] : dt;
-    const VjpColumn col{&vjp_lds[threadIdx.x], kVjpBlock};
-    step_vjp_unit<MODEL>(P, x, u, h, lam, col, gx, gu, gdt);
-#pragma unroll
-    for (int r = 0; r < 13; ++r) Xbar[(long)r * n + i] = gx[r];
-#pragma unroll
-    for (int r = 0; r < 7; ++r) Ubar[(long)r * n + i] = gu[r];
-    if (dtbar) dtbar[i] = gdt;
+    AdjAnalyticCoeffs<MODEL> coeffs;
+    step_vjp_lane<true>(P, coeffs, VjpColumn{&vjp_lds[threadIdx.x], kVjpBlock}, X, U, dt, dt_per_unit, Lam, n, i, Xbar, Ubar, dtbar);
 }
 
-// Rollout: one lane per instance, lambda in registers across the horizon.
-//   Xtraj [H+1][13][B] (the forward trajectory, ac_rollout_f32's layout), U [H][7][B], G [H+1][13][B] (dLoss/dX[k])
-//   -> X0bar [13][B], Ubar [H][7][B], dtbar [B] (nullable; the sum over the nodes of c_k . lambda_{k+1})
+// Rollout: one lane per instance (rollout_vjp_lane's layouts); dtbar nullable.
 template <int MODEL>
 __global__ __launch_bounds__(kVjpBlock) void k_rollout_vjp(const DevParams P, const float* __restrict__ Xtraj,
                                                            const float* __restrict__ U, float dt, long B, long H,
@@ -170,27 +215,8 @@ __global__ __launch_bounds__(kVjpBlock) void k_rollout_vjp(const DevParams P, co
     extern __shared__ float vjp_lds[];  // [vjp_lane_words(ns)][kVjpBlock]
     const long i = (long)blockIdx.x * kVjpBlock + threadIdx.x;
     if (i >= B) return;
-    const VjpColumn col{&vjp_lds[threadIdx.x], kVjpBlock};
-    float lam[13];
-    load_rows<13>(G + H * 13 * B, B, i, lam);
-    float gdt_sum = 0.f;
-#pragma nounroll
-    for (long k = H - 1; k >= 0; --k) {
-        float x[13], u[7], g[13], gx[13], gu[7], gdt;
-        load_rows<13>(Xtraj + k * 13 * B, B, i, x);
-        load_rows<7>(U + k * 7 * B, B, i, u);
-        load_rows<13>(G + k * 13 * B, B, i, g);
-        step_vjp_unit<MODEL>(P, x, u, dt, lam, col, gx, gu, gdt);
-        float* ub = Ubar + k * 7 * B;
-#pragma unroll
-        for (int r = 0; r < 7; ++r) ub[(long)r * B + i] = gu[r];
-        gdt_sum += gdt;
-#pragma unroll
-        for (int r = 0; r < 13; ++r) lam[r] = g[r] + gx[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 13; ++r) X0bar[(long)r * B + i] = lam[r];
-    if (dtbar) dtbar[i] = gdt_sum;
+    AdjAnalyticCoeffs<MODEL> coeffs;
+    rollout_vjp_lane<true>(P, coeffs, VjpColumn{&vjp_lds[threadIdx.x], kVjpBlock}, Xtraj, U, dt, B, H, G, i, X0bar, Ubar, dtbar);
 }
 
 // f: X, U, W [13|7|13][n] -> Xbar [13][n], Ubar [7][n]
@@ -205,10 +231,8 @@ __global__ __launch_bounds__(kBlock) void k_deriv_vjp(const DevParams P, const f
     load_rows<7>(U, n, i, u);
     load_rows<13>(W, n, i, w);
     deriv_vjp_unit<MODEL>(P, x, u, w, gx, gu);
-#pragma unroll
-    for (int r = 0; r < 13; ++r) Xbar[(long)r * n + i] = gx[r];
-#pragma unroll
-    for (int r = 0; r < 7; ++r) Ubar[(long)r * n + i] = gu[r];
+    store_rows<13>(Xbar, n, i, gx);
+    store_rows<7>(Ubar, n, i, gu);
 }
 
 // ---- composed: Jacobians from the sensitivity kernels, then lambda applied --------------------------------------------------
@@ -220,6 +244,20 @@ __global__ void k_vjp_recur(const float* __restrict__ A, const float* __restrict
                             const float* __restrict__ G, long B, long H, float* __restrict__ X0bar, float* __restrict__ Ubar,
                             float* __restrict__ dtbar, float* __restrict__ LamTraj);
 #ifdef AC_VJP_INSTANTIATE
+// gx += A' lam, gu += B' lam, gdt += c . lam for unit i of A [13][13][n], Bm [13][7][n], c [13][n] (C_NULLABLE: may be NULL)
+template <bool C_NULLABLE>
+AC_DI void jac_transpose_apply(const float* __restrict__ A, const float* __restrict__ Bm, const float* __restrict__ c, long n,
+                               long i, const float lam[13], float gx[13], float gu[7], float& gdt) {
+#pragma unroll 1
+    for (int r = 0; r < 13; ++r) {
+#pragma unroll
+        for (int j = 0; j < 13; ++j) gx[j] = fmaf(A[(long)(r * 13 + j) * n + i], lam[r], gx[j]);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) gu[j] = fmaf(Bm[(long)(r * 7 + j) * n + i], lam[r], gu[j]);
+        if (!C_NULLABLE || c) gdt = fmaf(c[(long)r * n + i], lam[r], gdt);
+    }
+}
+
 // One unit per lane:  Xbar = A' lam, Ubar = B' lam, dtbar = c . lam  (c, dtbar nullable).  A [13][13][n], Bm [13][7][n],
 // c [13][n] (ac_step_sens_f32's layout; Fx / Fu of ac_state_derivative_sens_f32 with c = NULL).
 __global__ __launch_bounds__(kBlock) void k_vjp_contract(const float* __restrict__ A, const float* __restrict__ Bm,
@@ -230,23 +268,10 @@ __global__ __launch_bounds__(kBlock) void k_vjp_contract(const float* __restrict
     if (i >= n) return;
     float lam[13];
     load_rows<13>(Lam, n, i, lam);
-    float gx[13], gu[7], gdt = 0.f;
-#pragma unroll
-    for (int j = 0; j < 13; ++j) gx[j] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) gu[j] = 0.f;
-#pragma unroll 1
-    for (int r = 0; r < 13; ++r) {
-#pragma unroll
-        for (int j = 0; j < 13; ++j) gx[j] = fmaf(A[(long)(r * 13 + j) * n + i], lam[r], gx[j]);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) gu[j] = fmaf(Bm[(long)(r * 7 + j) * n + i], lam[r], gu[j]);
-        if (c) gdt = fmaf(c[(long)r * n + i], lam[r], gdt);
-    }
-#pragma unroll
-    for (int j = 0; j < 13; ++j) Xbar[(long)j * n + i] = gx[j];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) Ubar[(long)j * n + i] = gu[j];
+    float gx[13] = {}, gu[7] = {}, gdt = 0.f;
+    jac_transpose_apply<true>(A, Bm, c, n, i, lam, gx, gu, gdt);
+    store_rows<13>(Xbar, n, i, gx);
+    store_rows<7>(Ubar, n, i, gu);
     if (dtbar) dtbar[i] = gdt;
 }
 
@@ -264,33 +289,16 @@ __global__ __launch_bounds__(kBlock) void k_vjp_recur(const float* __restrict__ 
     load_rows<13>(G + H * 13 * B, B, i, lam);
     float gdt = 0.f;
     for (long k = H - 1; k >= 0; --k) {
-        if (LamTraj) {  // (the weight gradient's units are (X_k, U_k, lambda_{k+1}), ac_wgrad.hpp)
-#pragma unroll
-            for (int j = 0; j < 13; ++j) LamTraj[(k * 13 + j) * B + i] = lam[j];
-        }
-        const float* Ak = A + k * 169 * B;
-        const float* Bk = Bm + k * 91 * B;
-        const float* ck = c + k * 13 * B;
-        float gx[13], gu[7];
+        // (the weight gradient's units are (X_k, U_k, lambda_{k+1}), ac_wgrad.hpp)
+        if (LamTraj) store_rows<13>(LamTraj + k * 13 * B, B, i, lam);
+        float gx[13], gu[7] = {};
         load_rows<13>(G + k * 13 * B, B, i, gx);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) gu[j] = 0.f;
-#pragma unroll 1
-        for (int r = 0; r < 13; ++r) {
-#pragma unroll
-            for (int j = 0; j < 13; ++j) gx[j] = fmaf(Ak[(long)(r * 13 + j) * B + i], lam[r], gx[j]);
-#pragma unroll
-            for (int j = 0; j < 7; ++j) gu[j] = fmaf(Bk[(long)(r * 7 + j) * B + i], lam[r], gu[j]);
-            gdt = fmaf(ck[(long)r * B + i], lam[r], gdt);
-        }
-        float* ub = Ubar + k * 7 * B;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) ub[(long)j * B + i] = gu[j];
+        jac_transpose_apply<false>(A + k * 169 * B, Bm + k * 91 * B, c + k * 13 * B, B, i, lam, gx, gu, gdt);
+        store_rows<7>(Ubar + k * 7 * B, B, i, gu);
 #pragma unroll
         for (int j = 0; j < 13; ++j) lam[j] = gx[j];
     }
-#pragma unroll
-    for (int j = 0; j < 13; ++j) X0bar[(long)j * B + i] = lam[j];
+    store_rows<13>(X0bar, B, i, lam);
     if (dtbar) dtbar[i] = gdt;
 }
 

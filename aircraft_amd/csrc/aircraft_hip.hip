@@ -242,10 +242,10 @@ template <class F> void with_analytic_model(const ac_handle* h, F&& f) {
     }
 }
 
-// One launch of an NN kernel: raise the kernel's dynamic-LDS limit, launch, record the launch for ac_last_launch when a
-// name is given, and return the launch status.
+// One launch of a kernel with dynamic LDS (the NN kernels, the fused reverse sweeps): raise the kernel's dynamic-LDS limit,
+// launch, record the launch for ac_last_launch when a name is given, and return the launch status.
 template <class K, class... Args>
-int launch_nn(ac_handle* h, hipStream_t st, const char* name, K kern, int grid, int block, int lds, const Args&... args) {
+int launch_kernel(ac_handle* h, hipStream_t st, const char* name, K kern, int grid, int block, int lds, const Args&... args) {
     const int rc = set_lds_limit(h, kern, lds);
     if (rc != AC_OK) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
@@ -270,6 +270,12 @@ template <class F> int pick_wt_mfma(const ac_handle* h, F&& f) {
     return pick<2, 4, 8>(h->wt, [&](auto WT) { return h->use_mfma ? f(WT, std::true_type{}) : f(WT, std::false_type{}); });
 }
 int instance(int rc, const char* missing) { return rc == kNoInstance ? fail(AC_ERR_UNSUPPORTED, missing) : rc; }
+// ... over the models of the fused reverse sweeps (ac_vjp.hpp): f(MODEL).  The callers' route and refusal checks have excluded
+// the MLP surrogate and the quadrotor.
+template <class F> int pick_fused_model(const ac_handle* h, F&& f) {
+    return instance(pick<AC_MODEL_DEFAULT, AC_MODEL_LINEAR, AC_MODEL_POLY>(h->dp.p.model_kind, f),
+                    "no fused reverse sweep for this model");
+}
 
 // The plan of the kernels on MlpEngine (sensitivity and forward): the matrix-core flavour runs its edge layers on the vector
 // ALUs and takes plan_sens; the cross-lane validation flavour keeps plan.  (The second-order and the cooperative rollout
@@ -311,6 +317,129 @@ int filter_loop(const char* name, bool predict, Step step, float* const buf[4], 
         pin = po;
     }
     return AC_OK;
+}
+
+// ---- reverse mode to parameters (ac_cgrad.hpp, ac_agrad.hpp): one recording sweep and one set of entry points; a descriptor
+// says what is recorded ----------------------------------------------------------------------------------------------------------
+int cgrad_floats_of(const ac_handle* h) {
+    const int mk = h->dp.p.model_kind;
+    return mk == AC_MODEL_POLY ? CgradFloats<AC_MODEL_POLY>::value : (mk == AC_MODEL_LINEAR ? CgradFloats<AC_MODEL_LINEAR>::value : 0);
+}
+// why the coefficient gradient cannot run on this handle (nullptr: it can); sets *code
+const char* cgrad_refusal(const ac_handle* h, int* code) {
+    *code = AC_ERR_UNSUPPORTED;
+    if (!cgrad_floats_of(h)) return "coefficient gradients exist for the cubic-fit (poly) and the linear model only";
+    if (model_ready(h) != AC_OK) { *code = AC_ERR_NO_MODEL; return "no coefficients installed: call ac_set_poly / ac_set_linear first"; }
+    if (h->dp.p.substeps > kCgradMaxSubsteps)
+        return "coefficient gradients: at most 30 RK4 sub-steps (240 + 13 sub-steps <= 640 words of LDS per lane)";
+    return nullptr;
+}
+// why the airframe gradient cannot run on this handle (nullptr: it can); sets *code
+const char* agrad_refusal(const ac_handle* h, int* code) {
+    *code = AC_ERR_UNSUPPORTED;
+    const int mk = h->dp.p.model_kind;
+    if (mk == AC_MODEL_NN) return "airframe gradients: the MLP surrogate has no fused reverse sweep (default, linear and cubic-fit models only)";
+    if (mk == AC_MODEL_QUAD) return "airframe gradients: the quadrotor's sweep is not recorded (default, linear and cubic-fit models only)";
+    if (model_ready(h) != AC_OK) { *code = AC_ERR_NO_MODEL; return "no coefficients installed: call ac_set_poly / ac_set_linear first"; }
+    if (h->dp.p.substeps > kAgradMaxSubsteps) return "airframe gradients: at most 40 RK4 sub-steps (the limit of the fused reverse sweep)";
+    return nullptr;
+}
+
+// What a parameter gradient records: its refusal, the gradient length on this handle, the workspace message, and its kernels
+// by model (with_model: pick over the models it is instantiated for).
+struct CoefGrad {
+    static constexpr auto refusal = cgrad_refusal;
+    static int floats(const ac_handle* h) { return cgrad_floats_of(h); }
+    static constexpr const char* kWorkspace = "coefficient-gradient workspace too small: see ac_cgrad_workspace_floats";
+    static constexpr const char* kStep = "k_step_cgrad";
+    static constexpr const char* kRollout = "k_rollout_cgrad";
+    template <class F> static int with_model(const ac_handle* h, F&& f) {
+        return instance(pick<AC_MODEL_LINEAR, AC_MODEL_POLY>(h->dp.p.model_kind, f), "no coefficient-gradient kernel for this model");
+    }
+    template <int M> static auto step_kernel() { return k_step_cgrad<M>; }
+    template <int M> static auto rollout_kernel() { return k_rollout_cgrad<M>; }
+};
+struct AirframeGrad {
+    static constexpr auto refusal = agrad_refusal;
+    static int floats(const ac_handle*) { return kAgradFloats; }
+    static constexpr const char* kWorkspace = "airframe-gradient workspace too small: see ac_agrad_workspace_floats";
+    static constexpr const char* kStep = "k_step_agrad";
+    static constexpr const char* kRollout = "k_rollout_agrad";
+    template <class F> static int with_model(const ac_handle* h, F&& f) { return pick_fused_model(h, f); }
+    template <int M> static auto step_kernel() { return k_step_agrad<M>; }
+    template <int M> static auto rollout_kernel() { return k_rollout_agrad<M>; }
+};
+
+template <class D> int pgrad_lds_bytes(const ac_handle* h) {
+    return cgrad_lane_words(D::floats(h), h->dp.p.substeps) * kVjpBlock * (int)sizeof(float);
+}
+// Workgroups of a launch over `units` lanes: one per tile of 64 up to the handle's cap — the CU count read at creation times
+// the workgroups whose LDS fits one CU (at most 8), or ac_set_cgrad_grid's value.  Never the runtime's occupancy: the same
+// inputs on the same handle give the same partials.
+template <class D> int pgrad_grid_of(const ac_handle* h, long units) {
+    const long tiles = (units + kVjpBlock - 1) / kVjpBlock;
+    long cap = h->cgrad_grid;
+    if (cap <= 0) {
+        const long per_cu = std::max(1, std::min(8, 160 * 1024 / pgrad_lds_bytes<D>(h)));
+        cap = (h->num_cus > 0 ? h->num_cus : 256) * per_cu;
+    }
+    return (int)std::max<long>(1, std::min(tiles, cap));
+}
+
+template <class D> int pgrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats) {
+    if (!h || !floats || n_or_B < 0 || H < 0 || which < AC_CGRAD_STEP || which > AC_CGRAD_ROLLOUT) return AC_ERR_BAD_ARG;
+    g_err[0] = 0;
+    int code;
+    if (const char* why = D::refusal(h, &code)) return fail(code, why);
+    *floats = (size_t)pgrad_grid_of<D>(h, n_or_B) * (size_t)D::floats(h);
+    return AC_OK;
+}
+
+// The sweep `kern` over `units` lanes with its partials in ws, then the F floats of the partials added in workgroup order
+template <class D, class K, class... Args>
+int pgrad_sweep(ac_handle* h, hipStream_t st, const char* name, K kern, long units, float* out, float* ws, size_t ws_floats,
+                const Args&... args) {
+    const int grid = pgrad_grid_of<D>(h, units), lds = pgrad_lds_bytes<D>(h), F = D::floats(h);
+    if (!ws || ws_floats < (size_t)grid * (size_t)F) return fail(AC_ERR_WORKSPACE, D::kWorkspace);
+    const int rc = D::with_model(h, [&](auto M) { return launch_kernel(h, st, name, kern(M), grid, kVjpBlock, lds, h->dp, args..., ws); });
+    if (rc != AC_OK) return rc;
+    hipLaunchKernelGGL(k_wgrad_reduce, (F + kBlock - 1) / kBlock, kBlock, 0, st, (const float*)ws, grid, F, out);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+
+template <class D>
+int pgrad_step(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
+               float* Xbar, float* Ubar, float* dtbar, float* out, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !out || n < 0 || (n > 0 && (!X || !U || !Lam))) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = D::refusal(h, &code)) return fail(code, why);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        AC_HIP(hipMemsetAsync(out, 0, (size_t)D::floats(h) * sizeof(float), st));
+        return AC_OK;
+    }
+    return pgrad_sweep<D>(h, st, D::kStep, [](auto M) { return D::template step_kernel<M()>(); }, n, out, ws, ws_floats, X, U, dt,
+                          dt_per_unit, Lam, n, Xbar, Ubar, dtbar);
+}
+
+template <class D>
+int pgrad_rollout(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
+                  float* Ubar, float* dtbar, float* out, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (!h || !out || B < 0 || H < 0 || (B > 0 && (!Xtraj || !G || (H > 0 && !U)))) return AC_ERR_BAD_ARG;
+    int code;
+    if (const char* why = D::refusal(h, &code)) return fail(code, why);
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0 || H == 0) {  // no step, no parameter enters; X[0] = x0: the cotangent passes through
+        AC_HIP(hipMemsetAsync(out, 0, (size_t)D::floats(h) * sizeof(float), st));
+        if (B > 0 && X0bar) AC_HIP(hipMemcpyAsync(X0bar, G, (size_t)B * 13 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (B > 0 && dtbar) AC_HIP(hipMemsetAsync(dtbar, 0, (size_t)B * sizeof(float), st));
+        return AC_OK;
+    }
+    return pgrad_sweep<D>(h, st, D::kRollout, [](auto M) { return D::template rollout_kernel<M()>(); }, B, out, ws, ws_floats, Xtraj,
+                          U, dt, B, H, G, X0bar, Ubar, dtbar);
 }
 
 }  // namespace
@@ -482,7 +611,7 @@ static int launch_nn_fwd(ac_handle* h, int op, const float* X, const float* U, f
         return instance(pick<OP_DERIV, OP_STEP, OP_AERO>(op, [&](auto o) {
             constexpr int OP = o;
             return pick<32, 64>(h->vwidth, [&](auto W) {
-                return launch_nn(h, st, name("k_nn_fwd_tiled<deriv>", "k_nn_fwd_tiled<step>", "k_nn_fwd_tiled<aero>"),
+                return launch_kernel(h, st, name("k_nn_fwd_tiled<deriv>", "k_nn_fwd_tiled<step>", "k_nn_fwd_tiled<aero>"),
                                  k_nn_fwd_tiled<W(), OP>, grid, kBlock, lds, h->dp, h->vplan, h->d_vblob, X, U, dt, dtp, n, blk, out);
             });
         }), kNoTiledInstance);
@@ -510,7 +639,7 @@ static int launch_nn_fwd(ac_handle* h, int op, const float* X, const float* U, f
         const int rc = instance(pick<OP_DERIV, OP_STEP, OP_AERO>(op, [&](auto o) {
             constexpr int OP = o;
             return pick<2, 4, 8>(h->wt, [&](auto WT) {
-                return launch_nn(h, st, name("k_nn_fwd4<deriv>", "k_nn_fwd4<step>", "k_nn_fwd4<aero>"), k_nn_fwd4<WT(), OP>, grid4,
+                return launch_kernel(h, st, name("k_nn_fwd4<deriv>", "k_nn_fwd4<step>", "k_nn_fwd4<aero>"), k_nn_fwd4<WT(), OP>, grid4,
                                  kBlock, plan.lds_total, h->dp, plan, h->d_blob, X, U, dt, dtp, n4, blk, out, zero);
             });
         }), kNoNnInstance);
@@ -520,7 +649,7 @@ static int launch_nn_fwd(ac_handle* h, int op, const float* X, const float* U, f
     return instance(pick<OP_DERIV, OP_STEP, OP_AERO>(op, [&](auto o) {
         constexpr int OP = o;
         return pick_wt_mfma(h, [&](auto WT, auto MF) {  // (ac_last_launch keeps k_nn_fwd4 when it ran)
-            return launch_nn(h, st, n4 == 0 ? name("k_nn_fwd<deriv>", "k_nn_fwd<step>", "k_nn_fwd<aero>") : nullptr,
+            return launch_kernel(h, st, n4 == 0 ? name("k_nn_fwd<deriv>", "k_nn_fwd<step>", "k_nn_fwd<aero>") : nullptr,
                              k_nn_fwd<WT(), MF(), OP>, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob, X, U, dt, dtp, n, blk, out, n4);
         });
     }), kNoNnInstance);
@@ -651,7 +780,7 @@ int ac_rollout_f32(ac_handle* h, const float* X0, const float* U, float dt, long
         const int grid = (int)((B + 4 * roll_units - 1) / (4 * roll_units));
         const int lds = h->vplan.image_floats * 4 + 4 * (int)roll_units * (h->vwidth + 4) * 4;
         return instance(pick<32, 64>(h->vwidth, [&](auto W) {
-            return launch_nn(h, st, "k_nn_rollout_tiled8", k_nn_rollout_tiled8<W()>, grid, kBlock, lds, h->dp, h->vplan, h->d_vblob,
+            return launch_kernel(h, st, "k_nn_rollout_tiled8", k_nn_rollout_tiled8<W()>, grid, kBlock, lds, h->dp, h->vplan, h->d_vblob,
                              X0, U, dt, B, H, Xout);
         }), kNoTiledInstance);
     }
@@ -659,7 +788,7 @@ int ac_rollout_f32(ac_handle* h, const float* X0, const float* U, float dt, long
         const int grid = (int)((B + kBlock - 1) / kBlock);
         const int lds = h->vplan.image_floats * 4 + 4 * 64 * (h->vwidth + 4) * 4;
         return instance(pick<32, 64>(h->vwidth, [&](auto W) {
-            return launch_nn(h, st, "k_nn_rollout_tiled", k_nn_rollout_tiled<W()>, grid, kBlock, lds, h->dp, h->vplan, h->d_vblob,
+            return launch_kernel(h, st, "k_nn_rollout_tiled", k_nn_rollout_tiled<W()>, grid, kBlock, lds, h->dp, h->vplan, h->d_vblob,
                              X0, U, dt, B, H, Xout);
         }), kNoTiledInstance);
     }
@@ -673,7 +802,7 @@ int ac_rollout_f32(ac_handle* h, const float* X0, const float* U, float dt, long
             return instance(pick<2, 4, 8>(h->wt, [&](auto wt) {
                 constexpr int WT = wt;
                 return pick<1, 2, 3>(nh, [&](auto NH) {
-                    return launch_nn(h, st, "k_nn_rollout_reg", k_nn_rollout_reg<WT, NH()>, grid, kBlock, lds, h->dp, h->plan,
+                    return launch_kernel(h, st, "k_nn_rollout_reg", k_nn_rollout_reg<WT, NH()>, grid, kBlock, lds, h->dp, h->plan,
                                      h->d_blob, X0, U, dt, B, H, Xout);
                 });
             }), kNoNnInstance);
@@ -683,14 +812,14 @@ int ac_rollout_f32(ac_handle* h, const float* X0, const float* U, float dt, long
             const int grid = (int)groups;
             const int lds = h->plan.lds_total + h->wt * 1024;  // + the activation exchange buffer
             return instance(pick<2, 4, 8>(h->wt, [&](auto WT) {
-                return launch_nn(h, st, "k_nn_rollout_coop", k_nn_rollout_coop<WT(), true>, grid, kBlock, lds, h->dp, h->plan,
+                return launch_kernel(h, st, "k_nn_rollout_coop", k_nn_rollout_coop<WT(), true>, grid, kBlock, lds, h->dp, h->plan,
                                  h->d_blob, X0, U, dt, B, H, Xout);
             }), kNoNnInstance);
         }
         const int grid = (int)((groups + 3) / 4);
         const MlpPlan& plan = engine_plan(h);
         return instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
-            return launch_nn(h, st, "k_nn_rollout", k_nn_rollout<WT(), MF()>, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob,
+            return launch_kernel(h, st, "k_nn_rollout", k_nn_rollout<WT(), MF()>, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob,
                              X0, U, dt, B, H, Xout);
         }), kNoNnInstance);
     }
@@ -723,7 +852,7 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
             const int grid = (int)std::min<long>((n + 63) / 64, cus_t);
             const int lds = h->vplan.image_floats * 4 + 8 * 48 * (h->vwidth + 4) * 4;
             return instance(pick<32, 64>(h->vwidth, [&](auto W) {
-                return launch_nn(h, st, "k_nn_step_sens_tiled8", k_nn_step_sens_tiled8<W()>, grid, kBlock8, lds, h->dp, h->vplan,
+                return launch_kernel(h, st, "k_nn_step_sens_tiled8", k_nn_step_sens_tiled8<W()>, grid, kBlock8, lds, h->dp, h->vplan,
                                  h->d_vblob, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c, h->d_queue);
             }), kNoTiledInstance);
         }
@@ -749,7 +878,7 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
             const int lds = ((h->plan_sens.lds_total + 15) & ~15) + kSensW2AccBytes;
             if (lds <= 80 * 1024) {
                 const int grid = (int)std::min<long>((n + 63) / 64, 2 * cus);
-                return launch_nn(h, st, "k_nn_step_sens_w2", k_nn_step_sens_w2<2>, grid, kBlock, lds, h->dp, h->plan_sens, h->d_blob,
+                return launch_kernel(h, st, "k_nn_step_sens_w2", k_nn_step_sens_w2<2>, grid, kBlock, lds, h->dp, h->plan_sens, h->d_blob,
                                  X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c);
             }
         }
@@ -762,7 +891,7 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
 #endif
             const MlpPlan& plan = f16 ? h->plan_f16 : bf ? h->plan_bf : engine_plan(h);
             auto launch_main = [&](auto kern) {
-                return launch_nn(h, st, "k_nn_step_sens", kern, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob, X, U, dt,
+                return launch_kernel(h, st, "k_nn_step_sens", kern, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob, X, U, dt,
                                  dt_per_unit, n_main, blk, Xn, A, Bm, c);
             };
             const int rc_m = f16 ? launch_main(k_nn_step_sens<8, true, kHiddenF16>)
@@ -775,7 +904,7 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
             const MlpPlan& plan_p = f16 ? h->plan_f16_pair : bf ? h->plan_bf_pair : h->plan_sens;
             const int lds_p = plan_p.lds_total + 2 * h->wt * 1024 + 2 * 16 * 36 * (int)sizeof(float);  // + the pairs' activation and output exchanges
             auto launch_pair = [&](auto kern) {  // (ac_last_launch keeps the main kernel when there is one)
-                return launch_nn(h, st, n_main == 0 ? "k_nn_step_sens_pair" : nullptr, kern, grid_p, kBlock, lds_p, h->dp, plan_p,
+                return launch_kernel(h, st, n_main == 0 ? "k_nn_step_sens_pair" : nullptr, kern, grid_p, kBlock, lds_p, h->dp, plan_p,
                                  h->d_blob, X, U, dt, dt_per_unit, n, blk, Xn, A, Bm, c, n_main);
             };
             return f16 ? launch_pair(k_nn_step_sens_pair<8, kHiddenF16>)
@@ -822,7 +951,7 @@ static int deriv_sens_impl(ac_handle* h, const float* X, const float* U, long n,
         const int grid = (int)std::min<long>((n + 63) / 64, cus_t);  // persistent workgroups + work queue (GroupQueue, ac_mlp_valu.hpp)
         const int lds = h->vplan.image_floats * 4 + 8 * 48 * (h->vwidth + 4) * 4;
         return instance(pick<32, 64>(h->vwidth, [&](auto W) {
-            return launch_nn(h, st, "k_nn_deriv_sens_tiled8", k_nn_deriv_sens_tiled8<W()>, grid, kBlock8, lds, h->dp, h->vplan,
+            return launch_kernel(h, st, "k_nn_deriv_sens_tiled8", k_nn_deriv_sens_tiled8<W()>, grid, kBlock8, lds, h->dp, h->vplan,
                              h->d_vblob, X, U, n, blk, Xdot, Fx, Fu, h->d_queue);
         }), kNoTiledInstance);
     }
@@ -830,7 +959,7 @@ static int deriv_sens_impl(ac_handle* h, const float* X, const float* U, long n,
         const int grid = (int)((n + 63) / 64);
         const MlpPlan& plan = engine_plan(h);
         return instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
-            return launch_nn(h, st, "k_nn_deriv_sens", k_nn_deriv_sens<WT(), MF()>, grid, kBlock, plan.lds_total, h->dp, plan,
+            return launch_kernel(h, st, "k_nn_deriv_sens", k_nn_deriv_sens<WT(), MF()>, grid, kBlock, plan.lds_total, h->dp, plan,
                              h->d_blob, X, U, n, blk, Xdot, Fx, Fu);
         }), kNoNnInstance);
     }
@@ -973,7 +1102,7 @@ static int hess_single(ac_handle* h, const float* X, const float* U, float dt, c
             if (need_r > h->rev_scratch_floats)
                 return fail(AC_ERR_WORKSPACE, "second-order workspace too small: call ac_reserve_hess_workspace(h, n) first");
             auto launch_rev = [&](auto kern) {
-                return launch_nn(h, st, "k_nn_stage_tensors_rev", kern, grid_r, kBlock, h->plan_rev.lds_total, h->dp, h->plan_rev,
+                return launch_kernel(h, st, "k_nn_stage_tensors_rev", kern, grid_r, kBlock, h->plan_rev.lds_total, h->dp, h->plan_rev,
                                  h->d_blob, X, U, dt, dt_per_unit, n, blk, h->rev_layers, h->d_rev_scratch, h->d_hess_ws);
             };
 #ifdef AC_HESS_REV6  // (A/B flavour: the six-slab reverse sweep, tools/archive/variant_lib.sh)
@@ -986,7 +1115,7 @@ static int hess_single(ac_handle* h, const float* X, const float* U, float dt, c
 #endif
         {
             auto launch_t = [&](auto kern) {
-                return launch_nn(h, st, nullptr, kern, grid_t, kBlock, h->plan.lds_total, h->dp, h->plan, h->d_blob, X, U, dt,
+                return launch_kernel(h, st, nullptr, kern, grid_t, kBlock, h->plan.lds_total, h->dp, h->plan, h->d_blob, X, U, dt,
                                  dt_per_unit, n, blk, h->d_hess_ws);
             };
             int rc = instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
@@ -1613,7 +1742,7 @@ static int rollout_policy(ac_handle* h, const ac_ilqr_cost* limits, const float*
             const int grid = (int)((Bout + 4 * roll_units - 1) / (4 * roll_units));
             const int lds = h->vplan.image_floats * 4 + 4 * (int)roll_units * (h->vwidth + 4) * 4;
             return instance(pick<32, 64>(h->vwidth, [&](auto W) {
-                return launch_nn(h, st, "k_nn_rollout_policy_tiled8", k_nn_rollout_policy_tiled8<W()>, grid, kBlock, lds, h->dp,
+                return launch_kernel(h, st, "k_nn_rollout_policy_tiled8", k_nn_rollout_policy_tiled8<W()>, grid, kBlock, lds, h->dp,
                                  h->vplan, h->d_vblob, pol, X0, dt, Bout, H, Xout, Uout);
             }), kNoTiledInstance);
         }
@@ -1624,14 +1753,14 @@ static int rollout_policy(ac_handle* h, const ac_ilqr_cost* limits, const float*
             return instance(pick<2, 4, 8>(h->wt, [&](auto wt) {
                 constexpr int WT = wt;
                 return pick<1, 2, 3>(nh, [&](auto NH) {
-                    return launch_nn(h, st, "k_nn_rollout_policy_reg", k_nn_rollout_policy_reg<WT, NH()>, grid, kBlock, ldsr, h->dp,
+                    return launch_kernel(h, st, "k_nn_rollout_policy_reg", k_nn_rollout_policy_reg<WT, NH()>, grid, kBlock, ldsr, h->dp,
                                      h->plan, h->d_blob, pol, X0, dt, Bout, H, Xout, Uout);
                 });
             }), kNoNnInstance);
         }
         const int lds = h->plan.lds_total + h->wt * 1024;
         return instance(pick<2, 4, 8>(h->wt, [&](auto WT) {
-            return launch_nn(h, st, "k_nn_rollout_policy_coop", k_nn_rollout_policy_coop<WT(), true>, grid, kBlock, lds, h->dp,
+            return launch_kernel(h, st, "k_nn_rollout_policy_coop", k_nn_rollout_policy_coop<WT(), true>, grid, kBlock, lds, h->dp,
                              h->plan, h->d_blob, pol, X0, dt, Bout, H, Xout, Uout);
         }), kNoNnInstance);
     }
@@ -1683,6 +1812,33 @@ size_t vjp_ws_floats(const ac_handle* h, int which, long n, long H) {
     return (size_t)n * (which == AC_VJP_DERIVATIVE ? kVjpDerivWs : kVjpStepWs);
 }
 int vjp_lds_bytes(const ac_handle* h) { return vjp_lane_words(h->dp.p.substeps) * kVjpBlock * (int)sizeof(float); }
+// The composed route's contraction of n units:  Xbar = A' lam, Ubar = B' lam, dtbar = c . lam  (c, dtbar nullable)
+int vjp_contract(ac_handle* h, hipStream_t st, const float* A, const float* Bm, const float* c, const float* Lam, long n,
+                 float* Xbar, float* Ubar, float* dtbar) {
+    const int grid = (int)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_vjp_contract, grid, kBlock, 0, st, A, Bm, c, Lam, n, Xbar, Ubar, dtbar);
+    note_launch(h, "k_vjp_contract", grid, kBlock, 0);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
+// The composed route over a saved rollout: every (node, instance) pair is one unit of the multiple-shooting sensitivity kernels
+// (x+, A, B, c into ws, kVjpStepWs floats per pair), then the reverse recurrence.  LamTraj (nullable) [H][13][B]: lambda_{k+1} per
+// node, for the weight gradient.
+int rollout_recur_composed(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G,
+                           float* X0bar, float* Ubar, float* dtbar, float* LamTraj, float* ws, void* stream) {
+    const size_t N = (size_t)B * (size_t)H;
+    float* Xn = ws;
+    float* A = Xn + 13 * N;
+    float* Bm = A + 169 * N;
+    float* c = Bm + 91 * N;
+    const int rc = sens_impl(h, Xtraj, U, dt, nullptr, B * H, B, Xn, A, Bm, c, stream);
+    if (rc != AC_OK) return rc;
+    const int grid = (int)((B + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_vjp_recur, grid, kBlock, 0, (hipStream_t)stream, A, Bm, c, G, B, H, X0bar, Ubar, dtbar, LamTraj);
+    note_launch(h, "k_vjp_recur", grid, kBlock, 0);
+    AC_HIP(hipGetLastError());
+    return AC_OK;
+}
 }  // namespace
 
 int ac_set_vjp_route(ac_handle* h, int route) {
@@ -1713,18 +1869,10 @@ int ac_step_vjp_f32(ac_handle* h, const float* X, const float* U, float dt, cons
     if (route == AC_VJP_FUSED) {
         const int grid = (int)((n + kVjpBlock - 1) / kVjpBlock);
         const int lds = vjp_lds_bytes(h);
-#define AC_VJP_STEP_CASE(M_)                                                                                            \
-        case M_: {                                                                                                      \
-            rc = set_lds_limit(h, k_step_vjp<M_>, lds);                                                                 \
-            if (rc != AC_OK) return rc;                                                                                 \
-            hipLaunchKernelGGL(k_step_vjp<M_>, grid, kVjpBlock, lds, st, h->dp, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar); \
-            break;                                                                                                      \
-        }
-        switch (h->dp.p.model_kind) { AC_VJP_STEP_CASE(AC_MODEL_LINEAR) AC_VJP_STEP_CASE(AC_MODEL_POLY) default: AC_VJP_STEP_CASE(AC_MODEL_DEFAULT) }
-#undef AC_VJP_STEP_CASE
-        note_launch(h, "k_step_vjp", grid, kVjpBlock, lds);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        return pick_fused_model(h, [&](auto M) {
+            return launch_kernel(h, st, "k_step_vjp", k_step_vjp<M()>, grid, kVjpBlock, lds, h->dp, X, U, dt, dt_per_unit, Lam, n, Xbar,
+                                 Ubar, dtbar);
+        });
     }
     const size_t N = (size_t)n;
     if (!ws || ws_floats < N * kVjpStepWs) return fail(AC_ERR_WORKSPACE, "VJP workspace too small: see ac_vjp_workspace_floats");
@@ -1734,11 +1882,7 @@ int ac_step_vjp_f32(ac_handle* h, const float* X, const float* U, float dt, cons
     float* c = Bm + 91 * N;
     rc = sens_impl(h, X, U, dt, dt_per_unit, n, n, Xn, A, Bm, dtbar ? c : nullptr, stream);
     if (rc != AC_OK) return rc;
-    const int grid = (int)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_vjp_contract, grid, kBlock, 0, st, A, Bm, dtbar ? c : nullptr, Lam, n, Xbar, Ubar, dtbar);
-    note_launch(h, "k_vjp_contract", grid, kBlock, 0);
-    AC_HIP(hipGetLastError());
-    return AC_OK;
+    return vjp_contract(h, st, A, Bm, dtbar ? c : nullptr, Lam, n, Xbar, Ubar, dtbar);
 }
 
 int ac_rollout_vjp_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
@@ -1759,33 +1903,14 @@ int ac_rollout_vjp_f32(ac_handle* h, const float* Xtraj, const float* U, float d
     if (route == AC_VJP_FUSED) {
         const int grid = (int)((B + kVjpBlock - 1) / kVjpBlock);
         const int lds = vjp_lds_bytes(h);
-#define AC_VJP_ROLL_CASE(M_)                                                                                            \
-        case M_: {                                                                                                      \
-            rc = set_lds_limit(h, k_rollout_vjp<M_>, lds);                                                              \
-            if (rc != AC_OK) return rc;                                                                                 \
-            hipLaunchKernelGGL(k_rollout_vjp<M_>, grid, kVjpBlock, lds, st, h->dp, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar); \
-            break;                                                                                                      \
-        }
-        switch (h->dp.p.model_kind) { AC_VJP_ROLL_CASE(AC_MODEL_LINEAR) AC_VJP_ROLL_CASE(AC_MODEL_POLY) default: AC_VJP_ROLL_CASE(AC_MODEL_DEFAULT) }
-#undef AC_VJP_ROLL_CASE
-        note_launch(h, "k_rollout_vjp", grid, kVjpBlock, lds);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        return pick_fused_model(h, [&](auto M) {
+            return launch_kernel(h, st, "k_rollout_vjp", k_rollout_vjp<M()>, grid, kVjpBlock, lds, h->dp, Xtraj, U, dt, B, H, G, X0bar,
+                                 Ubar, dtbar);
+        });
     }
-    const size_t N = (size_t)B * (size_t)H;
-    if (!ws || ws_floats < N * kVjpStepWs) return fail(AC_ERR_WORKSPACE, "VJP workspace too small: see ac_vjp_workspace_floats");
-    float* Xn = ws;
-    float* A = Xn + 13 * N;
-    float* Bm = A + 169 * N;
-    float* c = Bm + 91 * N;
-    // every (node, instance) pair of the saved trajectory is one unit of the multiple-shooting sensitivity kernels
-    rc = sens_impl(h, Xtraj, U, dt, nullptr, B * H, B, Xn, A, Bm, c, stream);
-    if (rc != AC_OK) return rc;
-    const int grid = (int)((B + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_vjp_recur, grid, kBlock, 0, st, A, Bm, c, G, B, H, X0bar, Ubar, dtbar, (float*)nullptr);
-    note_launch(h, "k_vjp_recur", grid, kBlock, 0);
-    AC_HIP(hipGetLastError());
-    return AC_OK;
+    if (!ws || ws_floats < (size_t)B * (size_t)H * kVjpStepWs)
+        return fail(AC_ERR_WORKSPACE, "VJP workspace too small: see ac_vjp_workspace_floats");
+    return rollout_recur_composed(h, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, nullptr, ws, stream);
 }
 
 int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, long n, const float* W, float* Xbar, float* Ubar,
@@ -1800,14 +1925,9 @@ int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, lo
     hipStream_t st = (hipStream_t)stream;
     if (route == AC_VJP_FUSED) {
         const int grid = (int)((n + kBlock - 1) / kBlock);
-        switch (h->dp.p.model_kind) {
-            case AC_MODEL_LINEAR: hipLaunchKernelGGL(k_deriv_vjp<AC_MODEL_LINEAR>, grid, kBlock, 0, st, h->dp, X, U, W, n, Xbar, Ubar); break;
-            case AC_MODEL_POLY: hipLaunchKernelGGL(k_deriv_vjp<AC_MODEL_POLY>, grid, kBlock, 0, st, h->dp, X, U, W, n, Xbar, Ubar); break;
-            default: hipLaunchKernelGGL(k_deriv_vjp<AC_MODEL_DEFAULT>, grid, kBlock, 0, st, h->dp, X, U, W, n, Xbar, Ubar); break;
-        }
-        note_launch(h, "k_deriv_vjp", grid, kBlock, 0);
-        AC_HIP(hipGetLastError());
-        return AC_OK;
+        return pick_fused_model(h, [&](auto M) {
+            return launch_kernel(h, st, "k_deriv_vjp", k_deriv_vjp<M()>, grid, kBlock, 0, h->dp, X, U, W, n, Xbar, Ubar);
+        });
     }
     const size_t N = (size_t)n;
     if (!ws || ws_floats < N * kVjpDerivWs) return fail(AC_ERR_WORKSPACE, "VJP workspace too small: see ac_vjp_workspace_floats");
@@ -1816,11 +1936,7 @@ int ac_state_derivative_vjp_f32(ac_handle* h, const float* X, const float* U, lo
     float* Fu = Fx + 169 * N;
     rc = deriv_sens_impl(h, X, U, n, n, Xd, Fx, Fu, stream);
     if (rc != AC_OK) return rc;
-    const int grid = (int)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_vjp_contract, grid, kBlock, 0, st, Fx, Fu, nullptr, W, n, Xbar, Ubar, nullptr);
-    note_launch(h, "k_vjp_contract", grid, kBlock, 0);
-    AC_HIP(hipGetLastError());
-    return AC_OK;
+    return vjp_contract(h, st, Fx, Fu, nullptr, W, n, Xbar, Ubar, nullptr);
 }
 
 // ---- reverse mode to the weights of the MLP surrogate (ac_wgrad.hpp) ----------------------------------------------------------
@@ -1853,7 +1969,7 @@ int wgrad_seeds_impl(ac_handle* h, const float* X, const float* U, float dt, con
     const int grid_t = (int)((n + 63) / 64);
     const MlpPlan& plan = engine_plan(h);
     int rc = instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
-        return launch_nn(h, st, "k_nn_stage_jac", k_nn_stage_jac<WT(), MF()>, grid_t, kBlock, plan.lds_total, h->dp, plan, h->d_blob,
+        return launch_kernel(h, st, "k_nn_stage_jac", k_nn_stage_jac<WT(), MF()>, grid_t, kBlock, plan.lds_total, h->dp, plan, h->d_blob,
                          X, U, dt, dt_per_unit, n, blk, table);
     }), kNoNnInstance);
     if (rc != AC_OK) return rc;
@@ -1876,7 +1992,7 @@ int wgrad_step_impl(ac_handle* h, const float* X, const float* U, float dt, cons
     if (rc != AC_OK) return rc;
     const int parts = wgrad_parts(h, N), lds = wgrad_lds_bytes(h->wg.n_layers, h->wt);
     rc = instance(pick_wt_mfma(h, [&](auto WT, auto MF) {
-        return launch_nn(h, st, "k_mlp_wgrad", k_mlp_wgrad<WT(), MF()>, parts, kWgBlock, lds, h->wg, (const float*)h->d_wgimg,
+        return launch_kernel(h, st, "k_mlp_wgrad", k_mlp_wgrad<WT(), MF()>, parts, kWgBlock, lds, h->wg, (const float*)h->d_wgimg,
                          (const float*)Z, (const float*)Ybar, n, 4 * n, partial);
     }), kNoNnInstance);
     if (rc != AC_OK) return rc;
@@ -1966,65 +2082,15 @@ int ac_rollout_wgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float
     float* X0bar = lam + 13 * N;
     float* Ubar = X0bar + 13 * Bs;
     float* dtbar = Ubar + 7 * N;
-    {   // the reverse recurrence of the composed VJP route, with lambda_{k+1} kept per node
-        float* Xn = ws;
-        float* A = Xn + 13 * N;
-        float* Bm = A + 169 * N;
-        float* c = Bm + 91 * N;
-        const int rc = sens_impl(h, Xtraj, U, dt, nullptr, B * H, B, Xn, A, Bm, c, stream);
-        if (rc != AC_OK) return rc;
-        const int grid = (int)((B + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_vjp_recur, grid, kBlock, 0, st, A, Bm, c, G, B, H, X0bar, Ubar, dtbar, lam);
-        AC_HIP(hipGetLastError());
-    }
+    // the reverse recurrence of the composed VJP route, with lambda_{k+1} kept per node
+    const int rc = rollout_recur_composed(h, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, lam, ws, stream);
+    if (rc != AC_OK) return rc;
     // (the Jacobians are consumed: the step gradient's buffers reuse their place)
     return wgrad_step_impl(h, Xtraj, U, dt, nullptr, B * H, B, lam, Wbar, ws, st);
 }
 
-// ---- reverse mode to the coefficients of the cubic-fit and the linear model (ac_cgrad.hpp) ------------------------------------
-namespace {
-int cgrad_floats_of(const ac_handle* h) {
-    const int mk = h->dp.p.model_kind;
-    return mk == AC_MODEL_POLY ? CgradFloats<AC_MODEL_POLY>::value : (mk == AC_MODEL_LINEAR ? CgradFloats<AC_MODEL_LINEAR>::value : 0);
-}
-// why the coefficient gradient cannot run on this handle (nullptr: it can); sets *code
-const char* cgrad_refusal(const ac_handle* h, int* code) {
-    *code = AC_ERR_UNSUPPORTED;
-    if (!cgrad_floats_of(h)) return "coefficient gradients exist for the cubic-fit (poly) and the linear model only";
-    if (model_ready(h) != AC_OK) { *code = AC_ERR_NO_MODEL; return "no coefficients installed: call ac_set_poly / ac_set_linear first"; }
-    if (h->dp.p.substeps > kCgradMaxSubsteps)
-        return "coefficient gradients: at most 30 RK4 sub-steps (240 + 13 sub-steps <= 640 words of LDS per lane)";
-    return nullptr;
-}
-int cgrad_lds_bytes(const ac_handle* h) {
-    return cgrad_lane_words(cgrad_floats_of(h), h->dp.p.substeps) * kVjpBlock * (int)sizeof(float);
-}
-// Workgroups of a launch over `units` lanes: one per tile of 64 up to the handle's cap — the CU count read at creation times
-// the workgroups whose LDS fits one CU (at most 8), or ac_set_cgrad_grid's value.  Never the runtime's occupancy: the same
-// inputs on the same handle give the same partials.
-int grad_grid_of(const ac_handle* h, long units, int lds_bytes) {
-    const long tiles = (units + kVjpBlock - 1) / kVjpBlock;
-    long cap = h->cgrad_grid;
-    if (cap <= 0) {
-        const long per_cu = std::max(1, std::min(8, 160 * 1024 / lds_bytes));
-        cap = (h->num_cus > 0 ? h->num_cus : 256) * per_cu;
-    }
-    return (int)std::max<long>(1, std::min(tiles, cap));
-}
-int cgrad_grid_of(const ac_handle* h, long units) { return grad_grid_of(h, units, cgrad_lds_bytes(h)); }
-// after the sweep `name`: the F floats of its `grid` partials added in workgroup order
-int grad_finish(ac_handle* h, hipStream_t st, const char* name, int grid, int lds, const float* partial, int F, float* out) {
-    note_launch(h, name, grid, kVjpBlock, lds);
-    AC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_wgrad_reduce, (F + kBlock - 1) / kBlock, kBlock, 0, st, partial, grid, F, out);
-    AC_HIP(hipGetLastError());
-    return AC_OK;
-}
-int cgrad_finish(ac_handle* h, hipStream_t st, const char* name, int grid, int lds, const float* partial, float* Thetabar) {
-    return grad_finish(h, st, name, grid, lds, partial, cgrad_floats_of(h), Thetabar);
-}
-}  // namespace
-
+// ---- reverse mode to parameters: the coefficients of the cubic-fit and the linear model (ac_cgrad.hpp), and mass, inertia,
+// inertia_inv and com (ac_agrad.hpp): the pgrad_* functions above with their descriptor ----------------------------------------
 int ac_coef_grad_floats(const ac_handle* h, size_t* floats) {
     if (!h || !floats) return AC_ERR_BAD_ARG;
     g_err[0] = 0;
@@ -2041,149 +2107,27 @@ int ac_set_cgrad_grid(ac_handle* h, int max_workgroups) {
 }
 
 int ac_cgrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats) {
-    if (!h || !floats || n_or_B < 0 || H < 0 || which < AC_CGRAD_STEP || which > AC_CGRAD_ROLLOUT) return AC_ERR_BAD_ARG;
-    g_err[0] = 0;
-    int code;
-    if (const char* why = cgrad_refusal(h, &code)) return fail(code, why);
-    *floats = (size_t)cgrad_grid_of(h, n_or_B) * (size_t)cgrad_floats_of(h);
-    return AC_OK;
+    return pgrad_workspace_floats<CoefGrad>(h, which, n_or_B, H, floats);
 }
-
 int ac_step_cgrad_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
                       float* Xbar, float* Ubar, float* dtbar, float* Thetabar, float* ws, size_t ws_floats, void* stream) {
-    AC_ENTER(h);
-    if (!h || !Thetabar || n < 0 || (n > 0 && (!X || !U || !Lam))) return AC_ERR_BAD_ARG;
-    int code;
-    if (const char* why = cgrad_refusal(h, &code)) return fail(code, why);
-    hipStream_t st = (hipStream_t)stream;
-    const int F = cgrad_floats_of(h);
-    if (n == 0) {
-        AC_HIP(hipMemsetAsync(Thetabar, 0, (size_t)F * sizeof(float), st));
-        return AC_OK;
-    }
-    const int grid = cgrad_grid_of(h, n), lds = cgrad_lds_bytes(h);
-    if (!ws || ws_floats < (size_t)grid * (size_t)F)
-        return fail(AC_ERR_WORKSPACE, "coefficient-gradient workspace too small: see ac_cgrad_workspace_floats");
-#define AC_CGRAD_STEP_CASE(M_)                                                                                          \
-        case M_: {                                                                                                      \
-            const int rc = set_lds_limit(h, k_step_cgrad<M_>, lds);                                                     \
-            if (rc != AC_OK) return rc;                                                                                 \
-            hipLaunchKernelGGL(k_step_cgrad<M_>, grid, kVjpBlock, lds, st, h->dp, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar, ws); \
-            break;                                                                                                      \
-        }
-    switch (h->dp.p.model_kind) { AC_CGRAD_STEP_CASE(AC_MODEL_LINEAR) default: AC_CGRAD_STEP_CASE(AC_MODEL_POLY) }
-#undef AC_CGRAD_STEP_CASE
-    return cgrad_finish(h, st, "k_step_cgrad", grid, lds, ws, Thetabar);
+    return pgrad_step<CoefGrad>(h, X, U, dt, dt_per_unit, n, Lam, Xbar, Ubar, dtbar, Thetabar, ws, ws_floats, stream);
 }
-
 int ac_rollout_cgrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
                          float* Ubar, float* dtbar, float* Thetabar, float* ws, size_t ws_floats, void* stream) {
-    AC_ENTER(h);
-    if (!h || !Thetabar || B < 0 || H < 0 || (B > 0 && (!Xtraj || !G || (H > 0 && !U)))) return AC_ERR_BAD_ARG;
-    int code;
-    if (const char* why = cgrad_refusal(h, &code)) return fail(code, why);
-    hipStream_t st = (hipStream_t)stream;
-    const int F = cgrad_floats_of(h);
-    if (B == 0 || H == 0) {  // no step, no coefficient enters; X[0] = x0: the cotangent passes through
-        AC_HIP(hipMemsetAsync(Thetabar, 0, (size_t)F * sizeof(float), st));
-        if (B > 0 && X0bar) AC_HIP(hipMemcpyAsync(X0bar, G, (size_t)B * 13 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (B > 0 && dtbar) AC_HIP(hipMemsetAsync(dtbar, 0, (size_t)B * sizeof(float), st));
-        return AC_OK;
-    }
-    const int grid = cgrad_grid_of(h, B), lds = cgrad_lds_bytes(h);
-    if (!ws || ws_floats < (size_t)grid * (size_t)F)
-        return fail(AC_ERR_WORKSPACE, "coefficient-gradient workspace too small: see ac_cgrad_workspace_floats");
-#define AC_CGRAD_ROLL_CASE(M_)                                                                                          \
-        case M_: {                                                                                                      \
-            const int rc = set_lds_limit(h, k_rollout_cgrad<M_>, lds);                                                  \
-            if (rc != AC_OK) return rc;                                                                                 \
-            hipLaunchKernelGGL(k_rollout_cgrad<M_>, grid, kVjpBlock, lds, st, h->dp, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, ws); \
-            break;                                                                                                      \
-        }
-    switch (h->dp.p.model_kind) { AC_CGRAD_ROLL_CASE(AC_MODEL_LINEAR) default: AC_CGRAD_ROLL_CASE(AC_MODEL_POLY) }
-#undef AC_CGRAD_ROLL_CASE
-    return cgrad_finish(h, st, "k_rollout_cgrad", grid, lds, ws, Thetabar);
+    return pgrad_rollout<CoefGrad>(h, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, Thetabar, ws, ws_floats, stream);
 }
-
-// ---- reverse mode to mass, inertia, inertia_inv and com (ac_agrad.hpp) -----------------------------------------------------------
-namespace {
-// why the airframe gradient cannot run on this handle (nullptr: it can); sets *code
-const char* agrad_refusal(const ac_handle* h, int* code) {
-    *code = AC_ERR_UNSUPPORTED;
-    const int mk = h->dp.p.model_kind;
-    if (mk == AC_MODEL_NN) return "airframe gradients: the MLP surrogate has no fused reverse sweep (default, linear and cubic-fit models only)";
-    if (mk == AC_MODEL_QUAD) return "airframe gradients: the quadrotor's sweep is not recorded (default, linear and cubic-fit models only)";
-    if (model_ready(h) != AC_OK) { *code = AC_ERR_NO_MODEL; return "no coefficients installed: call ac_set_poly / ac_set_linear first"; }
-    if (h->dp.p.substeps > kAgradMaxSubsteps) return "airframe gradients: at most 40 RK4 sub-steps (the limit of the fused reverse sweep)";
-    return nullptr;
-}
-int agrad_lds_bytes(const ac_handle* h) {
-    return cgrad_lane_words(kAgradFloats, h->dp.p.substeps) * kVjpBlock * (int)sizeof(float);
-}
-int agrad_grid_of(const ac_handle* h, long units) { return grad_grid_of(h, units, agrad_lds_bytes(h)); }
-}  // namespace
 
 int ac_agrad_workspace_floats(const ac_handle* h, int which, long n_or_B, long H, size_t* floats) {
-    if (!h || !floats || n_or_B < 0 || H < 0 || which < AC_CGRAD_STEP || which > AC_CGRAD_ROLLOUT) return AC_ERR_BAD_ARG;
-    g_err[0] = 0;
-    int code;
-    if (const char* why = agrad_refusal(h, &code)) return fail(code, why);
-    *floats = (size_t)agrad_grid_of(h, n_or_B) * (size_t)kAgradFloats;
-    return AC_OK;
+    return pgrad_workspace_floats<AirframeGrad>(h, which, n_or_B, H, floats);
 }
-
 int ac_step_agrad_f32(ac_handle* h, const float* X, const float* U, float dt, const float* dt_per_unit, long n, const float* Lam,
                       float* Xbar, float* Ubar, float* dtbar, float* Phibar, float* ws, size_t ws_floats, void* stream) {
-    AC_ENTER(h);
-    if (!h || !Phibar || n < 0 || (n > 0 && (!X || !U || !Lam))) return AC_ERR_BAD_ARG;
-    int code;
-    if (const char* why = agrad_refusal(h, &code)) return fail(code, why);
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) {
-        AC_HIP(hipMemsetAsync(Phibar, 0, (size_t)kAgradFloats * sizeof(float), st));
-        return AC_OK;
-    }
-    const int grid = agrad_grid_of(h, n), lds = agrad_lds_bytes(h);
-    if (!ws || ws_floats < (size_t)grid * (size_t)kAgradFloats)
-        return fail(AC_ERR_WORKSPACE, "airframe-gradient workspace too small: see ac_agrad_workspace_floats");
-#define AC_AGRAD_STEP_CASE(M_)                                                                                          \
-        case M_: {                                                                                                      \
-            const int rc = set_lds_limit(h, k_step_agrad<M_>, lds);                                                     \
-            if (rc != AC_OK) return rc;                                                                                 \
-            hipLaunchKernelGGL(k_step_agrad<M_>, grid, kVjpBlock, lds, st, h->dp, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar, ws); \
-            break;                                                                                                      \
-        }
-    switch (h->dp.p.model_kind) { AC_AGRAD_STEP_CASE(AC_MODEL_LINEAR) AC_AGRAD_STEP_CASE(AC_MODEL_POLY) default: AC_AGRAD_STEP_CASE(AC_MODEL_DEFAULT) }
-#undef AC_AGRAD_STEP_CASE
-    return grad_finish(h, st, "k_step_agrad", grid, lds, ws, kAgradFloats, Phibar);
+    return pgrad_step<AirframeGrad>(h, X, U, dt, dt_per_unit, n, Lam, Xbar, Ubar, dtbar, Phibar, ws, ws_floats, stream);
 }
-
 int ac_rollout_agrad_f32(ac_handle* h, const float* Xtraj, const float* U, float dt, long B, long H, const float* G, float* X0bar,
                          float* Ubar, float* dtbar, float* Phibar, float* ws, size_t ws_floats, void* stream) {
-    AC_ENTER(h);
-    if (!h || !Phibar || B < 0 || H < 0 || (B > 0 && (!Xtraj || !G || (H > 0 && !U)))) return AC_ERR_BAD_ARG;
-    int code;
-    if (const char* why = agrad_refusal(h, &code)) return fail(code, why);
-    hipStream_t st = (hipStream_t)stream;
-    if (B == 0 || H == 0) {  // no step, no constant enters; X[0] = x0: the cotangent passes through
-        AC_HIP(hipMemsetAsync(Phibar, 0, (size_t)kAgradFloats * sizeof(float), st));
-        if (B > 0 && X0bar) AC_HIP(hipMemcpyAsync(X0bar, G, (size_t)B * 13 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (B > 0 && dtbar) AC_HIP(hipMemsetAsync(dtbar, 0, (size_t)B * sizeof(float), st));
-        return AC_OK;
-    }
-    const int grid = agrad_grid_of(h, B), lds = agrad_lds_bytes(h);
-    if (!ws || ws_floats < (size_t)grid * (size_t)kAgradFloats)
-        return fail(AC_ERR_WORKSPACE, "airframe-gradient workspace too small: see ac_agrad_workspace_floats");
-#define AC_AGRAD_ROLL_CASE(M_)                                                                                          \
-        case M_: {                                                                                                      \
-            const int rc = set_lds_limit(h, k_rollout_agrad<M_>, lds);                                                  \
-            if (rc != AC_OK) return rc;                                                                                 \
-            hipLaunchKernelGGL(k_rollout_agrad<M_>, grid, kVjpBlock, lds, st, h->dp, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, ws); \
-            break;                                                                                                      \
-        }
-    switch (h->dp.p.model_kind) { AC_AGRAD_ROLL_CASE(AC_MODEL_LINEAR) AC_AGRAD_ROLL_CASE(AC_MODEL_POLY) default: AC_AGRAD_ROLL_CASE(AC_MODEL_DEFAULT) }
-#undef AC_AGRAD_ROLL_CASE
-    return grad_finish(h, st, "k_rollout_agrad", grid, lds, ws, kAgradFloats, Phibar);
+    return pgrad_rollout<AirframeGrad>(h, Xtraj, U, dt, B, H, G, X0bar, Ubar, dtbar, Phibar, ws, ws_floats, stream);
 }
 
 // ---- steady-flight trim (ac_trim.hpp) -----------------------------------------------------------------------------------------

@@ -452,10 +452,9 @@ class SixDOF(ABC):
             Xb, Ub, db = Xb[..., 0], Ub[..., 0], db[0]
         return Xb, Ub, db
 
-    def rollout_vjp(self, X, U, dt, G, ws=None):
-        """Reverse mode of rollout: X (H+1, 13, B) the trajectory rollout() returned for (x0, U, dt), G (H+1, 13, B) the
-        cotangent of every node -> (x0_bar (13, B), U_bar (H, num_controls, B), dt_bar (B,)).  dt is a scalar, as in
-        rollout(); dt_bar is the per-instance sum over the nodes."""
+    def _rollout_args(self, who, X, U, dt, G):
+        """The saved rollout (X, U, dt, G) of the reverse sweeps as contiguous fp32 device tensors, U padded to the ABI's seven
+        controls: -> (Xt (H+1, 13, B), Ut (H, 7, B), Gt, B, H, from_np)."""
         torch = _torch()
         dev = self._device_obj()
         from_np = not isinstance(X, torch.Tensor)
@@ -475,9 +474,17 @@ class SixDOF(ABC):
             raise ValueError(f"X {tuple(Xt.shape)}, U {tuple(Ut.shape)} and G {tuple(Gt.shape)} do not describe one rollout")
         if Ut.shape[1] < _lib.NUM_CONTROLS:
             Ut = torch.cat([Ut, torch.zeros((H, _lib.NUM_CONTROLS - Ut.shape[1], B), device=dev)], dim=1)
-        Ut = Ut.contiguous()
         if np.ndim(dt) > 0 or (isinstance(dt, torch.Tensor) and dt.numel() != 1):
-            raise ValueError("rollout_vjp: dt must be a scalar (as in rollout)")
+            raise ValueError(f"{who}: dt must be a scalar (as in rollout)")
+        return Xt, Ut.contiguous(), Gt, B, H, from_np
+
+    def rollout_vjp(self, X, U, dt, G, ws=None):
+        """Reverse mode of rollout: X (H+1, 13, B) the trajectory rollout() returned for (x0, U, dt), G (H+1, 13, B) the
+        cotangent of every node -> (x0_bar (13, B), U_bar (H, num_controls, B), dt_bar (B,)).  dt is a scalar, as in
+        rollout(); dt_bar is the per-instance sum over the nodes."""
+        torch = _torch()
+        dev = self._device_obj()
+        Xt, Ut, Gt, B, H, from_np = self._rollout_args("rollout_vjp", X, U, dt, G)
         lib, ws, wsn = self._vjp_ws("rollout", B, H, ws)
         X0b = torch.empty((self.num_states, B), device=dev, dtype=torch.float32)
         Ub = torch.empty((H, _lib.NUM_CONTROLS, B), device=dev, dtype=torch.float32)
@@ -534,10 +541,13 @@ class SixDOF(ABC):
     def wgrad_workspace(self, kind, n, H=0):
         """Device workspace of the weight-gradient call `kind` ("seeds", "step", "rollout" with n = B).  Allocate it before
         capturing a graph and pass it as `ws=`."""
+        return self._grad_workspace("ac_wgrad_workspace_floats", self._WGRAD_KINDS[kind], n, H)
+
+    def _grad_workspace(self, getter, which, n, H):
+        """A device workspace of the size the ABI's `getter` (ac_{wgrad,cgrad,agrad}_workspace_floats) reports; never empty."""
         lib = self._sync()
         need = C.c_size_t()
-        _lib.check(lib.ac_wgrad_workspace_floats(self._handle, self._WGRAD_KINDS[kind], int(n), int(H), C.byref(need)),
-                   "ac_wgrad_workspace_floats")
+        _lib.check(getattr(lib, getter)(self._handle, which, int(n), int(H), C.byref(need)), getter)
         return _torch().empty(max(int(need.value), 1), device=self._device_obj(), dtype=_torch().float32)
 
     def _wgrad_units(self, x, u, lam):
@@ -588,25 +598,7 @@ class SixDOF(ABC):
         returned for (x0, U, dt) and G (H+1, 13, B) the cotangent of every node: the layout of step_wgrad."""
         torch = _torch()
         dev = self._device_obj()
-
-        def t3(a, name, rows):
-            t = torch.as_tensor(np.asarray(a, dtype=np.float32) if not isinstance(a, torch.Tensor) else a)
-            if t.dim() != 3 or t.shape[1] not in rows:
-                raise ValueError(f"{name}: expected (., {rows[0]}, B), got {tuple(t.shape)}")
-            return t.to(device=dev, dtype=torch.float32)
-
-        Xt = t3(X, "X", (self.num_states,)).contiguous()
-        Gt = t3(G, "G", (self.num_states,)).contiguous()
-        Hp1, _, B = Xt.shape
-        H = Hp1 - 1
-        Ut = t3(U, "U", (self.num_controls, _lib.NUM_CONTROLS)) if H > 0 else torch.zeros((0, _lib.NUM_CONTROLS, B), device=dev)
-        if Gt.shape != Xt.shape or Ut.shape[0] != H or Ut.shape[2] != B:
-            raise ValueError(f"X {tuple(Xt.shape)}, U {tuple(Ut.shape)} and G {tuple(Gt.shape)} do not describe one rollout")
-        if Ut.shape[1] < _lib.NUM_CONTROLS:
-            Ut = torch.cat([Ut, torch.zeros((H, _lib.NUM_CONTROLS - Ut.shape[1], B), device=dev)], dim=1)
-        Ut = Ut.contiguous()
-        if np.ndim(dt) > 0 or (isinstance(dt, torch.Tensor) and dt.numel() != 1):
-            raise ValueError("rollout_wgrad: dt must be a scalar (as in rollout)")
+        Xt, Ut, Gt, B, H, _ = self._rollout_args("rollout_wgrad", X, U, dt, G)
         if ws is None:
             ws = self.wgrad_workspace("rollout", B, H)
         lib = self._sync()
@@ -637,11 +629,7 @@ class SixDOF(ABC):
     def coef_grad_workspace(self, kind, n, H=0):
         """Device workspace of the coefficient-gradient call `kind` ("step", "rollout" with n = B).  Allocate it before
         capturing a graph and pass it as `ws=`."""
-        lib = self._sync()
-        need = C.c_size_t()
-        _lib.check(lib.ac_cgrad_workspace_floats(self._handle, self._CGRAD_KINDS[kind], int(n), int(H), C.byref(need)),
-                   "ac_cgrad_workspace_floats")
-        return _torch().empty(max(int(need.value), 1), device=self._device_obj(), dtype=_torch().float32)
+        return self._grad_workspace("ac_cgrad_workspace_floats", self._CGRAD_KINDS[kind], n, H)
 
     def _step_param_grad(self, call, floats, workspace, x, u, dt, lam, ws, out, need):
         """One recording reverse sweep over n units (ac_step_cgrad_f32, ac_step_agrad_f32): -> (parameter gradient (floats,),
@@ -668,25 +656,7 @@ class SixDOF(ABC):
         U_bar (H, num_controls, B), dt_bar (B,))."""
         torch = _torch()
         dev = self._device_obj()
-
-        def t3(a, name, rows):
-            t = torch.as_tensor(np.asarray(a, dtype=np.float32) if not isinstance(a, torch.Tensor) else a)
-            if t.dim() != 3 or t.shape[1] not in rows:
-                raise ValueError(f"{name}: expected (., {rows[0]}, B), got {tuple(t.shape)}")
-            return t.to(device=dev, dtype=torch.float32)
-
-        Xt = t3(X, "X", (self.num_states,)).contiguous()
-        Gt = t3(G, "G", (self.num_states,)).contiguous()
-        Hp1, _, B = Xt.shape
-        H = Hp1 - 1
-        Ut = t3(U, "U", (self.num_controls, _lib.NUM_CONTROLS)) if H > 0 else torch.zeros((0, _lib.NUM_CONTROLS, B), device=dev)
-        if Gt.shape != Xt.shape or Ut.shape[0] != H or Ut.shape[2] != B:
-            raise ValueError(f"X {tuple(Xt.shape)}, U {tuple(Ut.shape)} and G {tuple(Gt.shape)} do not describe one rollout")
-        if Ut.shape[1] < _lib.NUM_CONTROLS:
-            Ut = torch.cat([Ut, torch.zeros((H, _lib.NUM_CONTROLS - Ut.shape[1], B), device=dev)], dim=1)
-        Ut = Ut.contiguous()
-        if np.ndim(dt) > 0 or (isinstance(dt, torch.Tensor) and dt.numel() != 1):
-            raise ValueError(f"{who}: dt must be a scalar (as in rollout)")
+        Xt, Ut, Gt, B, H, _ = self._rollout_args(who, X, U, dt, G)
         if ws is None:
             ws = workspace("rollout", B, H)
         lib = self._sync()
@@ -719,11 +689,7 @@ class SixDOF(ABC):
     def airframe_grad_workspace(self, kind, n, H=0):
         """Device workspace of the airframe-gradient call `kind` ("step", "rollout" with n = B).  Allocate it before capturing a
         graph and pass it as `ws=`."""
-        lib = self._sync()
-        need = C.c_size_t()
-        _lib.check(lib.ac_agrad_workspace_floats(self._handle, self._CGRAD_KINDS[kind], int(n), int(H), C.byref(need)),
-                   "ac_agrad_workspace_floats")
-        return _torch().empty(max(int(need.value), 1), device=self._device_obj(), dtype=_torch().float32)
+        return self._grad_workspace("ac_agrad_workspace_floats", self._CGRAD_KINDS[kind], n, H)
 
     def step_airframe_grad(self, x, u, dt, lam, ws=None, out=None, need=(True, True, True)):
         """Gradient of sum(lam * F(x, u, dt)) over the 22 airframe floats the kernels read, each as an independent number —

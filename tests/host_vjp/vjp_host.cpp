@@ -1,4 +1,4 @@
-// vjp_host.cpp — the fused reverse-mode kernels' per-unit code (aircraft_amd/csrc/ac_vjp.hpp: step_vjp_unit, deriv_vjp_unit)
+// vjp_host.cpp — the fused reverse-mode kernels' lane code (aircraft_amd/csrc/ac_vjp.hpp: step_vjp_lane, deriv_vjp_unit)
 // compiled for the HOST (g++, -DAC_HOST_CHECK) behind a small C API, so that `pytest -m "not gpu"` checks the sub-step
 // composition and the single normalisation adjoint against the float64 oracle without a GPU.  TEST INFRASTRUCTURE: nothing
 // in aircraft_amd loads this.
@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../aircraft_amd/csrc/ac_vjp.hpp"
+#include "../host_params.hpp"
 
 using namespace ac;
 
@@ -14,17 +15,22 @@ namespace {
 template <int MODEL>
 void run(const DevParams& P, int what, const float* X, const float* U, const float* dt, int dt_per_unit, const float* Lam, long n,
          float* Xbar, float* Ubar, float* dtbar) {
-    std::vector<float> col((size_t)vjp_lane_words(P.p.substeps));
-    const VjpColumn c{col.data(), 1};
-    for (long u = 0; u < n; ++u) {
-        float xv[13], uv[7], lam[13], gx[13], gu[7], gdt = 0.f;
-        for (int i = 0; i < 13; ++i) { xv[i] = X[i * n + u]; lam[i] = Lam[i * n + u]; }
-        for (int i = 0; i < 7; ++i) uv[i] = U[i * n + u];
-        if (what == 0) step_vjp_unit<MODEL>(P, xv, uv, dt_per_unit ? dt[u] : dt[0], lam, c, gx, gu, gdt);
-        else deriv_vjp_unit<MODEL>(P, xv, uv, lam, gx, gu);
-        for (int i = 0; i < 13; ++i) Xbar[i * n + u] = gx[i];
-        for (int i = 0; i < 7; ++i) Ubar[i * n + u] = gu[i];
-        dtbar[u] = gdt;
+    std::vector<float> colv((size_t)vjp_lane_words(P.p.substeps));
+    const VjpColumn col{colv.data(), 1};
+    AdjAnalyticCoeffs<MODEL> coeffs;
+    for (long i = 0; i < n; ++i) {
+        if (what == 0) {  // (k_step_vjp's lane)
+            step_vjp_lane(P, coeffs, col, X, U, dt[0], dt_per_unit ? dt : nullptr, Lam, n, i, Xbar, Ubar, dtbar);
+            continue;
+        }
+        float x[13], u[7], w[13], gx[13], gu[7];
+        load_rows<13>(X, n, i, x);
+        load_rows<7>(U, n, i, u);
+        load_rows<13>(Lam, n, i, w);
+        deriv_vjp_unit<MODEL>(P, x, u, w, gx, gu);
+        store_rows<13>(Xbar, n, i, gx);
+        store_rows<7>(Ubar, n, i, gu);
+        dtbar[i] = 0.f;
     }
 }
 
@@ -35,17 +41,7 @@ void run(const DevParams& P, int what, const float* X, const float* U, const flo
 extern "C" int host_vjp(const ac_params* p, const float* linear_W, const float* poly_coef, const float* poly_intercept, int what,
                         const float* X, const float* U, const float* dt, int dt_per_unit, const float* Lam, long n, float* Xbar,
                         float* Ubar, float* dtbar) {
-    DevParams P{};
-    P.p = *p;
-    if (linear_W) for (int i = 0; i < 36; ++i) P.linear_W[i] = linear_W[i];
-    alignas(64) static thread_local float tab[kPolyTabFloats];
-    if (poly_coef && poly_intercept) {
-        float grad[6 * 4 * 15], hess[6 * 10 * 5];
-        poly_gradient_tables(poly_coef, grad);
-        poly_hessian_tables(grad, hess);
-        poly_pack_tables(poly_coef, poly_intercept, grad, hess, tab);
-        P.poly_tab = tab;
-    }
+    const DevParams P = host_dev_params(p, linear_W, poly_coef, poly_intercept);
     if (P.p.substeps > kVjpMaxSubsteps) return -1;
 #define AC_CASE(M_) if (P.p.model_kind == M_) { run<M_>(P, what, X, U, dt, dt_per_unit, Lam, n, Xbar, Ubar, dtbar); return 0; }
     AC_CASE(AC_MODEL_DEFAULT) AC_CASE(AC_MODEL_LINEAR) AC_CASE(AC_MODEL_POLY)

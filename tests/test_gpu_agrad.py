@@ -144,21 +144,46 @@ def rollout_reference(model, B, H):
     return _ROLL_REF[(model, B, H)]
 
 
-@pytest.mark.parametrize("B", [1, 65])
-def test_rollout_airframe_grad_matches_central_differences(gpu, B):
+def rollout_case(gpu, B, H, grid=None):
+    """-> (errors per group of the rollout gradient through autodiff, the aircraft)"""
     from aircraft_amd import autodiff
 
-    H = 12
     X0, U, G, refs = rollout_reference("poly", B, H)
     ref, agree = R.check_reference(refs)
     ac = R.aircraft("poly")
+    if grid is not None:
+        ac.set_coef_grad_grid(grid)
     params = autodiff.AirframeParameters(ac)
     got = grads_through_params(params, lambda: (autodiff.rollout(ac, dev(X0, gpu), dev(U, gpu), DT, params=params) * dev(G, gpu)).sum())
     assert ac.last_launch()[0] == "k_rollout_agrad"
     errs = R.summed_errors(got, ref)
-    print(f"[agrad rollout] poly B={B} H={H} errs {errs} reference agreement {agree}")
-    parity_report("rollout_agrad", case="poly", B=B, H=H, worst_group=max(errs.values()), per_group=errs, reference_agreement=agree)
+    print(f"[agrad rollout] poly B={B} H={H} grid={ac.last_launch()[1]} errs {errs} reference agreement {agree}")
+    parity_report("rollout_agrad", case="poly", B=B, H=H, grid=ac.last_launch()[1], worst_group=max(errs.values()), per_group=errs,
+                  reference_agreement=agree)
+    return errs, ac
+
+
+@pytest.mark.parametrize("B", [1, 65])
+def test_rollout_airframe_grad_matches_central_differences(gpu, B):
+    errs, _ = rollout_case(gpu, B, 12)
     assert max(errs.values()) <= R.BAR_SUM, errs
+
+
+def test_rollout_airframe_grad_persistent_loop_and_ragged_tail(gpu):
+    errs, ac = rollout_case(gpu, 70, 3, grid=1)  # one workgroup over two tiles, the second of 6 instances
+    assert ac.last_launch()[1] == 1
+    assert max(errs.values()) <= R.BAR_SUM, errs
+
+
+def test_rollout_airframe_grad_zero_horizon(gpu):
+    """H = 0: X[0] = x0, no step and no airframe constant enters — G[0] passes through, everything else is zero."""
+    import torch
+
+    ac = R.aircraft("default")
+    X = torch.randn((1, 13, 70), device=gpu, generator=torch.Generator(device=gpu).manual_seed(3))
+    G = torch.randn((1, 13, 70), device=gpu, generator=torch.Generator(device=gpu).manual_seed(4))
+    phi, x0b, ub, db = ac.rollout_airframe_grad(X, torch.zeros((0, 7, 70), device=gpu), DT, G, out=torch.ones(22, device=gpu))
+    assert not phi.any() and torch.equal(x0b, G[0]) and ub.shape == (0, ac.num_controls, 70) and not db.any()
 
 
 @pytest.mark.parametrize("model", ["default", "poly"])

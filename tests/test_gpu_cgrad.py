@@ -122,22 +122,46 @@ def rollout_reference(B, H):
     return _ROLL_REF[(B, H)]
 
 
-@pytest.mark.parametrize("B", [1, 65])
-def test_rollout_coef_grad_matches_central_differences(gpu, B):
+def rollout_case(gpu, B, H, grid=None):
+    """-> (errors per tensor of the rollout gradient through autodiff, the aircraft)"""
     from aircraft_amd import autodiff
 
-    H = 12
     X0, U, G, refs = rollout_reference(B, H)
     want, agree = R.check_reference([R.summed(r) for r in refs])
     ac = make("poly")
+    if grid is not None:
+        ac.set_coef_grad_grid(grid)
     params = autodiff.CoefficientParameters(ac)
     got = grads_through_params(params, lambda: (autodiff.rollout(ac, dev(X0, gpu), dev(U, gpu), DT, params=params) * dev(G, gpu)).sum())
     assert ac.last_launch()[0] == "k_rollout_cgrad"
     errs = R.tensor_errors(got, want)
-    print(f"[cgrad rollout] poly B={B} H={H} errs {errs} reference agreement {agree}")
-    parity_report("rollout_cgrad", case="poly", B=B, H=H, worst_tensor_rel=max(errs.values()), per_tensor=errs,
-                  reference_agreement=agree)
+    print(f"[cgrad rollout] poly B={B} H={H} grid={ac.last_launch()[1]} errs {errs} reference agreement {agree}")
+    parity_report("rollout_cgrad", case="poly", B=B, H=H, grid=ac.last_launch()[1], worst_tensor_rel=max(errs.values()),
+                  per_tensor=errs, reference_agreement=agree)
+    return errs, ac
+
+
+@pytest.mark.parametrize("B", [1, 65])
+def test_rollout_coef_grad_matches_central_differences(gpu, B):
+    errs, _ = rollout_case(gpu, B, 12)
     assert max(errs.values()) < R.BAR, errs
+
+
+def test_rollout_coef_grad_persistent_loop_and_ragged_tail(gpu):
+    errs, ac = rollout_case(gpu, 70, 3, grid=1)  # one workgroup over two tiles, the second of 6 instances
+    assert ac.last_launch()[1] == 1
+    assert max(errs.values()) < R.BAR, errs
+
+
+def test_rollout_coef_grad_zero_horizon(gpu):
+    """H = 0: X[0] = x0, no step and no coefficient enters — G[0] passes through, everything else is zero."""
+    import torch
+
+    ac = make("poly")
+    X = torch.randn((1, 13, 70), device=gpu, generator=torch.Generator(device=gpu).manual_seed(3))
+    G = torch.randn((1, 13, 70), device=gpu, generator=torch.Generator(device=gpu).manual_seed(4))
+    th, x0b, ub, db = ac.rollout_coef_grad(X, torch.zeros((0, 7, 70), device=gpu), DT, G, out=torch.ones(210, device=gpu))
+    assert not th.any() and torch.equal(x0b, G[0]) and ub.shape == (0, ac.num_controls, 70) and not db.any()
 
 
 @pytest.mark.parametrize("model,H", [("linear", 6), ("poly", 6)])

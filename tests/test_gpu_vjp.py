@@ -119,13 +119,13 @@ def test_state_derivative_vjp_matches_oracle(gpu, name):
 ROLLOUT_DT = {"default": 0.002, "linear": 0.002}  # (their crude fits leave RK4's stability region at dt = 0.01 near trim)
 
 
-def rollout_problem(name, B, H, seed, gpu):
+def rollout_problem(name, B, H, seed, gpu, substeps=1):
     """-> ac, oracle, the GPU's trajectory (H+1, 13, B), U, cotangent G, dt"""
     import torch
 
     from tests.helpers import near_trim_problem
 
-    ac, orc = make(name)
+    ac, orc = make(name, substeps=substeps)
     X0, U = near_trim_problem(B, H, seed=seed)  # trajectories that stay inside the flight envelope
     U = f32_exact(U)
     rng = np.random.default_rng(seed)
@@ -177,6 +177,31 @@ def test_rollout_vjp_matches_float64_chain(gpu, name):
         _, cond = conditioning(orc, host(Xtraj)[0][:, loose], U[:, :, loose], dt)
         parity_report("rollout_vjp_loose", model=name, instances=loose.tolist(), err=err[loose].tolist(), conditioning=cond.tolist())
     assert ac.last_launch()[0] == ("k_vjp_recur" if name == "real_net" else "k_rollout_vjp")
+
+
+@pytest.mark.parametrize("substeps", [1, 3])
+def test_rollout_vjp_ragged_tile_and_substeps(gpu, substeps):
+    """B = 70: two tiles, the second of 6 instances; three sub-steps per node through the LDS column."""
+    ac, orc, Xtraj, U, G, dt = rollout_problem("poly", 70, 3, seed=63, gpu=gpu, substeps=substeps)
+    x0b, ub, db = ac.rollout_vjp(Xtraj, dev(U, gpu), dt, dev(G, gpu))
+    assert ac.last_launch()[:2] == ("k_rollout_vjp", 2)
+    want = chain_vjp(orc, host(Xtraj), U, G, dt)
+    err = instance_rel((host(x0b), host(ub), host(db)), want)
+    parity_report("rollout_vjp_ragged", model="poly", substeps=substeps, worst=float(err.max()), frac_2e5=float((err < 2e-5).mean()))
+    assert err.max() < 1e-4, (int(err.argmax()), float(err.max()))
+    assert (err < 2e-5).mean() >= 0.98
+
+
+@pytest.mark.parametrize("name", ["poly", "real_net"])
+def test_rollout_vjp_zero_horizon(gpu, name):
+    """H = 0 on the fused and the composed route: X[0] = x0, the cotangent passes through and dt does not enter."""
+    import torch
+
+    ac, _ = make(name)
+    X = torch.randn((1, 13, 70), device=gpu, generator=torch.Generator(device=gpu).manual_seed(3))
+    G = torch.randn((1, 13, 70), device=gpu, generator=torch.Generator(device=gpu).manual_seed(4))
+    x0b, ub, db = ac.rollout_vjp(X, torch.zeros((0, 7, 70), device=gpu), 0.01, G)
+    assert torch.equal(x0b, G[0]) and ub.shape == (0, ac.num_controls, 70) and not db.any()
 
 
 # ---- 3. fused route equals composed route ---------------------------------------------------------------------------------------
