@@ -31,6 +31,7 @@ UNIT_FLAGS = {
     # the same two kernels with the hidden layers on two-plane f16 MFMA (the route ac_set_mlp's gate picks; bf16 is the fall-back)
     "nn_inst_wt8_f16_sens": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],
     "nn_inst_wt8_f16_pair": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],
+    "nn_inst_wt8_f16_sens_r3": ["-DAC_CH=2", "-mllvm", "-slp-threshold=6", "-mllvm", "-amdgpu-mfma-vgpr-form"],  # (three-region ring)
 }
 
 

@@ -35,7 +35,9 @@ constexpr bool kBf16Hidden = true;
 #endif
 // How an engine runs its hidden layers: fp32 MFMA / vector ALUs (layer), three-plane bf16 MFMA or two-plane f16 MFMA (layer_bf).
 // The f16 form is a choice per NET (ac_set_mlp's range gate, ac_f16_pack.hpp); the bf16 kernels are its fall-back.
-constexpr int kHiddenFp32 = 0, kHiddenBf16 = 1, kHiddenF16 = 2;
+// kHiddenF16Ring3: the f16 form on the three-region ring of the bf16 route, for a net whose four-region ring does not fit
+// the LDS (f16_ring4_lds, ac_mlp_plan.hpp); the one-wave kHiddenF16 engine streams through four regions (acquire()).
+constexpr int kHiddenFp32 = 0, kHiddenBf16 = 1, kHiddenF16 = 2, kHiddenF16Ring3 = 3;
 constexpr int kDefaultHidden = kBf16Hidden ? kHiddenBf16 : kHiddenFp32;
 
 // ---- 16x16x4 fp32 matrix-multiply-accumulate on one wave -------------------------------------
@@ -122,7 +124,9 @@ template <int NSLAB, int WT, bool USE_MFMA, bool TANGENT = (NSLAB == 6), bool SE
           int HID = kHiddenFp32>
 struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHiddenFp32> {
     static constexpr bool BF = HID != kHiddenFp32;   // hidden layers through layer_bf (plane operands, half-layer ring)
-    static constexpr bool F16 = HID == kHiddenF16;
+    static constexpr bool F16 = HID == kHiddenF16 || HID == kHiddenF16Ring3;
+    // Four-region ring (the one-wave f16 engine): two slots of (front, back), layer l whole in slot l mod 2 — see acquire()
+    static constexpr bool kRing4 = HID == kHiddenF16 && PAIR == 0;
     static constexpr int NP = F16 ? 2 : 3;           // planes per operand
     static constexpr int NPROD = F16 ? 3 : 6;        // plane products (MFMAs) per output tile and k-chunk
     using TripleHolder<SECOND && NSLAB <= 10>::tri;
@@ -207,9 +211,11 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
         for (int l = 0; l < plan.n_layers; ++l)
             if (plan.lds_off[l] >= 0) lds_dma_copy(gblob + plan.g_off[l], lds + plan.lds_off[l], plan.bytes[l], wave, nwaves, lane);
         if constexpr (BF) {
-            // three-region ring: the front half of the first hidden layer into region 0 (the wave-pair ring loads on acquire)
+            // three-region ring: the front half of the first hidden layer into region 0 (the wave-pair ring loads on acquire);
+            // four-region ring: the whole layer into slot 0 (front and back are adjacent in the blob and in the ring)
             if (!kPairRing && plan.n_streamed > 0)
-                lds_dma_copy(gblob + plan.g_off[plan.first_streamed], lds + plan.bf_region[0], kBfFront, wave, nwaves, lane);
+                lds_dma_copy(gblob + plan.g_off[plan.first_streamed], lds + plan.bf_region[0], kRing4 ? kBfFront + kBfBack : kBfFront,
+                             wave, nwaves, lane);
         } else if (plan.n_streamed > 0) {
             const int l = plan.first_streamed;
             lds_dma_copy(gblob + plan.g_off[l], lds + plan.ring_off[0], plan.bytes[l], wave, nwaves, lane);
@@ -425,6 +431,8 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
     static constexpr int KC = WT / 2;  // 32-deep k-chunks
     static constexpr bool kPairRing = PAIR != 0;
     static constexpr int kBfFront = (WT / 2) * KC * NP * 1024 + 1024, kBfBack = (WT / 2) * KC * NP * 1024;
+    static constexpr int kRing4Pieces = (kBfFront + kBfBack) >> 10;  // four-region ring: 65 pieces to a layer ...
+    static constexpr int kRing4PerWave = (kRing4Pieces + 3) / 4;      // ... 17 issue points to each of the four waves
 
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     AC_DI static unsigned cvt_pk_bf16(f32x2 xy) {
@@ -492,6 +500,7 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(v) : "v"(lds_addr), "i"(off));
         return v;
     }
+    AC_DI static unsigned lds_addr(const char* p) { return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p; }
     AC_DI static void wait_frags() {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -622,14 +631,17 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
     // Stages a gap takes before the next gap gets any: bf16 one (12 gaps to a block: its fullest block, a tanh tile, fills
     // them one each).  f16 has the same units in the same blocks and half the gaps, so a block's stages are dealt level:
     // ceil(stages of the block / gaps) to a gap.
-    AC_DI static constexpr int gap_share(int S, int B) {
-        if (!F16) return 1;
+    AC_DI static constexpr int block_stages(int S, int B) {  // stages block B of slab S carries
         int t = 0;
         for (int u = 0; u < NU; ++u) {
             const int us = unit_slab(S, B, u);
             if (us >= 0) t += unit_stages(us, u);
         }
-        const int per = (t + NGAP - 1) / NGAP;
+        return t;
+    }
+    AC_DI static constexpr int gap_share(int S, int B) {
+        if (!F16) return 1;
+        const int per = (block_stages(S, B) + NGAP - 1) / NGAP;
         return per < 1 ? 1 : per;
     }
     static constexpr int kSumGap = F16 ? NGAP / 2 : 4;  // first gap of a block that may carry a hi + lo sum
@@ -647,6 +659,44 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
                 if ((j / per < NGAP ? j / per : NGAP - 1) == J && n-- == 0) return u * 16 + k;
         }
         return -1;
+    }
+    AC_DI static constexpr int gap_stages(int S, int B, int J) {  // stages gap J carries
+        int n = 0;
+        while (gap_stage(S, B, J, n) >= 0) ++n;
+        return n;
+    }
+
+    // Four-region ring: where a wave issues its kRing4PerWave requests for the next layer, one piece to a gap.  Not at the
+    // head of the layer and not in slabs 0 and 1 (the exposed splits, the bias reads, the tanh tiles): slabs 2 to NSLAB - 2
+    // take an equal share each (the remainder to the first of them), in the blocks of the slab that carry the fewest
+    // stages, earlier ones first among equals.  None in the last slab, so the request is complete a slab before the layer
+    // ends (measured against slabs 2 to NSLAB - 1 with the last slab's share in its first half: the wait at the next
+    // layer's head and slab 0 were 170 cycles per layer call longer).  ord[B]: the issue point of block B
+    // of slab S (ring4_piece), -1: none.
+    static constexpr int kRing4Slab0 = 2, kRing4Slab1 = NSLAB - 1;  // slabs [kRing4Slab0, kRing4Slab1)
+    struct Ring4Slab { int ord[NB > 0 ? NB : 1]; };
+    AC_DI static constexpr int ring4_count(int S) {
+        constexpr int n = kRing4Slab1 - kRing4Slab0 > 0 ? kRing4Slab1 - kRing4Slab0 : 1;
+        return (S < kRing4Slab0 || S >= kRing4Slab1) ? 0 : kRing4PerWave / n + (S - kRing4Slab0 < kRing4PerWave % n ? 1 : 0);
+    }
+    AC_DI static constexpr Ring4Slab ring4_slab(int S) {
+        Ring4Slab r{};
+        int load[NB > 0 ? NB : 1] = {}, first = 0;
+        for (int s = kRing4Slab0; s < S; ++s) first += ring4_count(s);
+        for (int b = 0; b < NB; ++b) load[b] = block_stages(S, b);
+        for (int b = 0, o = first; b < NB; ++b) {
+            int rank = 0;
+            for (int c = 0; c < NB; ++c) rank += load[c] < load[b] || (load[c] == load[b] && c < b);
+            r.ord[b] = rank < ring4_count(S) ? o++ : -1;
+        }
+        return r;
+    }
+    // ... and in the gap of that block that carries the fewest stages, behind the block's fragment reads; the latest of equals
+    AC_DI static constexpr int ring4_gap(int S, int B) {
+        int best = NP * CH;
+        for (int J = NP * CH + 1; J < NGAP; ++J)
+            if (gap_stages(S, B, J) <= gap_stages(S, B, best)) best = J;
+        return best;
     }
 
     // Registers of one layer_bf call (every index into them is a compile-time constant: they stay registers).
@@ -765,6 +815,10 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
         else r.hi[S & 1][nc + i] = mfma_bf(r.w[cur][i][wp], x, r.hi[S & 1][nc + i]);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (more && J < NP * CH) r.w[cur ^ 1][J / NP][J % NP] = bf_frag(r, nnc + J / NP, nkc, J % NP);
+        if constexpr (kRing4 && S >= kRing4Slab0 && J >= NP * CH) {  // four-region ring: one piece of the next layer
+            constexpr int ord = ring4_slab(S).ord[B];
+            if constexpr (ord >= 0 && J == ring4_gap(S, B)) ring4_piece<ord>(r.la0);
+        }
         static_assert(F16 || gap_stage(S, B, J, 2) < 0, "at most two stages to a gap");
         bf_gap_stages<S, B, J, 0>(r);
         __builtin_amdgcn_sched_barrier(0);
@@ -775,8 +829,9 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
         constexpr int nc = blk_group(B) * CH, c = blk_chunk(B);
         constexpr int nnc = blk_group((B + 1) % NB) * CH;
         __builtin_amdgcn_sched_barrier(0);
-        // slab 0 about to enter the back half: wait for it before the first read of it
-        if constexpr (S == 0 && nc < WT / 2 && nnc >= WT / 2) { mid_layer(); __builtin_amdgcn_sched_barrier(0); }
+        // slab 0 about to enter the back half: wait for it before the first read of it (four-region ring: the whole layer
+        // landed before the barrier at its head)
+        if constexpr (!kRing4 && S == 0 && nc < WT / 2 && nnc >= WT / 2) { mid_layer(); __builtin_amdgcn_sched_barrier(0); }
         // this block's fragments (requested during the previous block) have landed
         wait_frags();
         if constexpr (c == 0) {
@@ -809,13 +864,13 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
 
     AC_DI void layer_bf(const char* wfront) {
         const frag8* wf0 = reinterpret_cast<const frag8*>(wfront) + lane;
-        const frag8* wf1 = reinterpret_cast<const frag8*>(this->bf_back) + lane;
+        const frag8* wf1 = reinterpret_cast<const frag8*>(kRing4 ? wfront + kBfFront : this->bf_back) + lane;
         static_assert(WT % CH == 0 && (WT / 2) % CH == 0 && CH < KC, "a chunk of output tiles lies in one half");
         static_assert((WT / 2) * KC * NP * 1024 <= 65536, "a half-layer fits the ds_read immediate offset");
         BfRegs r;
         // LDS addresses of this lane's piece in the two halves (generic -> LDS pointer: the low 32 bits)
-        r.la0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf0;
-        r.la1 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)wf1;
+        r.la0 = lds_addr((const char*)wf0);
+        r.la1 = lds_addr((const char*)wf1);
         r.bias4 = reinterpret_cast<const f32x4*>(wfront + kBfBack);
 #pragma unroll
         for (int i = 0; i < CH; ++i)
@@ -1249,6 +1304,19 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
         }
     }
 
+    // Issue point `ord` of the request for the next layer: piece wave + 4 ord (the last point: the last piece, from every
+    // wave — the same bytes to the same place).  One wave-instruction: a scalar base and the 32-bit vector offset the layer's
+    // fragment reads keep anyway (la0: the lane's LDS address in the front half, which acquire() took off dma_src).
+    template <int ORD> AC_DI void ring4_piece(unsigned la0) {
+        static_assert(ORD >= 0 && ORD < kRing4PerWave, "issue point");
+        unsigned pc = (unsigned)(4 * ORD) << 10;
+        if constexpr (4 * ORD + 4 > kRing4Pieces) pc = ((unsigned)(kRing4Pieces - 1) - (unsigned)__builtin_amdgcn_readfirstlane(wave)) << 10;
+        const char* sb = dma_src + pc;
+        asm volatile("" : "+s"(sb));  // the base stays scalar: summed with the lane offset first it is a 64-bit vector add per piece
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + (size_t)la0),
+                                         (__attribute__((address_space(3))) void*)(lds + dma_dst + pc), 16, 0, 0);
+    }
+
     // LDS address of layer l's block; for a streamed layer: wait for its DMA, then (the barrier having
     // proven every wave is done with the other slot) request the next streamed layer into that slot.
     AC_DI const char* acquire(int l) {
@@ -1262,7 +1330,26 @@ struct MlpEngine : TripleHolder<SECOND && NSLAB <= 10>, BfRingState<HID != kHidd
             // it has 1/12 of a layer to land: mid_layer() waits for it), and the next layer's front into the previous layer's
             // back region behind the mid-layer barrier.  The wave-pair kernel (less LDS: two regions) loads both halves here.
             const float* src = gblob + plan.g_off[l];
-            if constexpr (kPairRing) {
+            if constexpr (kRing4) {
+                // Four regions = two slots of (front, back); layer l lies whole in slot l mod 2, requested during the layer
+                // before (ring4_piece, in the gaps of slabs 2 to NSLAB - 2), so the wait above is for a request a layer old.
+                // The barrier above is the only one of a hidden layer.  It proves that every wave has finished the previous
+                // layer, so that layer's slot may be overwritten from here on: the next layer is requested into it behind
+                // this barrier and nowhere else.  That is the whole write-after-read argument.  (Read-after-write: a wave
+                // waits for its own pieces of a layer in front of the barrier at the layer's head.)
+                (void)src;
+                const Ring4Step step = f16_ring4_step(plan, ring_pos, snext);
+                snext = step.snext;
+                ++ring_pos;
+                // (both start at this wave's first piece, piece `wave`; the source less the LDS address of the layer read now:
+                // ring4_piece adds the lane's fragment address in that layer, 16 lane beyond it, as the vector offset)
+                const char* wl = lds + f16_ring4_slot(plan, step.read_slot);
+                const unsigned w0 = (unsigned)__builtin_amdgcn_readfirstlane(wave) << 10;
+                dma_src = (const char*)(gblob + __builtin_amdgcn_readfirstlane(plan.g_off[step.next_layer])) + w0 -
+                          (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr(wl));
+                dma_dst = (unsigned)__builtin_amdgcn_readfirstlane(f16_ring4_slot(plan, step.next_slot)) + w0;
+                return wl;
+            } else if constexpr (kPairRing) {
                 lds_dma_copy(src, lds + plan.bf_region[0], kBfFront, wave, nwaves, lane);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();

@@ -13,8 +13,6 @@
 
 namespace ac {
 
-constexpr int kLdsBudget = 160 * 1024;  // gfx950 LDS per workgroup
-
 // What the handle keeps of a model once blob and image are on the device.
 struct MlpModelInfo {
     MlpPlan plan;
@@ -26,6 +24,7 @@ struct MlpModelInfo {
     MlpPlan plan_f16_pair;  // passes the range gate (f16_gate); plan_bf / plan_bf_pair stay its fall-back
     bool has_bf;
     int f16_gate;           // F16Gate code of the net (0: passes); meaningful when has_bf
+    int f16_ring4_lds;      // LDS bytes of the one-wave f16 kernel on its four-region ring (f16_ring4_lds); 0: three regions
     bool has_rev;           // reverse sweep of k_nn_stage_tensors_rev (ac_hess_rev.hpp); rev_layers = layers of the net itself
     int rev_layers;
     int wt;                 // register tiles per slab the plan needs (2, 4 or 8)
@@ -324,6 +323,7 @@ inline int build_mlp_model(int n_layers, const int* widths, const int* act, cons
     }
     m.plan_bf_pair = want_bf ? drop_third_region(m.plan_bf) : ps;
     m.plan_f16_pair = want_bf ? drop_third_region(m.plan_f16) : ps;
+    m.f16_ring4_lds = want_bf ? f16_ring4_lds(m.plan_f16, f16_front_bytes(wt)) : 0;
     MlpPlan& pr = m.plan_rev = ps;
     if (want_rev) {
         for (int i = 0; i < n_hid; ++i) {

@@ -88,6 +88,7 @@ struct ac_handle : MlpModelInfo {
     // measurement aids, diagnostic flavours only (-DAC_DIAG_ENV; always false in the product library):
     bool no_pair;  // AIRCRAFT_HIP_NO_PAIR=1: never route a remainder to k_nn_step_sens_pair
     bool all_pair; // AIRCRAFT_HIP_ALL_PAIR=1: every unit through k_nn_step_sens_pair
+    bool f16_ring3; // AIRCRAFT_HIP_F16_RING3=1: the one-wave f16 kernel on the three-region ring (as a net whose fourth region does not fit)
     bool has_linear, has_poly, has_mlp;
     int hidden_route;       // ac_hidden_route (ac_set_hidden_route); 0 = AC_HIDDEN_AUTO
     float* d_rev_scratch;  // per-wave layer states of k_nn_stage_tensors_rev (ac_reserve_hess_workspace)
@@ -487,6 +488,8 @@ int ac_create(const ac_params* params, ac_handle** out) {
         h->no_pair = e && e[0] == '1';
         const char* ea = getenv("AIRCRAFT_HIP_ALL_PAIR");
         h->all_pair = ea && ea[0] == '1';
+        const char* e3 = getenv("AIRCRAFT_HIP_F16_RING3");
+        h->f16_ring3 = e3 && e3[0] == '1';
         // AIRCRAFT_HIP_HIDDEN_ROUTE=bf16|f16: the handle's initial hidden-layer route (ac_set_hidden_route overrides it)
         const char* er = getenv("AIRCRAFT_HIP_HIDDEN_ROUTE");
         if (er && !strcmp(er, "bf16")) h->hidden_route = AC_HIDDEN_BF16;
@@ -890,11 +893,16 @@ static int sens_impl(ac_handle* h, const float* X, const float* U, float dt, con
             const int grid = (int)((n_main + 63) / 64);  // (A/B flavour: a workgroup per task, as in round 2)
 #endif
             const MlpPlan& plan = f16 ? h->plan_f16 : bf ? h->plan_bf : engine_plan(h);
+            // the f16 kernel streams whole layers through FOUR half-layer regions, the fourth behind the plan's three
+            // (f16_ring4_lds, ac_mlp_plan.hpp); a net whose fourth region does not fit keeps the three-region kernel
+            const bool ring4 = f16 && h->f16_ring4_lds > 0 && !h->f16_ring3;
+            const int lds_main = ring4 ? h->f16_ring4_lds : plan.lds_total;
             auto launch_main = [&](auto kern) {
-                return launch_kernel(h, st, "k_nn_step_sens", kern, grid, kBlock, plan.lds_total, h->dp, plan, h->d_blob, X, U, dt,
+                return launch_kernel(h, st, "k_nn_step_sens", kern, grid, kBlock, lds_main, h->dp, plan, h->d_blob, X, U, dt,
                                  dt_per_unit, n_main, blk, Xn, A, Bm, c);
             };
-            const int rc_m = f16 ? launch_main(k_nn_step_sens<8, true, kHiddenF16>)
+            const int rc_m = ring4 ? launch_main(k_nn_step_sens<8, true, kHiddenF16>)
+                                 : f16 ? launch_main(k_nn_step_sens<8, true, kHiddenF16Ring3>)
                                  : instance(pick_wt_mfma(h, [&](auto WT, auto MF) { return launch_main(k_nn_step_sens<WT(), MF()>); }),
                                             kNoNnInstance);
             if (rc_m != AC_OK) return rc_m;
