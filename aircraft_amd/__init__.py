@@ -7,7 +7,7 @@ include/aircraft_hip.h.  PyTorch is used for device buffers, streams and torch.d
 """
 from .utils import AircraftConfiguration, TrajectoryConfiguration, MlpData, load_model, load_poly, load_linear
 from .dynamics.base import SixDOF, SixDOFOpts, BatchedFunction
-from .dynamics.aircraft import EKF, UKF, Aircraft, AircraftOpts, EkfNoiseFit, EkfNoiseStats, EkfSmooth, EkfTrace, LqgResult, LqrResult, ModesResult, SensorModel, TrimResult
+from .dynamics.aircraft import EKF, UKF, Aircraft, AircraftOpts, EkfMapSmooth, EkfNoiseFit, EkfNoiseStats, EkfSmooth, EkfTrace, LqgResult, LqrResult, ModesResult, SensorModel, TrimResult
 from .dynamics.quadrotor import Quadrotor
 from .dynamics.coefficient_models import (COEFF_MODEL_REGISTRY, CoefficientModel, DefaultModel, LinearModel,
                                           NeuralModel, PolynomialModel)
@@ -17,7 +17,7 @@ from . import autodiff
 
 __all__ = [
     "AircraftConfiguration", "TrajectoryConfiguration", "MlpData", "load_model", "load_poly", "load_linear",
-    "SixDOF", "SixDOFOpts", "BatchedFunction", "Aircraft", "AircraftOpts", "TrimResult", "LqrResult", "ModesResult", "EKF", "UKF", "EkfTrace", "EkfSmooth", "EkfNoiseStats", "EkfNoiseFit", "SensorModel", "LqgResult", "Quadrotor", "COEFF_MODEL_REGISTRY",
+    "SixDOF", "SixDOFOpts", "BatchedFunction", "Aircraft", "AircraftOpts", "TrimResult", "LqrResult", "ModesResult", "EKF", "UKF", "EkfTrace", "EkfSmooth", "EkfMapSmooth", "EkfNoiseStats", "EkfNoiseFit", "SensorModel", "LqgResult", "Quadrotor", "COEFF_MODEL_REGISTRY",
     "CoefficientModel", "DefaultModel", "LinearModel", "NeuralModel", "PolynomialModel", "AircraftHipError",
     "TrajectoryData", "load_trajectory", "save_trajectory", "autodiff",
 ]

@@ -32,6 +32,9 @@ LQG_GROUPS = 5                                        # ac_sense_opts: GPS p, GP
 RTS_NOT_PD, RTS_NONFINITE = 1, 2                      # ac_ekf_smooth_f32 status bits per link and instance
 EM_NOT_PD, EM_NONFINITE = 1, 2                        # ac_ekf_em_f32 status values per node and instance
 EM_CHUNK = 32                                         # ac_ekf_em_f32: nodes per float64 partial sum (kEmChunk)
+IEKS_P0_NOT_PD, IEKS_NONFINITE, IEKS_QZERO_DEFECT, IEKS_NO_DECREASE = 1, 2, 4, 8  # ac_ieks_cost_f32 / ac_ieks_solve_f32 status bits
+IEKS_CHUNK = 32                                       # ac_ieks_cost_f32: nodes per float64 partial sum (kIeksChunk)
+IEKS_MAX_CANDIDATES = 8                               # longest ladder of ac_ieks_*
 EIG_STATUS = {0: "converged", 1: "max_iter", 3: "non_finite"}  # ac_eig_f32 / ac_modes_f32 status per instance
 EIG_MAX_M = 13                                        # ac_eig_f32: 1 <= m <= 13
 MODES_FLIGHT = 0xEF8                                  # ac_modes_opts.coords: chart coordinates 3-7 and 9-11
@@ -263,6 +266,16 @@ PROTOTYPES = {
     "ac_ekf_em_workspace_floats": (C.c_int, [_VP, C.c_long, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_ekf_em_f32": (C.c_int, [_VP, C.POINTER(EkfEmOpts), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP,
                                 _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "ac_ieks_workspace_floats": (C.c_int, [_VP, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_size_t)]),
+    "ac_ieks_pass_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long]
+                         + [_VP] * 12 + [C.c_size_t, _VP]),
+    "ac_ieks_cost_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long,
+                                   C.c_long] + [_VP] * 6 + [C.c_size_t, _VP]),
+    "ac_ieks_candidates_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_float), C.c_int, C.c_long, C.c_long, _VP, _VP, _VP]),
+    "ac_ieks_accept_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_float), C.c_int, C.c_long, C.c_long, _VP, _VP, _VP, _VP,
+                                     _VP]),
+    "ac_ieks_solve_f32": (C.c_int, [_VP, C.POINTER(EkfOpts), _VP, _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP, C.c_long, C.c_long,
+                                    C.c_int, C.POINTER(C.c_float), C.c_int] + [_VP] * 19 + [C.c_size_t, _VP]),
     "ac_eig_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP]),
     "ac_modes_workspace_floats": (C.c_int, [_VP, C.c_long, C.POINTER(C.c_size_t)]),
     "ac_modes_f32": (C.c_int, [_VP, C.POINTER(ModesOpts), _VP, _VP, C.c_float, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,

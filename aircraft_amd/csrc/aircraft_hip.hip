@@ -31,6 +31,7 @@
 #include "ac_ekf.hpp"
 #include "ac_rts.hpp"
 #include "ac_em.hpp"
+#include "ac_ieks.hpp"
 #include "ac_ukf.hpp"
 #include "ac_lqg.hpp"
 #include "ac_wgrad.hpp"
@@ -2812,6 +2813,212 @@ int ac_ekf_em_f32(ac_handle* h, const ac_ekf_em_opts* o, const float* Xpred, con
     AC_HIP(em_launch(io, (hipStream_t)stream, &grid, &lds));
     note_launch(h, T > 0 ? "k_ekf_em_nodes" : "k_ekf_em_reduce", grid, kEmGroups * kEkfLanes, lds);
     return AC_OK;
+}
+
+// ---- iterated extended Kalman smoother (ac_ieks.hpp, ieks_inst.hip) -----------------------------------------------------------------
+namespace {
+// The workspace: F [T][13][n] | A [T][169][n] | B [T][91][n] (the pass) | the cost's region for `cols` columns: F [T][13][cols] |
+// partial sums [chunks][2][cols] float64 | status [chunks][cols] int32 | then the solve's own: Xc [T+1][13][cols] | Uc [T][7][cols] |
+// Jc [cols] | stc [cols] int32 | the smoother's status [T][n] int32.  Every buffer starts on a 256-byte boundary.
+struct IeksCostWs {
+    float* Fc;
+    double* part;
+    int* pst;
+    float* end;
+    IeksCostWs(float* ws, size_t cols, size_t K) {
+        Fc = align256(ws);
+        part = (double*)align256(Fc + K * 13 * cols);
+        pst = (int*)align256((float*)part + (size_t)ieks_chunks((long)K) * 4 * cols);
+        end = (float*)pst + (size_t)ieks_chunks((long)K) * cols;
+    }
+};
+struct IeksWs {
+    float *F, *A, *Bm, *cost, *Xc, *Uc, *Jc, *end;
+    int *stc, *rst;
+    float* pass_end;
+    IeksWs(float* ws, size_t N, size_t K, size_t C) {
+        const size_t cols = N * (C ? C : 1);
+        F = align256(ws);
+        A = align256(F + K * 13 * N);
+        Bm = align256(A + K * 169 * N);
+        pass_end = Bm + K * 91 * N;
+        cost = align256(pass_end);
+        Xc = align256(IeksCostWs(cost, cols, K).end);
+        Uc = align256(Xc + (K + 1) * 13 * cols);
+        Jc = align256(Uc + K * 7 * cols);
+        stc = (int*)align256(Jc + cols);
+        rst = (int*)align256((float*)stc + cols);
+        end = (float*)rst + K * N;
+    }
+};
+constexpr size_t kIeksWsPad = 11 * 64;
+size_t ieks_pass_floats(long n, long T) { return (size_t)(IeksWs(nullptr, (size_t)n, (size_t)T, 1).pass_end - (float*)nullptr) + 3 * 64; }
+size_t ieks_cost_floats(long cols, long T) { return (size_t)(IeksCostWs(nullptr, (size_t)cols, (size_t)T).end - (float*)nullptr) + 3 * 64; }
+size_t ieks_ws_floats(long n, long T, int C) { return (size_t)(IeksWs(nullptr, (size_t)n, (size_t)T, (size_t)C).end - (float*)nullptr) + kIeksWsPad; }
+const char* const kIeksFixedWing = "the iterated Kalman smoother is defined for the fixed-wing models only";
+
+int ieks_ladder(const float* ladder, int candidates, IeksLadder* lad) {
+    if (!ladder || candidates < 1 || candidates > kIeksMaxCand) return fail(AC_ERR_BAD_ARG, "ieks: the ladder has 1 .. 8 values");
+    lad->count = candidates;
+    for (int c = 0; c < kIeksMaxCand; ++c) lad->a[c] = 0.f;
+    for (int c = 0; c < candidates; ++c) {
+        if (!(ladder[c] > 0.f) || !(ladder[c] <= 1.0f)) return fail(AC_ERR_BAD_ARG, "ieks: the ladder's values must lie in (0, 1]");
+        lad->a[c] = ladder[c];
+    }
+    return AC_OK;
+}
+
+// the checks the entry points share; *go = false: nothing to do (AC_OK)
+int ieks_check(ac_handle* h, const ac_ekf_opts* o, float dt, long n, long T, bool* go) {
+    *go = false;
+    if (!h || !o || n < 0 || T < 0) return AC_ERR_BAD_ARG;
+    if (!(dt > 0.f) || !(dt <= 3.0e38f)) return fail(AC_ERR_BAD_ARG, "ieks: dt must be finite and > 0");
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kIeksFixedWing);
+    if (n == 0 || T == 0) return AC_OK;
+    if (T + 1 > 2147483647L / ((n * kIeksMaxCand + kIeksBlock - 1) / kIeksBlock + 1)) return fail(AC_ERR_BAD_ARG, "ieks: n * T exceeds the launch dimension");
+    const int rc = model_ready(h);
+    if (rc != AC_OK) return rc;
+    *go = true;
+    return AC_OK;
+}
+
+int ieks_pass_impl(ac_handle* h, const ac_ekf_opts* o, const float* X0, const float* P0, const float* Xbar, const float* U, float dt,
+                   const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xs, float* Ps, float* ll,
+                   float* nu, float* S, float* nis, int* used, int* status, float* Xpreds, float* Ppreds, float* Abars, float* ws,
+                   void* stream) {
+    const IeksWs w(ws, (size_t)n, (size_t)T, 1);
+    const int rc = sens_impl(h, Xbar, U, dt, nullptr, n * T, n, w.F, w.A, w.Bm, nullptr, stream);
+    if (rc != AC_OK) return rc;
+    const IeksIo io{X0, P0, Xbar, w.F, w.A, Z, Qd, Rd, mask, Xs, Ps, ll, nu, S, nis, used, status, Xpreds, Ppreds, Abars, n, T};
+    int grid = 0, lds = 0;
+    AC_HIP(ieks_launch_filter(*o, h->dp.p.epsilon, io, (hipStream_t)stream, &grid, &lds));
+    note_launch(h, "k_ieks_filter", grid, kIeksGroups * kEkfLanes, lds);
+    return AC_OK;
+}
+
+// wsc: a region of at least ieks_cost_floats(reps n, T) floats
+int ieks_cost_impl(ac_handle* h, const ac_ekf_opts* o, const float* X0, const float* P0, const float* Xt, const float* Ut, float dt,
+                   const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long reps, long T, float* J, float* Jprior,
+                   float* Jproc, float* Jmeas, int* status, float* wsc, void* stream) {
+    const long cols = n * reps;
+    const IeksCostWs w(wsc, (size_t)cols, (size_t)T);
+    const int rc = step_impl(h, Xt, Ut, dt, nullptr, cols * T, cols, w.Fc, stream);
+    if (rc != AC_OK) return rc;
+    const IeksCostIo io{X0, P0, Xt, w.Fc, Z, Qd, Rd, mask, w.part, w.pst, J, Jprior, Jproc, Jmeas, status,
+                        {o->mag_ned[0], o->mag_ned[1], o->mag_ned[2]}, h->dp.p.epsilon, n, reps, T};
+    int grid = 0;
+    AC_HIP(ieks_launch_cost(io, (hipStream_t)stream, &grid));
+    note_launch(h, "k_ieks_cost_nodes", grid, kIeksBlock, 0);
+    return AC_OK;
+}
+}  // namespace
+
+int ac_ieks_workspace_floats(const ac_handle* h, long n, long T, int candidates, size_t* floats) {
+    if (!h || !floats || n < 0 || T < 0 || candidates < 0 || candidates > kIeksMaxCand) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kIeksFixedWing);
+    *floats = ieks_ws_floats(n, T, candidates);
+    return AC_OK;
+}
+
+int ac_ieks_pass_f32(ac_handle* h, const ac_ekf_opts* o, const float* X0, const float* P0, const float* Xbar, const float* U, float dt,
+                     const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T, float* Xs, float* Ps, float* ll,
+                     float* nu, float* S, float* nis, int* used, int* status, float* Xpreds, float* Ppreds, float* Abars, float* ws,
+                     size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    bool go = false;
+    const int rc = ieks_check(h, o, dt, n, T, &go);
+    if (rc != AC_OK || !go) return rc;
+    if (!X0 || !P0 || !Xbar || !U || !Z || !Qd || !Rd || !Xs || !Ps || !Xpreds || !Ppreds || !Abars)
+        return fail(AC_ERR_BAD_ARG, "ieks pass: a required pointer is NULL");
+    if (!ws || ws_floats < ieks_pass_floats(n, T)) return fail(AC_ERR_WORKSPACE, "ieks workspace too small: see ac_ieks_workspace_floats");
+    return ieks_pass_impl(h, o, X0, P0, Xbar, U, dt, Z, mask, Qd, Rd, n, T, Xs, Ps, ll, nu, S, nis, used, status, Xpreds, Ppreds, Abars,
+                          ws, stream);
+}
+
+int ac_ieks_cost_f32(ac_handle* h, const ac_ekf_opts* o, const float* X0, const float* P0, const float* Xtraj, const float* Utraj,
+                     float dt, const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long reps, long T, float* J,
+                     float* Jprior, float* Jproc, float* Jmeas, int* status, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (reps < 1 || reps > kIeksMaxCand) return fail(AC_ERR_BAD_ARG, "ieks cost: reps must be 1 .. 8");
+    bool go = false;
+    const int rc = ieks_check(h, o, dt, n, T, &go);
+    if (rc != AC_OK || !go) return rc;
+    if (!X0 || !P0 || !Xtraj || !Utraj || !Z || !Qd || !Rd || !J || !status)
+        return fail(AC_ERR_BAD_ARG, "ieks cost: a required pointer is NULL");
+    if (!ws || ws_floats < ieks_cost_floats(n * reps, T)) return fail(AC_ERR_WORKSPACE, "ieks workspace too small: see ac_ieks_workspace_floats");
+    return ieks_cost_impl(h, o, X0, P0, Xtraj, Utraj, dt, Z, mask, Qd, Rd, n, reps, T, J, Jprior, Jproc, Jmeas, status, ws, stream);
+}
+
+int ac_ieks_candidates_f32(ac_handle* h, const float* Xbar, const float* Xs0, const float* Xs, const float* U, const float* ladder,
+                           int candidates, long n, long T, float* Xc, float* Uc, void* stream) {
+    AC_ENTER(h);
+    if (!h || n < 0 || T < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kIeksFixedWing);
+    IeksLadder lad;
+    const int rc = ieks_ladder(ladder, candidates, &lad);
+    if (rc != AC_OK) return rc;
+    if (n == 0 || T == 0) return AC_OK;
+    if (!Xbar || !Xs0 || !Xs || !U || !Xc || !Uc) return fail(AC_ERR_BAD_ARG, "ieks candidates: a required pointer is NULL");
+    const IeksCandIo io{Xbar, Xs0, Xs, U, Xc, Uc, lad, n, T};
+    int grid = 0;
+    AC_HIP(ieks_launch_candidates(io, (hipStream_t)stream, &grid));
+    note_launch(h, "k_ieks_candidates", grid, kIeksBlock, 0);
+    return AC_OK;
+}
+
+int ac_ieks_accept_f32(ac_handle* h, const float* Jcur, const float* Jc, const int* stc, const float* Xc, const float* ladder,
+                       int candidates, long n, long T, float* Xbar, float* alpha, float* Jout, int* status, void* stream) {
+    AC_ENTER(h);
+    if (!h || n < 0 || T < 0) return AC_ERR_BAD_ARG;
+    if (h->dp.p.model_kind == AC_MODEL_QUAD) return fail(AC_ERR_UNSUPPORTED, kIeksFixedWing);
+    IeksLadder lad;
+    const int rc = ieks_ladder(ladder, candidates, &lad);
+    if (rc != AC_OK) return rc;
+    if (n == 0 || T == 0) return AC_OK;
+    if (!Jcur || !Jc || !stc || !Xc || !Xbar || !alpha || !Jout || !status) return fail(AC_ERR_BAD_ARG, "ieks accept: a required pointer is NULL");
+    if (rts_overlap({Jcur, (size_t)n}, {Jout, (size_t)n})) return fail(AC_ERR_BAD_ARG, "ieks accept: Jout overlaps Jcur");
+    const IeksAcceptIo io{Jcur, Jc, stc, Xc, Xbar, alpha, Jout, status, lad, n, T};
+    int grid = 0;
+    AC_HIP(ieks_launch_accept(io, (hipStream_t)stream, &grid));
+    note_launch(h, "k_ieks_accept", grid, kIeksBlock, 0);
+    return AC_OK;
+}
+
+int ac_ieks_solve_f32(ac_handle* h, const ac_ekf_opts* o, const float* X0, const float* P0, float* Xbar, const float* U, float dt,
+                      const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T, int iters, const float* ladder,
+                      int candidates, float* Xs, float* Ps, float* Xs0, float* Ps0, float* Xf, float* Pf, float* ll, float* nu, float* S,
+                      float* nis, int* used, int* fstatus, float* Xpreds, float* Ppreds, float* Abars, float* cost, float* alpha,
+                      int* status, float* ws, size_t ws_floats, void* stream) {
+    AC_ENTER(h);
+    if (iters < 0) return fail(AC_ERR_BAD_ARG, "ieks solve: iters must be >= 0");
+    bool go = false;
+    int rc = ieks_check(h, o, dt, n, T, &go);
+    if (rc != AC_OK) return rc;
+    IeksLadder lad;
+    rc = ieks_ladder(ladder, candidates, &lad);
+    if (rc != AC_OK || !go) return rc;
+    if (!X0 || !P0 || !Xbar || !U || !Z || !Qd || !Rd || !Xs || !Ps || !Xs0 || !Ps0 || !Xf || !Pf || !Xpreds || !Ppreds || !Abars || !cost ||
+        !status || (iters > 0 && !alpha))
+        return fail(AC_ERR_BAD_ARG, "ieks solve: a required pointer is NULL");
+    if (!ws || ws_floats < ieks_ws_floats(n, T, candidates)) return fail(AC_ERR_WORKSPACE, "ieks workspace too small: see ac_ieks_workspace_floats");
+    const IeksWs w(ws, (size_t)n, (size_t)T, (size_t)candidates);
+    const size_t N = (size_t)n;
+    rc = ieks_cost_impl(h, o, X0, P0, Xbar, U, dt, Z, mask, Qd, Rd, n, 1, T, cost, nullptr, nullptr, nullptr, status, w.cost, stream);
+    for (int it = 0; it <= iters && rc == AC_OK; ++it) {
+        rc = ieks_pass_impl(h, o, X0, P0, Xbar, U, dt, Z, mask, Qd, Rd, n, T, Xf, Pf, ll, nu, S, nis, used, fstatus, Xpreds, Ppreds, Abars,
+                            ws, stream);
+        if (rc != AC_OK) break;
+        rc = ac_ekf_smooth_f32(h, X0, P0, Xf, Pf, Xpreds, Ppreds, Abars, n, T, Xs, Ps, Xs0, Ps0, nullptr, w.rst, stream);
+        if (rc != AC_OK || it == iters) break;
+        rc = ac_ieks_candidates_f32(h, Xbar, Xs0, Xs, U, ladder, candidates, n, T, w.Xc, w.Uc, stream);
+        if (rc != AC_OK) break;
+        rc = ieks_cost_impl(h, o, X0, P0, w.Xc, w.Uc, dt, Z, mask, Qd, Rd, n, candidates, T, w.Jc, nullptr, nullptr, nullptr, w.stc, w.cost,
+                            stream);
+        if (rc != AC_OK) break;
+        rc = ac_ieks_accept_f32(h, cost + (size_t)it * N, w.Jc, w.stc, w.Xc, ladder, candidates, n, T, Xbar, alpha + (size_t)it * N,
+                                cost + (size_t)(it + 1) * N, status, stream);
+    }
+    return rc;
 }
 
 // ---- MPPI: sampler and softmin update (ac_mppi.hpp, mppi_inst.hip) ---------------------------------------------------------------

@@ -165,6 +165,28 @@ class EkfSmooth:
 
 
 @dataclass
+class EkfMapSmooth:
+    """What EKF.map_smooth returns (numpy in -> numpy out; tensors stay on the device): the maximum-a-posteriori trajectory of
+    a log by Gauss-Newton, the iterated extended Kalman smoother (include/aircraft_hip.h, ac_ieks_solve_f32).
+    X (T, 13, n), P (T, 12, 12, n), X0 (13, n), P0 (12, 12, n): the smoothed nodes and the smoothed initial node of the last
+    linearised pass, as EkfSmooth's.  cost (iters + 1, n): the MAP cost J of the nominal before the first iteration and after
+    each; alpha (iters, n): the accepted step length of each iteration, 0 where no candidate lowered J.  status (n,): bit 1
+    (value 1) the prior covariance has no Cholesky factor, bit 2 (value 2) a node or J was not finite, bit 3 (value 4) a defect
+    in a row whose q is 0, bit 4 (value 8) an iteration found no decrease (the nominal then stays where it is).  trace: the
+    EkfTrace of the last pass (with Xpred, Ppred, Abar, X0, P0), which EKF.smooth and EKF.noise_stats accept; nominal
+    (T + 1, 13, n): the final nominal, the initial node first."""
+    X: Any
+    P: Any
+    X0: Any
+    P0: Any
+    cost: Any
+    alpha: Any
+    status: Any
+    trace: Any
+    nominal: Any
+
+
+@dataclass
 class EkfNoiseStats:
     """What EKF.noise_stats returns for a recorded filter run and its smoothed trace (numpy in -> numpy out; tensors stay on
     the device): the M-step of an EM estimate of the diagonal Q and R (include/aircraft_hip.h, ac_ekf_em_f32).
@@ -399,6 +421,78 @@ class EKF:
                                          Ab.data_ptr(), n, T, Xs.data_ptr(), Ps.data_ptr(), ptr(Xs0), ptr(Ps0), ptr(Cg), st.data_ptr(),
                                          sysm._stream()), "ac_ekf_smooth_f32")
         return Xs, Ps, Xs0, Ps0, Cg, st
+
+    # ---- MAP trajectory by Gauss-Newton (include/aircraft_hip.h, ac_ieks_solve_f32) -----------------------
+    @staticmethod
+    def _ladder(ladder):
+        try:
+            lad = [float(v) for v in ladder]
+        except (TypeError, ValueError):
+            raise ValueError(f"ekf map_smooth: ladder must be a sequence of numbers, got {ladder!r}") from None
+        if not 1 <= len(lad) <= _lib.IEKS_MAX_CANDIDATES or not all(np.isfinite(v) and 0 < v <= 1 for v in lad) \
+                or any(b >= a for a, b in zip(lad, lad[1:])):
+            raise ValueError(f"ekf map_smooth: ladder must be 1 .. {_lib.IEKS_MAX_CANDIDATES} decreasing values in (0, 1], got {ladder!r}")
+        return lad
+
+    def map_smooth(self, U, dt, Z, mask=None, iters=5, init=None, ladder=(1, .5, .25, .125)) -> EkfMapSmooth:
+        """The maximum-a-posteriori trajectory of a log U (T, 7, n), Z (T, 15, n), mask (T, n) or None, by `iters` Gauss-Newton
+        iterations (the iterated extended Kalman smoother): linearise about a nominal trajectory, one affine filter pass and
+        one RTS sweep, then a line search on the MAP cost over the `ladder` of step lengths.  The bank's (x, P) is the prior of
+        the initial node and is NOT advanced; for a moving horizon slide the window and advance the bank with filter.
+        init: the nominal to start from: None, the bank's own filter(record=True) + smooth on a copy of its state; an array
+        (T + 1, 13, n) (the initial node first); an EkfSmooth with X0; or "rollout", the open-loop rollout of x under U.
+        No host synchronisation.  -> EkfMapSmooth."""
+        torch = _torch_mod()
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+            raise ValueError(f"ekf map_smooth: iters must be an integer >= 0, got {iters!r}")
+        lad = self._ladder(ladder)
+        shape = tuple(Z.shape) if isinstance(Z, torch.Tensor) else np.shape(Z)
+        if len(shape) != (2 if self._vec else 3) or shape[0] < 1:
+            raise ValueError(f"ekf map_smooth: Z must have shape (T, 15, n) with T >= 1, got {shape}")
+        T = shape[0]
+        if isinstance(init, str):
+            if init != "rollout":
+                raise ValueError(f"ekf map_smooth: init must be None, 'rollout', an array (T + 1, 13, n) or an EkfSmooth, got {init!r}")
+        elif isinstance(init, EkfSmooth):
+            if init.X is None or init.X0 is None:
+                raise ValueError("ekf map_smooth: the EkfSmooth carries no X0: run smooth(trace, initial=True)")
+        elif isinstance(init, EkfTrace):
+            raise ValueError("ekf map_smooth: init takes the EkfSmooth of smooth(trace), not the trace")
+        dt, T, Zt, Ut, M = self._filter_args(U, dt, Z, mask)
+        if isinstance(init, EkfSmooth):
+            Xb = torch.cat([self._rows(init.X0, (), 13, "init.X0").unsqueeze(0), self._rows(init.X, (T,), 13, "init.X")]).contiguous()
+        elif init is not None and not isinstance(init, str):
+            Xb = self._rows(init, (T + 1,), 13, "init").clone()
+
+        # ---- device side ----
+        sysm, n, dev = self.system, self.n, self._X.device
+        X0, P0 = self._X, self._P
+        if init is None:
+            tr = self._filter(Ut, dt, Zt, M, T, True)
+            self._X, self._P = X0, P0
+            sm = self._smooth(X0, P0, tr[0], tr[1], tr[8], tr[9], tr[10], T, False)
+            Xb = torch.cat([sm[2].unsqueeze(0), sm[0]]).contiguous()
+        elif isinstance(init, str):
+            Xb = sysm.rollout(X0, Ut, dt).contiguous().clone()
+        lib = sysm._sync()
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        e = lambda *s: torch.empty(s, **f32)  # noqa: E731
+        Xs, Ps, Xs0, Ps0, Xf, Pf = e(T, 13, n), e(T, 12, 12, n), e(13, n), e(12, 12, n), e(T, 13, n), e(T, 12, 12, n)
+        ll, nu, S, nis = e(n), e(T, _lib.EKF_ROWS, n), e(T, _lib.EKF_ROWS, n), e(T, n)
+        used, fst, st = torch.empty((T, n), **i32), torch.empty((T, n), **i32), torch.empty((n,), **i32)
+        Xp, Pp, Ab = e(T, 13, n), e(T, 12, 12, n), e(T, 12, 12, n)
+        cost, alpha = e(int(iters) + 1, n), e(int(iters), n)
+        ws = sysm.ieks_workspace(n, T, len(lad))
+        o = EKF._opts(self, True)
+        cl = (C.c_float * len(lad))(*lad)
+        _lib.check(lib.ac_ieks_solve_f32(sysm._handle, C.byref(o), X0.data_ptr(), P0.data_ptr(), Xb.data_ptr(), Ut.data_ptr(), C.c_float(dt),
+                                         Zt.data_ptr(), None if M is None else M.data_ptr(), self._Qd.data_ptr(), self._Rd.data_ptr(), n, T,
+                                         int(iters), cl, len(lad), *(t.data_ptr() for t in (Xs, Ps, Xs0, Ps0, Xf, Pf, ll, nu, S, nis, used, fst,
+                                                                                           Xp, Pp, Ab, cost, alpha, st)),
+                                         ws.data_ptr(), ws.numel(), sysm._stream()), "ac_ieks_solve_f32")
+        g = self._give
+        trace = EkfTrace(*(g(t) for t in (Xf, Pf, nu, S, nis, ll, used, fst, Xp, Pp, Ab, X0, P0)))
+        return EkfMapSmooth(g(Xs), g(Ps), g(Xs0), g(Ps0), g(cost), g(alpha), g(st), trace, g(Xb))
 
     # ---- EM estimate of q and r (include/aircraft_hip.h, ac_ekf_em_f32; DESIGN.md §4.17) ---------------------------------
     @staticmethod
@@ -1105,6 +1199,14 @@ class Aircraft(SixDOF):
         lib = self._sync()
         need = C.c_size_t()
         _lib.check(lib.ac_ekf_em_workspace_floats(self._handle, int(n), int(T), C.byref(need)), "ac_ekf_em_workspace_floats")
+        return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
+
+    def ieks_workspace(self, n: int, T: int, candidates: int):
+        """Device workspace of EKF.map_smooth over n instances, T steps and a ladder of `candidates` step lengths
+        (ac_ieks_workspace_floats)."""
+        lib = self._sync()
+        need = C.c_size_t()
+        _lib.check(lib.ac_ieks_workspace_floats(self._handle, int(n), int(T), int(candidates), C.byref(need)), "ac_ieks_workspace_floats")
         return _torch_mod().empty(max(need.value, 1), device=self._device_obj(), dtype=_torch_mod().float32)
 
     def ukf_workspace(self, n: int):

@@ -882,6 +882,71 @@ int ac_ekf_em_f32(ac_handle* h, const ac_ekf_em_opts* o, const float* Xpred /* [
                   int* status /* [T][n] */, float* Qn /* [12][n] | NULL */, float* Rn /* [15][n] | NULL */, float* ws,
                   size_t ws_floats, void* stream);
 
+/* ---- iterated extended Kalman smoother: Gauss-Newton on the MAP trajectory of a log (fixed-wing models) ----------
+ * Nominal Xbar [T+1][13][n]: Xbar[0] is node -1 (the initial node), Xbar[k+1] is filter node k.  Prior (X0, P0); U, Z, mask, Qd, Rd as
+ * in ac_ekf_filter_rec_f32; [+] / [-] the filter's chart and its inverse.  MAP cost per instance J = Jprior + Jproc + Jmeas:
+ *     Jprior = 1/2 e0' P0^-1 e0, e0 = Xbar[0] [-] X0 (plain Cholesky of P0, its lower triangle is read, one triangular solve);
+ *     Jproc  = 1/2 sum_k sum_j w_kj^2 / Qd_j, w_k = Xbar[k+1] [-] F(Xbar[k], U_k, dt); a row with Qd_j = 0 adds nothing and sets
+ *              status bit 4 when w_kj != 0;
+ *     Jmeas  = 1/2 sum_k sum_{used i} (z_ki - h_i(Xbar[k+1]))^2 / Rd_i, a row being used when its mask bit is set and z is finite.
+ * ac_ieks_pass_f32: one linearised pass about Xbar.  One sensitivity launch over the T n units writes F_k, A_k into the workspace;
+ *   k_ieks_filter runs the whole forward recursion in one launch, one instance per 16-lane group, the deviation d (R^12, about
+ *   the nominal) and P in registers from step to step, from d = X0 [-] Xbar[0], P = P0.  Step k: Abar_k = E(F_k) A_k G(Xbar[k]) (the
+ *   filter's expression and operation order), c_k = F_k [-] Xbar[k+1], d- = c_k + Abar_k d, P- = 1/2 (X + X') + diag(Qd) with
+ *   X = Abar P Abar' (ac_ekf_step_f32's bits on equal operands); nu_i = z_i - h_i(Xbar[k+1]) and H AT THE NOMINAL; the fifteen
+ *   scalar updates in row order with ac_ekf_step_f32's recursion and rejection rule, from d = d- (rho = nu_i - h_i d).  Records in
+ *   ac_ekf_filter_rec_f32's shapes: Xs[k] = Xbar[k+1] [+] d_k, Ps[k], Xpreds[k] = Xbar[k+1] [+] d-_k, Ppreds[k], Abars[k], nu, S, nis,
+ *   used, status [T][n] (ac_ekf_step_f32's bits), ll [n] summed in step order; ll, nu, S, nis, used, status may be NULL.  No reset
+ *   Jacobian and no chart-change Jacobian is applied: re-basing the deviation from F_k to Xbar[k+1] is the first-order `+ c_k`, so
+ *   a fixed point of the iteration is stationary for J to second order in the deviations only.  A step whose Xbar[k], Xbar[k+1],
+ *   F_k, A_k, d- or P- is not finite sets status bit 2 (value 2): no row is applied at that node (used 0), and the recursion
+ *   restarts there from d = 0, P = P- if all of P- is finite, else P0; Xs[k] = Xbar[k+1] bit for bit, Ps[k] = that P.
+ *   ac_ekf_smooth_f32 on these records with (X0, P0) gives the smoothed trajectory; ac_ekf_em_f32 runs on them as on the filter's.
+ * ac_ieks_cost_f32: J of reps n trajectories Xtraj [T+1][13][reps n] under Utraj [T][7][reps n]; the data of column c are those of
+ *   instance c mod n.  A plain step launch supplies F; k_ieks_cost_nodes runs over (blocks of columns) x (chunks of 32 consecutive
+ *   nodes), per-node terms float32, float64 sums in node order; k_ieks_cost_reduce sums the chunks in chunk order, adds Jprior and
+ *   rounds to float32 once.  J [reps n]; Jprior, Jproc, Jmeas [reps n] or NULL; status [reps n]: bit 1 (value 1) P0 has no Cholesky
+ *   factor, bit 2 (value 2) a node, an F or J is not finite, bit 3 (value 4) a defect in a row with Qd_j = 0.
+ * ac_ieks_candidates_f32: Xc [T+1][13][C n], column c n + i = Xbar [+] ladder[c] (X^s [-] Xbar) per node (X^s: Xs0 for node -1, Xs [T][13][n]
+ *   for the others), and Uc [T][7][C n], U replicated.  ladder: C host floats, 1 <= C <= 8.
+ * ac_ieks_accept_f32: per instance the first c with Jc[c n + i] < Jcur[i] and status bit 2 of stc[c n + i] clear: its columns of Xc
+ *   are copied into Xbar, alpha[i] = ladder[c], Jout[i] = Jc[c n + i], status[i] |= stc[c n + i]; none: Xbar is kept, alpha[i] = 0,
+ *   Jout[i] = Jcur[i], status[i] |= 8 (no decrease).  status [n] is read and written.  Jout must not overlap Jcur.
+ * ac_ieks_solve_f32: `iters` Gauss-Newton iterations as a host loop of the calls above from the caller's Xbar, which is updated in
+ *   place: cost[0] = J(Xbar) and status = its bits; per iteration pass, ac_ekf_smooth_f32, candidates, one step launch and one cost
+ *   over the C n candidates, accept -> alpha[it], cost[it+1]; then one more pass and smoother at the final Xbar.  Outputs: the final
+ *   smoothed Xs [T][13][n], Ps, Xs0, Ps0; that last pass's records Xf, Pf, ll, nu, S, nis, used, fstatus, Xpreds, Ppreds, Abars;
+ *   cost [iters+1][n], alpha [iters][n], status [n].  Every output is bit-equal to issuing the single calls in that order.  An
+ *   instance without a decrease stays where it is: the same nominal gives the same pass, candidates and decision again.
+ * No atomics, every sum in a fixed order: an instance's bits depend neither on n, on reps nor on its place in the batch.
+ * ws / ws_floats: caller-owned device scratch of at least ac_ieks_workspace_floats(h, n, T, candidates) floats (the pass ignores
+ * `candidates`; the cost needs candidates >= reps), else AC_ERR_WORKSPACE.  AC_ERR_UNSUPPORTED for the quadrotor; AC_ERR_BAD_ARG
+ * for n < 0, T < 0, reps < 1, iters < 0, a ladder that is not 1 .. 8 finite values in (0, 1], a NULL required pointer, or dt not
+ * finite and > 0; n == 0 or T == 0 is AC_OK and launches nothing.  Asynchronous, no allocation, no synchronisation,
+ * hipGraph-capturable. */
+int ac_ieks_workspace_floats(const ac_handle* h, long n, long T, int candidates, size_t* floats);
+int ac_ieks_pass_f32(ac_handle* h, const ac_ekf_opts* o, const float* X0 /* [13][n] */, const float* P0 /* [12][12][n] */,
+                     const float* Xbar /* [T+1][13][n] */, const float* U /* [T][7][n] */, float dt, const float* Z /* [T][15][n] */,
+                     const int* mask /* [T][n] | NULL */, const float* Qd, const float* Rd, long n, long T, float* Xs, float* Ps,
+                     float* ll, float* nu, float* S, float* nis, int* used, int* status, float* Xpreds, float* Ppreds, float* Abars,
+                     float* ws, size_t ws_floats, void* stream);
+int ac_ieks_cost_f32(ac_handle* h, const ac_ekf_opts* o, const float* X0, const float* P0, const float* Xtraj /* [T+1][13][reps n] */,
+                     const float* Utraj /* [T][7][reps n] */, float dt, const float* Z, const int* mask, const float* Qd,
+                     const float* Rd, long n, long reps, long T, float* J /* [reps n] */, float* Jprior, float* Jproc, float* Jmeas,
+                     int* status /* [reps n] */, float* ws, size_t ws_floats, void* stream);
+int ac_ieks_candidates_f32(ac_handle* h, const float* Xbar, const float* Xs0 /* [13][n] */, const float* Xs /* [T][13][n] */,
+                           const float* U, const float* ladder /* host, [candidates] */, int candidates, long n, long T,
+                           float* Xc /* [T+1][13][C n] */, float* Uc /* [T][7][C n] */, void* stream);
+int ac_ieks_accept_f32(ac_handle* h, const float* Jcur /* [n] */, const float* Jc /* [C n] */, const int* stc /* [C n] */,
+                       const float* Xc, const float* ladder, int candidates, long n, long T, float* Xbar, float* alpha /* [n] */,
+                       float* Jout /* [n] */, int* status /* [n], in and out */, void* stream);
+int ac_ieks_solve_f32(ac_handle* h, const ac_ekf_opts* o, const float* X0, const float* P0, float* Xbar /* in and out */,
+                      const float* U, float dt, const float* Z, const int* mask, const float* Qd, const float* Rd, long n, long T,
+                      int iters, const float* ladder, int candidates, float* Xs, float* Ps, float* Xs0, float* Ps0, float* Xf,
+                      float* Pf, float* ll, float* nu, float* S, float* nis, int* used, int* fstatus, float* Xpreds, float* Ppreds,
+                      float* Abars, float* cost /* [iters+1][n] */, float* alpha /* [iters][n] */, int* status /* [n] */, float* ws,
+                      size_t ws_floats, void* stream);
+
 /* ---- flight modes: eigenvalues of the trim linearisation ---------------------------------------------------------
  * ac_eig_f32 (any handle): the eigenvalues of n real m x m matrices M [m][m][n], 1 <= m <= 13, float32 in and out with float64
  * arithmetic between (the eigenvalues carry the rounding of the output, 6e-8, not the matrix's conditioning), one instance per
