@@ -27,7 +27,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // The sensitivity engines of the two headline kernels (k_nn_step_sens<8, true>, k_nn_step_sens_pair<8>) run their hidden
 // layers on bf16 MFMA with three-plane operands (MlpEngine::layer_bf).  -DAC_HIDDEN_FP32 (in those two units
-// AND in aircraft_hip.hip, which then hands them plan_sens) builds the fp32 form of round 4 for A/B measurements.
+// AND in abi_core.hip, which then hands them plan_sens) builds the fp32 form of round 4 for A/B measurements.
 #ifdef AC_HIDDEN_FP32
 constexpr bool kBf16Hidden = false;
 #else

@@ -1,6 +1,6 @@
 // ac_mlp_model.hpp — everything ac_set_mlp computes on the host before it touches the device: the folded net, the packed
 // weight blob, the LDS plans of every kernel family, and the weight image of the tiled vector-ALU engine.  Plain C++ (no
-// HIP): aircraft_hip.hip uploads what build_mlp_model returns, and tests/test_mlp_model_host.py checks it with g++ alone.
+// HIP): abi_core.hip uploads what build_mlp_model returns, and tests/test_mlp_model_host.py checks it with g++ alone.
 #pragma once
 #include <algorithm>
 #include <cstdio>

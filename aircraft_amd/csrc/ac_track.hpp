@@ -11,16 +11,9 @@
 // (flags from ac_set_track).  Outside [0,1] the position is the end knot and the tangent is zero (:821-823).
 #pragma once
 #include "ac_math.hpp"
+#include "ac_track_dev.hpp"  // TrackDev
 
 namespace ac {
-
-struct TrackDev {
-    const float* __restrict__ coef;  // [nseg][3][4]
-    const float* __restrict__ knot_exact;  // [nseg + 1]: 1 where the knot's float64 value is an fp32 number
-    int nseg;
-    float inv_length;   // 1 / track.length()
-    float end_pos[3];   // track.eval(1.0), the terminal-alignment target (moving_horizon.py:91)
-};
 
 struct MhttWeights {  // moving_horizon.py:47-55
     float w_tracking, w_progress, w_progress_rate, w_backward, w_terminal_align, w_low_velocity, w_control;

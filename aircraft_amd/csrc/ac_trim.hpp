@@ -10,7 +10,7 @@
 //     r_v  = q^-1 f[3:6] q - w_b x v_b                    (body-axis rate of change of the velocity vector)
 //     r_w  = f[10:13]                                     (f = state_derivative(x, u))
 // r = 0 exactly when body velocity and body rates are constant.  Damped Gauss-Newton (Levenberg-Marquardt) with box
-// projection, a fixed number of iterations, each one three launches (aircraft_hip.hip, ac_trim_f32):
+// projection, a fixed number of iterations, each one three launches (abi_flight.hip, ac_trim_f32):
 //   k_trim_assemble     z -> X [13][n], U [7][n] in the workspace (one lane per instance)
 //   derivative sens.    the handle's own ac_state_derivative_sens_f32 launch: Xdot, Fx [13][13][n], Fu [13][7][n]
 //   k_trim_update       r and J_z = dr/dz (a Dual<6> seeded in z: f's tangent is Fx dx/dz + Fu du/dz, pushed through

@@ -1,5 +1,5 @@
 """The rollout-engine matrix: one row per template instance that ac_rollout_f32 / ac_rollout_policy_f32 can pick for an MLP
-surrogate (aircraft_amd/csrc/aircraft_hip.hip), plus the analytic models and the quadrotor for the closed loop.
+surrogate (aircraft_amd/csrc/abi_core.hip and abi_ilqr.hip), plus the analytic models and the quadrotor for the closed loop.
 
 The host picks by the FOLDED net:  wt = 2, 4 or 8 register tiles for a largest hidden width <= 32, <= 64 or <= 128;
 nh = folded layers - 2 hidden x hidden layers.  With the matrix cores on, 1 <= nh <= 3 takes the register-resident engine

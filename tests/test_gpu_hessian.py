@@ -23,7 +23,7 @@ def rel_block(got, want):
 
 
 def nn_route(hidden, use_mfma=True, n_products=None):
-    """The stage-tensor kernel hess_single (aircraft_hip.hip) dispatches for a net (widths after the fold of activation-free
+    """The stage-tensor kernel hess_single (abi_hess.hip) dispatches for a net (widths after the fold of activation-free
     layers), then k_step_hess: last_launch() names only the latter.  Register tiles per slab: width <= 32 -> 2, <= 64 -> 4,
     else 8; width 128 takes the reverse sweep for one to three hidden products, the slab kernel and its cross-pair launch for
     more (matrix cores only)."""

@@ -24,6 +24,36 @@ def test_library_exports_every_declared_symbol():
     assert lib.ac_version().startswith(b"aircraft_hip")
 
 
+def test_abi_units_compile_every_kernel_once(tmp_path):
+    """The C ABI is split over the abi_*.hip units behind ac_abi.hpp.  With -fno-gpu-rdc a kernel that two of them instantiate
+    links silently and doubles its code object, so the sets of kernels the units compile must be pairwise disjoint, and the
+    header they all include must define none."""
+    import glob
+    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+
+    from aircraft_amd import build as B
+
+    assert "__global__" not in open(os.path.join(B.CSRC, "ac_abi.hpp")).read()
+    units = sorted(glob.glob(os.path.join(B.CSRC, "abi_*.hip")))
+    assert len(units) >= 2
+
+    def kernels(src):
+        name = os.path.basename(src)[:-4]
+        out = str(tmp_path / (name + ".s"))
+        subprocess.run(["hipcc", *B.CFLAGS, *B.UNIT_FLAGS.get(name, []), "-S", "--cuda-device-only", src, "-o", out], check=True,
+                       capture_output=True)
+        return name, set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", open(out).read(), re.M))
+
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        got = dict(ex.map(kernels, units))
+    assert any(got.values()), "no kernel parsed"
+    names = sorted(got)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            assert not (got[a] & got[b]), (a, b, sorted(got[a] & got[b]))
+
+
 def test_struct_layout_matches_header():
     from aircraft_amd import _lib
 

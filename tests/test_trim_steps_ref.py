@@ -53,7 +53,7 @@ def test_layout_matches_the_header():
     assert [int(const(c)) for c in ("AC_TRIM_CONVERGED", "AC_TRIM_MAXITER", "AC_TRIM_BOUND", "AC_TRIM_NONFINITE")] == [0, 1, 2, 3]
     assert "lam * (1.0f / 3.0f)" in h and "lam * 4.0f" in h
     # the carving in ac_trim_f32
-    src = open(os.path.join(CSRC, "aircraft_hip.hip")).read()
+    src = "".join(open(os.path.join(CSRC, f)).read() for f in ("ac_abi.hpp", "abi_flight.hip"))  # (align256: ac_abi.hpp)
     assert re.search(r"kTrimWsPad\s*=\s*6\s*\*\s*64;", src) and T.WS_PAD == 6 * 64
     assert "(((uintptr_t)p + 255) & ~(uintptr_t)255)" in src
     carve = re.findall(r"float\* (\w+) = align256\(([^;]*)\);", src)
